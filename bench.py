@@ -7,9 +7,13 @@ already resident in HBM.
 
 N = 1 (default): BASELINE.json configs[1] -- das, 8 mics, 1024-pt FFT / hop 512, one
 65 536-frame batch, computed in DOUBLE like the reference (das.cpp:16-24: std::complex<double>, FFTW double plans):
-das_f64_pair_kernel (das_f64_w64.hip).  `extra` carries the fused fp32 kernel on the same batch (`das_f32`, with its own roofline
-block; --das-f32 makes it the headline) and one line per other BASELINE config (mvdr 8-mic, phasempf 256 x 256,
-lcmv 16-mic K = 3 per-GPU shard).
+das_f64_pair_kernel (das_f64_w64.hip); --das-f32 makes the fused fp32 kernel the headline.
+
+A plain run sets up, warms up, times the K steps, writes the last step's output if --dump-outputs is given and prints
+the line.  --full adds everything the headline figure does not need: `cpu_baseline` (the oracle on one host core and
+on all of them), `roofline` (per-launch kernel events inside the timed steps, the launched kernels, PMC traffic) and
+`extra` (the fused fp32 kernel on the same batch as `das_f32`, with its own roofline block, and one line per other
+BASELINE config: mvdr 8-mic, phasempf 256 x 256, lcmv 16-mic K = 3 per-GPU shard, ...).
 
 N > 1 (`--gpus N`, one rank per GPU over torch.distributed / RCCL): ONE global stream is cut into
 contiguous frame ranges by beamform_amd.shard.plan; every rank holds only its slice (its owned hops
@@ -39,6 +43,21 @@ NFFT = 1024
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy ceiling)
 FP64_VECTOR_PEAK_TF = 78.6  # AMD's public MI355X FP64 vector figure (not in the guide)
 GATHER_TIMEOUT_RC = 3       # exit code of every rank when the gather watchdog fires (the compute-only line is printed first)
+DUMP_BYTES = 32 << 20       # --dump-outputs: bytes written per run at most (the headline's output is 128 MiB)
+
+
+def dump_output(directory: str, name: str, y, max_bytes: int) -> None:
+    """Write `y` (a float32 device tensor of whole hops) as directory/<name>.npy: whole when it fits max_bytes, otherwise the hops
+    numpy.random.default_rng(0) picks without replacement, in stream order, as an array [hops, HOP].  The pick depends only
+    on the output's size, so two runs with the same arguments write the same hops."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    if y.numel() * 4 > max_bytes:
+        hops = y.reshape(-1, HOP)
+        pick = np.sort(np.random.default_rng(0).choice(hops.shape[0], max_bytes // (HOP * 4), replace=False))
+        y = hops.index_select(0, torch.from_numpy(pick).to(y.device))
+    np.save(os.path.join(directory, f"{name}.npy"), y.cpu().numpy().astype(np.float32, copy=False))
 
 
 def algorithmic_bytes_per_frame(n_mics: int) -> int:
@@ -247,12 +266,17 @@ def main():
                          "hangs on hardware this build never saw must not cost the run its compute figures, and must not pass as a success")
     ap.add_argument("--pieces", type=int, default=4)
     ap.add_argument("--dump-gathered", default="", help="rank 0 writes the stream its final gather assembled (float32 .npy): for tests")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the output of the last one as DIR/y.npy (DIR/y_rank<r>.npy at N > 1; float32):\n"
+                         "whole when it fits DUMP_BYTES, otherwise a fixed seeded sample of whole hops (see dump_output)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: cpu_baseline, roofline, extra (secondary lines)")
     ap.add_argument("--cpu-frames", type=int, default=196608,
-                    help="frames in the CPU-baseline sample (0 = skip); the default is ~12 s of single-core work (its oracle, with the FFT plan cached, does ~16 k frames per second)")
-    ap.add_argument("--no-cpu", action="store_true")
+                    help="--full: frames in the CPU-baseline sample (0 = skip); the default is ~12 s of single-core work (its oracle, with the FFT plan cached, does ~16 k frames per second)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--cpu-all-cores-frames", type=int, default=40960,
-                    help="frames per host core in the all-cores CPU baseline (0 = skip): ~2.5 s per worker at the oracle's ~16 k frames/s")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary lines (other BASELINE configs)")
+                    help="--full: frames per host core in the all-cores CPU baseline (0 = skip): ~2.5 s per worker at the oracle's ~16 k frames/s")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the secondary lines (other BASELINE configs)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -276,10 +300,10 @@ def main():
     from beamform_amd.params import make_params
     from beamform_amd.synth import stream_noise
 
-    # CPU baselines first (rank 0, N = 1 only): the all-cores pool forks, which must happen before this process
+    # CPU baselines first (--full, rank 0, N = 1 only): the all-cores pool forks, which must happen before this process
     # initialises the GPU; the untimed settle phase below brings the clocks back up afterwards
     cpu_line = None
-    if world == 1 and not force_dist and not args.no_cpu and args.cpu_frames > 0:
+    if args.full and world == 1 and not force_dist and not args.no_cpu and args.cpu_frames > 0:
         cpu_line = cpu_baseline(args.algo, args.mics, args.cpu_frames)
         if args.cpu_all_cores_frames > 0:
             try:
@@ -428,26 +452,24 @@ def main():
     for _ in range(args.warmup):
         step()
     from beamform_amd.capi import launch_trace
-    with launch_trace() as tr0:   # which kernels a step launches (untimed): `traffic` is printed only beside the kernels it was taken on
-        step()
-    launched_headline = tr0.kernels
-    # the K timed steps, with every launch of the dominant kernel bracketed by its own HIP event pair on the launch stream: the
-    # roofline duration comes from the very launches the step time covers (so kernel_ms <= ms_per_step by construction)
-    bf.kernel_timing_begin()
+    if args.full:
+        with launch_trace() as tr0:   # which kernels a step launches (untimed): `traffic` is printed only beside the kernels it was taken on
+            step()
+        launched_headline = tr0.kernels
+        # the K timed steps, with every launch of the dominant kernel bracketed by its own HIP event pair on the launch stream: the
+        # roofline duration comes from the very launches the step time covers (so kernel_ms <= ms_per_step by construction)
+        bf.kernel_timing_begin()
     dt = timed(args.steps)
-    ms_kernel, n_timed_launches = bf.kernel_timing_end()
+    if args.full:
+        ms_kernel, n_timed_launches = bf.kernel_timing_end()
     ms_call = dt / args.steps * 1e3
+    if args.dump_outputs:
+        dump_output(args.dump_outputs, "y" if world == 1 else f"y_rank{rank}", y_own if sharded else y, DUMP_BYTES // world)
+
     def make_line(dt_g, dt_o, gather_error, extra):
         """The one JSON line (rank 0).  Called at the end -- or by the gather watchdog with what has been measured so far."""
         frames_total = frames_per_step_all_ranks * args.steps
         value = frames_total / dt
-        bpf = algorithmic_bytes_per_frame(M)
-        units_per_launch = S * n_feed
-        # fused das: its one kernel; the other nodes run a chain of kernels (stft -> per-bin -> istft): the chain's duration
-        k_ms = ms_kernel if ms_kernel > 0 else ms_call
-        achieved = bpf * units_per_launch / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-        tag = f"{args.algo}{M}" + ("_f64" if das_impl == BF_DAS_F64 else "")
-        traffic, traffic_note = (load_traffic(tag, launched_headline) if (n_feed == 65536 and S == 1 and args.layout == "planar") else (None, None))
         if sharded:
             shl = shard.plan(F_total, world, world - 1, halo)
             wl = (f"{args.algo} {M}-mic 1024-pt (hop 512), ONE {F_total}-frame stream frame-sharded x{world} by shard.plan "
@@ -477,28 +499,37 @@ def main():
                                     if M <= 16 else "explicit"),
                        "microphones_with_identical_weight_rows": dup_rows,
                        "forward_transforms_per_frame_pair": ((M - 1 - (1 if dup_rows else 0)) if (args.algo == "das" and das_impl == BF_DAS_F64 and args.layout == "planar") else None)},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         # PMC traffic exists for the profiled workloads only (profiles/traffic_<tag>.json), and only while the
-                         # file's kernels are the ones this run launched
-                         "traffic": traffic,
-                         "kernel": ("das_fused_kernel" if das_impl == BF_DAS_FUSED_F32 else ("das_f64_pair_kernel" if args.layout == "planar" else "das_f64_ring_kernel")) if args.algo == "das"
-                                   else "bin pipeline (stft + per-bin kernel + istft)",
-                         "kernels_launched_per_step": sorted({norm_kernel_name(k) for k in launched_headline}),
-                         "kernel_ms": k_ms, "call_ms": ms_call, "kernel_launches_timed": n_timed_launches,
-                         "kernel_ms_source": "one HIP event pair per launch on the launch stream, inside the K timed steps",
-                         "algorithmic_bytes_per_frame": bpf,
-                         "frames_per_launch": units_per_launch, "frac_of_measured_copy_ceiling_6290": achieved / 6290.0},
         }
-        if traffic_note:
-            out["roofline"]["traffic_stale"] = traffic_note
+        if args.full:
+            bpf = algorithmic_bytes_per_frame(M)
+            units_per_launch = S * n_feed
+            # fused das: its one kernel; the other nodes run a chain of kernels (stft -> per-bin -> istft): the chain's duration
+            k_ms = ms_kernel if ms_kernel > 0 else ms_call
+            achieved = bpf * units_per_launch / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+            tag = f"{args.algo}{M}" + ("_f64" if das_impl == BF_DAS_F64 else "")
+            traffic, traffic_note = (load_traffic(tag, launched_headline) if (n_feed == 65536 and S == 1 and args.layout == "planar") else (None, None))
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS,
+                               # PMC traffic exists for the profiled workloads only (profiles/traffic_<tag>.json), and only while the
+                               # file's kernels are the ones this run launched
+                               "traffic": traffic,
+                               "kernel": ("das_fused_kernel" if das_impl == BF_DAS_FUSED_F32 else ("das_f64_pair_kernel" if args.layout == "planar" else "das_f64_ring_kernel")) if args.algo == "das"
+                                         else "bin pipeline (stft + per-bin kernel + istft)",
+                               "kernels_launched_per_step": sorted({norm_kernel_name(k) for k in launched_headline}),
+                               "kernel_ms": k_ms, "call_ms": ms_call, "kernel_launches_timed": n_timed_launches,
+                               "kernel_ms_source": "one HIP event pair per launch on the launch stream, inside the K timed steps",
+                               "algorithmic_bytes_per_frame": bpf,
+                               "frames_per_launch": units_per_launch, "frac_of_measured_copy_ceiling_6290": achieved / 6290.0}
+            if traffic_note:
+                out["roofline"]["traffic_stale"] = traffic_note
         out["n_ranks_seen"] = n_ranks_seen
         if force_dist:
             out["forced_dist"] = ("BF_BENCH_FORCE_DIST=1: the N > 1 code path on a one-rank RCCL group (every piece of the overlapped gather sent "
                                   "to and received from rank 0 itself); an execution check, not a scaling result")
         if gather_error:
             out["gather_error"] = gather_error
-        out["cpu_baseline"] = cpu_line  # None at N > 1 (the contract asks for it on rank 0 at N = 1 only)
+        if args.full:
+            out["cpu_baseline"] = cpu_line  # None at N > 1 (the contract asks for it on rank 0 at N = 1 only)
         if extra:
             out["extra"] = extra
         return out
@@ -628,7 +659,7 @@ def main():
         return line
 
     extra = None
-    if rank == 0 and world == 1 and not force_dist and args.algo == "das" and not args.no_extra and S == 1 and layout == BF_PLANAR:
+    if args.full and rank == 0 and world == 1 and not force_dist and args.algo == "das" and not args.no_extra and S == 1 and layout == BF_PLANAR:
         extra = {}
         noise = ("input = uniform noise in [-0.5, 0.5): every in-band bin passes the magnitude gate, so every bin-frame "
                  "takes the covariance solve (the worst case; real scenes close part of the gates)")

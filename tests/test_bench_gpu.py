@@ -38,7 +38,7 @@ def _check_line(d, n, dtype="f64"):
 
 
 def test_bench_single_gpu_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + ["--cpu-frames", "256", "--cpu-all-cores-frames", "512"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + ["--full", "--cpu-frames", "256", "--cpu-all-cores-frames", "512"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json(out.stdout)
@@ -51,16 +51,49 @@ def test_bench_single_gpu_line():
 
 
 def test_bench_fp32_headline_on_request():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + ["--no-cpu", "--das-f32"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + ["--full", "--no-cpu", "--das-f32"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     _check_line(_last_json(out.stdout), 1, dtype="f32")
 
 
+def test_bench_plain_line_and_dumped_output(tmp_path):
+    """Without --full the line carries the headline figures only (no CPU baselines, roofline or secondary lines), and
+    --dump-outputs writes what the last timed step computed: here the whole 4096-frame output, which must be the output of the same
+    seeded input through the same node in this process, bit for bit.  This checks that the dump is faithful (whole output, float32,
+    bytes as computed); that the output is right is the parity tests' job.  It relies on das in double giving the same bytes on every
+    launch, and on every step after the first seeing the same stream state (the same batch again): so it cannot tell the last step
+    from any other step after the first, and does not try to."""
+    import numpy as np
+    import torch
+    from beamform_amd.capi import BF_DAS_F64, Beamformer
+    from beamform_amd.params import make_params
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + ["--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = _last_json(out.stdout)
+    assert d["metric"] == "stft_frames_per_sec" and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 4096 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+    assert not {"roofline", "cpu_baseline", "extra"} & set(d)
+    assert sorted(os.listdir(tmp_path)) == ["y.npy"]
+    got = np.load(tmp_path / "y.npy")
+    assert got.dtype == np.float32 and got.shape == (1, 4096 * 512)
+    g = torch.Generator(device="cuda:0").manual_seed(1234)   # bench.py's input for rank 0
+    x = torch.rand((1, 8, 4096 * 512), device="cuda:0", generator=g, dtype=torch.float32) - 0.5
+    y = torch.empty((1, 4096 * 512), device="cuda:0", dtype=torch.float32)
+    bf = Beamformer(make_params("das", n_mics=8), das_impl=BF_DAS_F64)
+    for _ in range(2):   # every step continues the stream of the step before it: the last one follows a pass over the same batch
+        bf.process_device(x.data_ptr(), 4096, y.data_ptr())
+    torch.cuda.synchronize()
+    bf.close()
+    assert np.array_equal(got, y.cpu().numpy())
+
+
 def test_bench_two_ranks_through_the_launcher():
     env = dict(os.environ, BF_BENCH_ONE_DEVICE="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29653", os.path.join(ROOT, "bench.py"), "--gpus", "2"] + SMALL + ["--no-cpu"]
+           "--master-port", "29653", os.path.join(ROOT, "bench.py"), "--gpus", "2"] + SMALL + ["--full", "--no-cpu"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json(out.stdout)

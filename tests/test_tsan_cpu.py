@@ -1,6 +1,6 @@
 """ThreadSanitizer run of libbfcore's HOST control plane (tests/host_tsan): one thread hammers bf_set_theta /
 bf_set_interference / bf_get_weights / checkpoints while another drives bf_process_hop -- the reference's ROS-callback
-thread against its JACK thread (das.cpp:94-99 vs :72-92, lcmv.cpp:258-309 vs :142-162).  g++ -fsanitize=thread build
+thread against its JACK thread (das.cpp:94-99 vs :72-92, lcmv.cpp:258-309 vs :142-162).  clang++ -Xarch_host -fsanitize=thread build
 of capi.cpp + config.cpp + pipeline.hip against a host stand-in for the HIP runtime; kernels are stubs that only read
 the tables a launch was given and check that every batch saw ONE consistent {column count, steering table}."""
 import os
