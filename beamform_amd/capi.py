@@ -33,7 +33,9 @@ EXPORTS = (
     "bf_resampler_create", "bf_resampler_set_table", "bf_resampler_reset", "bf_resampler_out_count", "bf_resampler_latency",
     "bf_resampler_process_device", "bf_resampler_process", "bf_resampler_destroy", "bf_resampler_default_table",
     "bf_resampler_set_mode", "bf_resampler_callback", "bf_resampler_callback_device",
+    "bf_doa_create", "bf_doa_set_phat_floor", "bf_doa_process_device", "bf_doa_process", "bf_doa_reset", "bf_doa_destroy",
 )
+BF_DOA_MAX_ANGLES = 1024
 
 
 class BfConfig(C.Structure):
@@ -188,6 +190,14 @@ def load():
     L.bf_resampler_set_mode.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.bf_resampler_callback.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bf_resampler_callback_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]
+    L.bf_doa_create.argtypes = [C.POINTER(BfConfig), C.POINTER(C.c_double), C.c_int, C.c_double, C.c_double, C.c_int,
+                                C.POINTER(C.c_void_p)]
+    L.bf_doa_set_phat_floor.argtypes = [C.c_void_p, C.c_double]
+    L.bf_doa_process_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bf_doa_process.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.bf_doa_reset.argtypes = [C.c_void_p]
+    L.bf_doa_destroy.argtypes = [C.c_void_p]
+    L.bf_doa_destroy.restype = None
     _lib = L
     return L
 
@@ -537,3 +547,59 @@ class Beamformer:
 
     def set_state(self, blob: bytes):
         self._chk(self._L.bf_set_state(self._h, blob, len(blob)), "bf_set_state")
+
+
+class Doa:
+    """SRP-PHAT direction-of-arrival maps (bf_doa_*): per block of `frames_per_block` frames, the PHAT-weighted steered response
+    power of every angle in `angles` (degrees) over the band [freq_lo, freq_hi] Hz, and the index of the best angle.  `params`
+    supplies the geometry, hop and sample rate (a beamform_amd.params dict); the angle of a peak is what das takes in set_theta."""
+
+    def __init__(self, params: dict, angles, freq_lo: float, freq_hi: float, frames_per_block: int, device: int = 0,
+                 n_streams: int = 1, layout: int = BF_PLANAR, phat_floor: float = None):
+        self._L = load()
+        self.cfg = config_from_params(params, device, n_streams, layout)
+        self.angles = np.ascontiguousarray(angles, np.float64).ravel()
+        self.M, self.H = params["n_mics"], params["hop"]
+        self.W, self.n_streams = int(frames_per_block), n_streams
+        self._h = C.c_void_p()
+        a = self.angles.ctypes.data_as(C.POINTER(C.c_double)) if self.angles.size else None
+        rc = self._L.bf_doa_create(C.byref(self.cfg), a, int(self.angles.size), float(freq_lo), float(freq_hi), self.W,
+                                   C.byref(self._h))
+        if rc:
+            raise BfError(rc, "bf_doa_create", self._L.bf_last_error(None).decode())
+        if phat_floor is not None:
+            self.set_phat_floor(phat_floor)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.bf_doa_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def _chk(self, rc, what):
+        if rc:
+            raise BfError(rc, what, (self._L.bf_last_error(None) or b"").decode() or self._L.bf_strerror(rc).decode())
+
+    def set_phat_floor(self, eps: float):
+        self._chk(self._L.bf_doa_set_phat_floor(self._h, float(eps)), "bf_doa_set_phat_floor")
+
+    def reset(self):
+        self._chk(self._L.bf_doa_reset(self._h), "bf_doa_reset")
+
+    def process(self, x: np.ndarray):
+        """Host batch, layout as Beamformer.process -> (map [n_streams, n_blocks, n_angles] float64, peak [n_streams, n_blocks] int32);
+        the leading axis is dropped when n_streams == 1."""
+        x = np.ascontiguousarray(x, np.float32)
+        n = x.size // (self.n_streams * self.M * self.H)
+        nb = n // self.W if self.W else 0
+        m = np.empty((self.n_streams, nb, self.angles.size), np.float64)
+        p = np.empty((self.n_streams, nb), np.int32)
+        self._chk(self._L.bf_doa_process(self._h, x.ctypes.data, n, m.ctypes.data, p.ctypes.data), "bf_doa_process")
+        return (m[0], p[0]) if self.n_streams == 1 else (m, p)
+
+    def process_device(self, x_ptr: int, n_frames: int, map_ptr: int = 0, peak_ptr: int = 0, stream: int = 0):
+        """Device buffers: map [n_streams][n_frames/W][n_angles] float64 and / or peak [n_streams][n_frames/W] int32."""
+        self._chk(self._L.bf_doa_process_device(self._h, x_ptr, n_frames, map_ptr or None, peak_ptr or None, stream or None),
+                  "bf_doa_process_device")

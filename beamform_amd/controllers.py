@@ -273,3 +273,42 @@ def follow(node, x: np.ndarray, controller, ref_channel: int = 0):
             node.set_theta(theta)
             published.append((t, theta))
     return np.concatenate(ys), published
+
+
+class DoaTheta:
+    """A /theta publisher driven by a direction-of-arrival map (beamform_amd.capi.Doa, bf_doa_*): on_map(row) returns the angle
+    of the block's peak, or None when the map value there is below `min_peak` (nothing to steer to)."""
+
+    def __init__(self, angles, min_peak: float = 0.0):
+        self.angles = np.asarray(angles, dtype=np.float64).ravel()
+        self.min_peak = float(min_peak)
+
+    def on_map(self, row):
+        row = np.asarray(row, dtype=np.float64)
+        d = int(np.argmax(row))  # the lowest index on ties, as bf_doa's peak
+        if row[d] < self.min_peak:
+            return None
+        return float(self.angles[d])
+
+
+def follow_doa(node, doa, x: np.ndarray, frames_per_block: int, controller):
+    """The closed loop with a localiser in place of the gradient scripts, one block of `frames_per_block` JACK periods at a time:
+    doa.process(block) -> controller.on_map(map row) -> node.set_theta, the node processing the same block with the angle the
+    PREVIOUS block published (one block of latency, as an external localiser has).
+
+    node: process(x [M, n*hop]) -> [n*hop], set_theta(deg), attribute H (beamform_amd.capi.Beamformer).  doa: beamform_amd.capi.Doa
+    on the same geometry, one stream, W = frames_per_block.  x: [M, F*hop] float32, F a multiple of frames_per_block.
+    Returns (y [F*hop], published: list of (block index, theta)), the shape of follow()'s result."""
+    H, W = node.H, int(frames_per_block)
+    F = x.shape[1] // H
+    ys, published = [], []
+    for b in range(F // W):
+        seg = np.ascontiguousarray(x[:, b * W * H:(b + 1) * W * H])
+        m, _ = doa.process(seg)
+        y = node.process(seg)
+        ys.append(np.array(y, copy=True))
+        theta = controller.on_map(m[0])
+        if theta is not None:
+            node.set_theta(theta)
+            published.append((b, theta))
+    return np.concatenate(ys), published

@@ -17,6 +17,7 @@
 #include <cxxabi.h>
 
 #include "../../include/bfcore.h"
+#include "doa.hpp"
 #include "geometry.hpp"
 #include "kernels.hpp"
 #include "launch_trace.hpp"
@@ -25,6 +26,8 @@
 using namespace bf;
 
 static thread_local std::string g_last_error;
+// what bf_last_error(NULL) reports; the handles of other files (doa.cpp) record their errors here too
+void bf::set_last_error(const std::string &msg) { g_last_error = msg; }
 
 // ---- launch trace (launch_trace.hpp): the kernels the calling thread launches between bf_trace_begin and bf_trace_end ----------
 static thread_local std::vector<const void *> *g_trace = nullptr;

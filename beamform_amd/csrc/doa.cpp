@@ -1,0 +1,342 @@
+// doa.cpp -- bf_doa_*: SRP-PHAT direction-of-arrival maps over the nodes' frames (include/bfcore.h, DESIGN.md "Direction-of-arrival
+// maps").  Host side: argument checks, the steering table (SteeringSet, the weights das steers with), scratch sizing and the launch
+// sequence per chunk of frames.  Every per-frame operation runs in the gfx950 kernels (pipeline_kernels.hpp launch_stft,
+// doa_kernels.hip); there is no CPU fallback.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/bfcore.h"
+#include "doa.hpp"
+#include "geometry.hpp"
+#include "pipeline_kernels.hpp"
+
+using namespace bf;
+
+struct bf_doa {
+    int M = 0, H = 0, N = 0, S = 1, NP = 1, layout = 0, device = 0, n_cus = 256;
+    int D = 0, W = 1, klo = 0, nK = 0, G = 1;
+    double eps = 1e-10;
+    std::string err;
+    const KernelSet *ks = nullptr;
+    hipStream_t stream = nullptr;                 // bf_doa_process (host buffers)
+    f64x2 *d_steer = nullptr, *d_tw = nullptr;    // [bin - klo][mic][angle]; forward-transform twiddles
+    double *d_win = nullptr;                      // sqrt-Hann
+    float *d_hist = nullptr;                      // [stream][hop before the next frame], layout as the input
+    // scratch for one chunk of `cap` frames (allocated on first use, grown up to the budget, kept)
+    long cap = 0;
+    f64x2 *d_Z = nullptr;
+    unsigned *d_flags = nullptr;
+    double *d_part = nullptr;
+    // staging of bf_doa_process
+    float *d_x = nullptr;
+    double *d_map = nullptr;
+    int32_t *d_peak = nullptr;
+    size_t x_cap = 0, map_cap = 0, peak_cap = 0;
+};
+
+namespace {
+
+// spectra + partial sums of one chunk stay within about this many bytes (a chunk never holds less than one block)
+constexpr size_t kDoaChunkBytes = 256ull << 20;
+constexpr size_t kDoaMaxTableBytes = 512ull << 20;
+
+int fail(bf_doa *d, int code, const std::string &what, hipError_t e = hipSuccess) {
+    std::string msg = what;
+    if (e != hipSuccess) {
+        msg += ": ";
+        msg += hipGetErrorString(e);
+    }
+    if (d) d->err = msg;
+    set_last_error(msg);
+    return code;
+}
+
+#define DOA_HIP(d, call)                                                  \
+    do {                                                                  \
+        hipError_t e_ = (call);                                           \
+        if (e_ != hipSuccess) return fail((d), BF_EIO, #call, e_);        \
+    } while (0)
+
+size_t frame_bytes(const bf_doa *d) {
+    return (size_t)d->S * ((size_t)d->NP * d->N * sizeof(f64x2) + (size_t)d->G * d->D * sizeof(double) + 2 * sizeof(unsigned));
+}
+
+// frames per chunk: a multiple of W within the budget
+long chunk_budget(const bf_doa *d) {
+    long c = (long)(kDoaChunkBytes / frame_bytes(d));
+    c -= c % d->W;
+    return c < d->W ? d->W : c;
+}
+
+int ensure_scratch(bf_doa *d, long frames) {
+    if (frames <= d->cap) return BF_OK;
+    DOA_HIP(d, hipDeviceSynchronize());  // a batch still in flight may read the old buffers
+    (void)hipFree(d->d_Z);
+    (void)hipFree(d->d_flags);
+    (void)hipFree(d->d_part);
+    d->d_Z = nullptr;
+    d->d_flags = nullptr;
+    d->d_part = nullptr;
+    d->cap = 0;
+    const size_t S = d->S;
+    if (hipMalloc((void **)&d->d_Z, S * frames * d->NP * d->N * sizeof(f64x2)) != hipSuccess ||
+        hipMalloc((void **)&d->d_flags, S * (frames + 1) * 2 * sizeof(unsigned)) != hipSuccess ||
+        hipMalloc((void **)&d->d_part, (size_t)d->G * S * frames * d->D * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(d, BF_ENOMEM, "bf_doa scratch");
+    }
+    d->cap = frames;
+    return BF_OK;
+}
+
+void release(bf_doa *d) {
+    void *ptrs[] = {d->d_steer, d->d_tw, d->d_win, d->d_hist, d->d_Z, d->d_flags, d->d_part, d->d_x, d->d_map, d->d_peak};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    if (d->stream) (void)hipStreamDestroy(d->stream);
+}
+
+}  // namespace
+
+int bf_doa_create(const bf_config *cfg, const double *angles_deg, int n_angles, double freq_lo, double freq_hi, int frames_per_block,
+                  bf_doa **out) {
+    if (!out) return fail(nullptr, BF_EINVAL, "bf_doa_create: out is NULL");
+    *out = nullptr;
+    if (!cfg) return fail(nullptr, BF_EINVAL, "bf_doa_create: cfg is NULL");
+    if (cfg->n_mics < 2 || cfg->n_mics > BF_MAX_MICS) return fail(nullptr, BF_EINVAL, "bf_doa_create: n_mics must be 2 .. BF_MAX_MICS");
+    if (cfg->hop < 64 || cfg->hop > 4096 || (cfg->hop & (cfg->hop - 1)) != 0)
+        return fail(nullptr, BF_EINVAL, "bf_doa_create: hop must be a power of two from 64 to 4096");
+    if (!(cfg->sample_rate > 0) || !std::isfinite(cfg->sample_rate)) return fail(nullptr, BF_EINVAL, "bf_doa_create: sample_rate");
+    if (cfg->n_streams < 1) return fail(nullptr, BF_EINVAL, "bf_doa_create: n_streams < 1");
+    if (cfg->layout != BF_PLANAR && cfg->layout != BF_INTERLEAVED) return fail(nullptr, BF_EINVAL, "bf_doa_create: layout");
+    if (!angles_deg || n_angles < 1 || n_angles > BF_DOA_MAX_ANGLES)
+        return fail(nullptr, BF_EINVAL, "bf_doa_create: n_angles must be 1 .. BF_DOA_MAX_ANGLES");
+    for (int i = 0; i < n_angles; ++i)
+        if (!std::isfinite(angles_deg[i])) return fail(nullptr, BF_EINVAL, "bf_doa_create: angle not finite");
+    if (frames_per_block < 1) return fail(nullptr, BF_EINVAL, "bf_doa_create: frames_per_block < 1");
+    if (!(freq_lo <= freq_hi)) return fail(nullptr, BF_EINVAL, "bf_doa_create: freq_lo > freq_hi");
+    const int M = cfg->n_mics, H = cfg->hop, N = 2 * H;
+    // the band: bins 1 .. N/2-1 whose frequency (frequency_vector, quirk Q1 included) lies in [freq_lo, freq_hi]; the vector is
+    // nondecreasing there, so the band is one run of bins
+    const std::vector<double> freqs = frequency_vector(N, cfg->sample_rate);
+    int klo = -1, khi = -1;
+    for (int k = 1; k <= N / 2 - 1; ++k)
+        if (freqs[k] >= freq_lo && freqs[k] <= freq_hi) {
+            if (klo < 0) klo = k;
+            khi = k;
+        }
+    if (klo < 0) return fail(nullptr, BF_EINVAL, "bf_doa_create: no bin in [freq_lo, freq_hi]");
+    const int nK = khi - klo + 1;
+    const size_t table = (size_t)nK * M * n_angles * sizeof(f64x2);
+    if (table > kDoaMaxTableBytes) return fail(nullptr, BF_EINVAL, "bf_doa_create: steering table (angles x bins x mics) above 512 MiB");
+    const int ndev = bf_device_count();
+    if (ndev <= 0) return fail(nullptr, BF_ENODEV, "no HIP device visible; libbfcore has no CPU fallback");
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, BF_ENODEV, "device ordinal out of range");
+
+    bf_doa *d = new bf_doa();
+    d->M = M;
+    d->H = H;
+    d->N = N;
+    d->S = cfg->n_streams;
+    d->NP = (M + 1) / 2;
+    d->layout = cfg->layout;
+    d->device = cfg->device;
+    d->D = n_angles;
+    d->W = frames_per_block;
+    d->klo = klo;
+    d->nK = nK;
+    d->G = doa_segments(nK);
+    d->ks = kernel_set(N);
+#define DOA_CREATE_HIP(call)                                  \
+    do {                                                      \
+        hipError_t e_ = (call);                               \
+        if (e_ != hipSuccess) {                               \
+            int rc_ = fail(nullptr, BF_EIO, #call, e_);       \
+            release(d);                                       \
+            delete d;                                         \
+            return rc_;                                       \
+        }                                                     \
+    } while (0)
+    if (!d->ks) {
+        delete d;
+        return fail(nullptr, BF_ENOSYS, "bf_doa_create: no forward transform for this hop");
+    }
+    DOA_CREATE_HIP(hipSetDevice(d->device));
+    hipDeviceProp_t prop;
+    DOA_CREATE_HIP(hipGetDeviceProperties(&prop, d->device));
+    d->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    DOA_CREATE_HIP(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+
+    // w_m(theta_d, k): exactly the column das steers with (update_weights(true), das.cpp:27-45), [bin - klo][mic][angle]
+    ArrayGeometry geo;
+    geo.set(cfg->mic_x, cfg->mic_y, M);
+    std::vector<f64x2> T((size_t)nK * M * n_angles);
+    SteeringSet st;
+    st.allocate(N, M, 1);
+    for (int a = 0; a < n_angles; ++a) {
+        st.update_column(geo, freqs, 0, angles_deg[a], true);
+        for (int kk = 0; kk < nK; ++kk)
+            for (int m = 0; m < M; ++m) {
+                const cplxd w = st.at(klo + kk, m, 0);
+                T[((size_t)kk * M + m) * n_angles + a] = f64x2{w.real(), w.imag()};
+            }
+    }
+    DOA_CREATE_HIP(hipMalloc((void **)&d->d_steer, table));
+    DOA_CREATE_HIP(hipMemcpy(d->d_steer, T.data(), table, hipMemcpyHostToDevice));
+    const std::vector<f64x2> tw = N == 1024 ? twiddle_table_32x32<f64x2>() : stockham_twiddles<f64x2>(N);
+    DOA_CREATE_HIP(hipMalloc((void **)&d->d_tw, tw.size() * sizeof(f64x2)));
+    DOA_CREATE_HIP(hipMemcpy(d->d_tw, tw.data(), tw.size() * sizeof(f64x2), hipMemcpyHostToDevice));
+    const std::vector<double> win = sqrt_hann(N);
+    DOA_CREATE_HIP(hipMalloc((void **)&d->d_win, win.size() * sizeof(double)));
+    DOA_CREATE_HIP(hipMemcpy(d->d_win, win.data(), win.size() * sizeof(double), hipMemcpyHostToDevice));
+    DOA_CREATE_HIP(hipMalloc((void **)&d->d_hist, (size_t)d->S * M * H * sizeof(float)));
+    DOA_CREATE_HIP(hipMemset(d->d_hist, 0, (size_t)d->S * M * H * sizeof(float)));
+#undef DOA_CREATE_HIP
+    *out = d;
+    return BF_OK;
+}
+
+int bf_doa_set_phat_floor(bf_doa *d, double eps) {
+    if (!d || !(eps >= 0) || !std::isfinite(eps)) return fail(d, BF_EINVAL, "bf_doa_set_phat_floor: eps must be finite and >= 0");
+    d->eps = eps;
+    return BF_OK;
+}
+
+int bf_doa_process_device(bf_doa *d, const float *x_dev, size_t n_frames, double *map_dev, int32_t *peak_dev, void *hip_stream) {
+    if (!d) return fail(nullptr, BF_EINVAL, "bf_doa_process_device: handle is NULL");
+    if (!map_dev && !peak_dev) return fail(d, BF_EINVAL, "bf_doa_process_device: map and peak are both NULL");
+    if (n_frames % (size_t)d->W != 0) return fail(d, BF_EINVAL, "bf_doa_process_device: n_frames is not a multiple of frames_per_block");
+    if (n_frames == 0) return BF_OK;
+    if (!x_dev) return fail(d, BF_EINVAL, "bf_doa_process_device: x is NULL");
+    hipStream_t s = (hipStream_t)hip_stream;
+    DOA_HIP(d, hipSetDevice(d->device));
+    const long F = (long)n_frames, CF = std::min(chunk_budget(d), F);
+    int rc = ensure_scratch(d, CF);
+    if (rc != BF_OK) return rc;
+    const int M = d->M, H = d->H;
+    const long mic_stride = d->layout == BF_PLANAR ? F * H : 1;
+    const long stream_stride = (long)M * F * H;
+    const long nb_total = F / d->W;
+    for (long c0 = 0; c0 < F; c0 += CF) {
+        const long n = std::min(CF, F - c0);
+        const float *xc = x_dev + (d->layout == BF_PLANAR ? c0 * H : c0 * (long)H * M);
+        DOA_HIP(d, launch_doa_hop_flags(xc, d->d_hist, d->d_flags, n, mic_stride, stream_stride, d->S, M, H, d->layout, s));
+        StftArgs sa{};
+        sa.x = xc;
+        sa.hist = d->d_hist;
+        sa.Z = d->d_Z;
+        sa.tw = d->d_tw;
+        sa.win = d->d_win;
+        sa.n_frames = n;
+        sa.frames_ws = CF;
+        sa.frame_off = 0;
+        sa.mic_stride = mic_stride;
+        sa.stream_stride_x = stream_stride;
+        sa.n_streams = d->S;
+        sa.n_mics = M;
+        sa.layout = d->layout;
+        sa.n_fft_mics = M;
+        sa.skip_lo = d->N;  // store everything ...
+        sa.skip_hi = 0;
+        const int khi = d->klo + d->nK - 1;
+        if (khi < d->N / 2 - 2) {  // ... but the bins between the band's top bin and its mirror
+            sa.skip_lo = khi;
+            sa.skip_hi = d->N - khi;
+        }
+        sa.z48 = 0;
+        sa.halve = 1;  // X_a = Z[k] + conj Z[N-k], X_b = -i (Z[k] - conj Z[N-k])
+        sa.run_len = 1;
+        DOA_HIP(d, d->ks->stft(sa, d->n_cus, s));
+        DoaMapArgs ma;
+        ma.Z = d->d_Z;
+        ma.flags = d->d_flags;
+        ma.steer = d->d_steer;
+        ma.part = d->d_part;
+        ma.eps = d->eps;
+        ma.n_frames = n;
+        ma.frames_ws = CF;
+        ma.n_streams = d->S;
+        ma.n_mics = M;
+        ma.nfft = d->N;
+        ma.n_angles = d->D;
+        ma.klo = d->klo;
+        ma.n_bins = d->nK;
+        DOA_HIP(d, launch_doa_map(ma, s));
+        DoaReduceArgs ra;
+        ra.part = d->d_part;
+        ra.map = map_dev;
+        ra.peak = peak_dev;
+        ra.scale = 1.0 / ((double)d->W * d->nK * M * M);
+        ra.frames_ws = CF;
+        ra.map_blocks = nb_total;
+        ra.block0 = c0 / d->W;
+        ra.n_blocks = n / d->W;
+        ra.n_streams = d->S;
+        ra.n_angles = d->D;
+        ra.n_segments = d->G;
+        ra.frames_per_block = d->W;
+        DOA_HIP(d, launch_doa_reduce(ra, s));
+        // the chunk's last hop is the next chunk's (and the next call's) hop -1 (util.h:305-308)
+        if (d->layout == BF_PLANAR)
+            DOA_HIP(d, hipMemcpy2DAsync(d->d_hist, H * sizeof(float), xc + (n - 1) * H, (size_t)mic_stride * sizeof(float), H * sizeof(float),
+                                        (size_t)d->S * M, hipMemcpyDeviceToDevice, s));
+        else
+            DOA_HIP(d, hipMemcpy2DAsync(d->d_hist, (size_t)H * M * sizeof(float), xc + (n - 1) * (long)H * M, (size_t)stream_stride * sizeof(float),
+                                        (size_t)H * M * sizeof(float), (size_t)d->S, hipMemcpyDeviceToDevice, s));
+    }
+    return BF_OK;
+}
+
+int bf_doa_process(bf_doa *d, const float *x_host, size_t n_frames, double *map_host, int32_t *peak_host) {
+    if (!d) return fail(nullptr, BF_EINVAL, "bf_doa_process: handle is NULL");
+    if (!map_host && !peak_host) return fail(d, BF_EINVAL, "bf_doa_process: map and peak are both NULL");
+    if (n_frames % (size_t)d->W != 0) return fail(d, BF_EINVAL, "bf_doa_process: n_frames is not a multiple of frames_per_block");
+    if (n_frames == 0) return BF_OK;
+    if (!x_host) return fail(d, BF_EINVAL, "bf_doa_process: x is NULL");
+    DOA_HIP(d, hipSetDevice(d->device));
+    const size_t xe = (size_t)d->S * d->M * n_frames * d->H, nb = (size_t)d->S * (n_frames / d->W), me = nb * d->D;
+    auto grow = [&](void **p, size_t &cap, size_t bytes) -> int {
+        if (bytes <= cap) return BF_OK;
+        DOA_HIP(d, hipStreamSynchronize(d->stream));
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+        cap = 0;
+        if (hipMalloc(p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(d, BF_ENOMEM, "bf_doa_process staging");
+        }
+        cap = bytes;
+        return BF_OK;
+    };
+    int rc = grow((void **)&d->d_x, d->x_cap, xe * sizeof(float));
+    if (rc == BF_OK && map_host) rc = grow((void **)&d->d_map, d->map_cap, me * sizeof(double));
+    if (rc == BF_OK && peak_host) rc = grow((void **)&d->d_peak, d->peak_cap, nb * sizeof(int32_t));
+    if (rc != BF_OK) return rc;
+    DOA_HIP(d, hipMemcpyAsync(d->d_x, x_host, xe * sizeof(float), hipMemcpyHostToDevice, d->stream));
+    rc = bf_doa_process_device(d, d->d_x, n_frames, map_host ? d->d_map : nullptr, peak_host ? d->d_peak : nullptr, d->stream);
+    if (rc != BF_OK) return rc;
+    if (map_host) DOA_HIP(d, hipMemcpyAsync(map_host, d->d_map, me * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if (peak_host) DOA_HIP(d, hipMemcpyAsync(peak_host, d->d_peak, nb * sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
+    DOA_HIP(d, hipStreamSynchronize(d->stream));
+    return BF_OK;
+}
+
+int bf_doa_reset(bf_doa *d) {
+    if (!d) return fail(nullptr, BF_EINVAL, "bf_doa_reset: handle is NULL");
+    DOA_HIP(d, hipSetDevice(d->device));
+    DOA_HIP(d, hipDeviceSynchronize());  // batches enqueued on any stream finish with the old history
+    DOA_HIP(d, hipMemset(d->d_hist, 0, (size_t)d->S * d->M * d->H * sizeof(float)));
+    return BF_OK;
+}
+
+void bf_doa_destroy(bf_doa *d) {
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    (void)hipDeviceSynchronize();
+    release(d);
+    delete d;
+}

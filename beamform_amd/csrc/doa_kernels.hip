@@ -1,0 +1,272 @@
+// doa_kernels.hip -- SRP-PHAT direction-of-arrival maps (bf_doa_*, include/bfcore.h; DESIGN.md "Direction-of-arrival maps").
+//
+//   P[s][b][d] = 1 / (W |K| M^2) sum_{t in block b} sum_{k in K} | sum_m conj(w_m(theta_d, k)) X^_{s,m,t}(k) |^2,  X^ = X / |X| (0 at |X| <= eps)
+//
+// The forward transforms are the bin pipeline's (launch_stft: packed microphone pairs Z = FFT(h a + i h b), stored halved, so that
+// X_a = Z[k] + conj Z[N-k] and X_b = -i (Z[k] - conj Z[N-k])).  Three kernels per chunk of frames:
+//   doa_hop_flags_kernel  which microphones have a nonzero sample in each hop: a microphone whose windowed frame is exactly zero gets
+//                         X^ = 0 exactly (its packed partner's rounding residue never becomes a unit vector)
+//   doa_map_kernel        per (frame tile, angle tile, band segment): the per-bin [angles x M] . [M x frames] complex product, |.|^2,
+//                         summed over the segment's bins in ascending order -> one partial sum per (segment, stream, frame, angle)
+//   doa_reduce_kernel     per (stream, block): segments in order, then the block's frames in order, the scale, and the argmax
+// Every sum has one fixed order that depends on the band and W only: map and peak bytes do not depend on how a stream is cut into
+// calls or chunks, nor on the launch.  No atomics reach a sum (the hop flags are OR-ed).
+#include <climits>
+
+#include "doa.hpp"
+#include "launch_trace.hpp"
+
+namespace bf {
+namespace {
+
+constexpr int kDoaBlock = 256;
+
+__global__ __launch_bounds__(kDoaBlock) void doa_hop_flags_kernel(const float *x, const float *hist, unsigned *flags, long n_frames,
+                                                                  long mic_stride, long stream_stride_x, int n_mics, int hop, int layout) {
+    __shared__ unsigned sh[2];
+    const int tid = threadIdx.x;
+    const long h = (long)blockIdx.x - 1;  // hop -1: the carried hop in front of the batch
+    const int s = blockIdx.y, M = n_mics, H = hop;
+    if (tid < 2) sh[tid] = 0u;
+    __syncthreads();
+    const float *p;
+    long ms;
+    if (h < 0) {
+        p = hist + (long)s * M * H;  // [mic][hop] (planar) or [hop][mic]
+        ms = H;
+    } else {
+        p = x + (long)s * stream_stride_x + (layout == 0 ? h * H : h * (long)H * M);
+        ms = mic_stride;
+    }
+    unsigned tail = 0u, full = 0u;
+    for (int i = tid; i < M * H; i += kDoaBlock) {
+        int m, j;
+        float v;
+        if (layout == 0) {
+            m = i / H;
+            j = i - m * H;
+            v = p[(long)m * ms + j];
+        } else {
+            j = i / M;
+            m = i - j * M;
+            v = p[i];
+        }
+        if (v != 0.f) {
+            full |= 1u << m;
+            if (j > 0) tail |= 1u << m;
+        }
+    }
+    if (tail) atomicOr(&sh[0], tail);
+    if (full) atomicOr(&sh[1], full);
+    __syncthreads();
+    if (tid < 2) flags[((long)s * (n_frames + 1) + (h + 1)) * 2 + tid] = sh[tid];
+}
+
+__device__ __forceinline__ f64x2 phat(double re, double im, double eps, bool live) {
+    const double mag = sqrt(re * re + im * im);
+    if (!live || !(mag > eps)) return f64x2{0.0, 0.0};
+    return f64x2{re / mag, im / mag};
+}
+
+// One workgroup: 64 frames (wavefront w, lane group lf = lane / 16: frames 16 w + 4 lf .. + 3) x 32 angles (lane la = lane mod 16: angles
+// 2 la, 2 la + 1) x the bins of one band segment.  Per bin the normalised spectra of the tile's frames and the tile's steering column are
+// staged in LDS (the next bin's are fetched into registers while this one is multiplied): every steering element is read from memory
+// once per 64 frames, every spectrum element once per 32 angles.  MT: microphones known at compile time (0 = run-time count, <= 32).
+template <int MT>
+__global__ __launch_bounds__(kDoaBlock) void doa_map_kernel(DoaMapArgs a) {
+    constexpr int MX = MT ? MT : 32, NPX = (MX + 1) / 2;
+    constexpr int kItems = (kDoaTileFrames * NPX + kDoaBlock - 1) / kDoaBlock;
+    constexpr int kWItems = (MX * kDoaTileAngles + kDoaBlock - 1) / kDoaBlock;
+    constexpr int kUnrollM = MT ? MT : 4;
+    constexpr int XS = MX + 1;  // row of one frame in LDS (padded: the four lane groups read rows in different banks)
+    __shared__ f64x2 xs[kDoaTileFrames * XS];
+    __shared__ f64x2 ws[MX * kDoaTileAngles];
+    const int M = MT ? MT : a.n_mics, NP = (M + 1) / 2, N = a.nfft, D = a.n_angles;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, la = lane & 15, lf = lane >> 4;
+    const int n_at = (D + kDoaTileAngles - 1) / kDoaTileAngles;
+    const int at = blockIdx.x % n_at, ft = blockIdx.x / n_at;  // angle tiles fastest: workgroups on the same frames run side by side (L2)
+    const int g = blockIdx.y, s = blockIdx.z;
+    const long t0 = (long)ft * kDoaTileFrames;
+    const int d0 = at * kDoaTileAngles;
+    const int kk0 = g * kDoaSegBins, kk1 = min(kk0 + kDoaSegBins, a.n_bins);
+    const long FW = a.frames_ws, n = a.n_frames;
+
+    // staging items: (frame f, pair p) of the spectra, (mic m, angle al) of the steering column
+    unsigned fm[kItems];  // microphones whose windowed frame is not exactly zero
+    f64x2 za[kItems], zb[kItems], wv[kWItems];
+#pragma unroll
+    for (int j = 0; j < kItems; ++j) {
+        const int idx = tid + kDoaBlock * j;
+        fm[j] = 0u;
+        za[j] = zb[j] = f64x2{0.0, 0.0};
+        if (idx < kDoaTileFrames * NP) {
+            const long t = t0 + idx / NP;
+            if (t < n) {
+                const unsigned *fl = a.flags + ((long)s * (n + 1) + t) * 2;  // hop t-1 (sample 0 carries window 0) and hop t
+                fm[j] = fl[0] | fl[3];
+            }
+        }
+    }
+    auto fetch = [&](int kk) {
+        const int k = a.klo + kk;
+#pragma unroll
+        for (int j = 0; j < kItems; ++j) {
+            const int idx = tid + kDoaBlock * j;
+            if (idx < kDoaTileFrames * NP && fm[j]) {
+                const long t = t0 + idx / NP;
+                const int p = idx % NP;
+                const f64x2 *zr = a.Z + (((long)s * FW + t) * NP + p) * N;
+                za[j] = zr[k];
+                zb[j] = zr[N - k];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kWItems; ++j) {
+            const int idx = tid + kDoaBlock * j;
+            if (idx < M * kDoaTileAngles) {
+                const int m = idx / kDoaTileAngles, d = min(d0 + idx % kDoaTileAngles, D - 1);
+                wv[j] = a.steer[((long)kk * M + m) * D + d];
+            }
+        }
+    };
+    auto stage = [&]() {
+#pragma unroll
+        for (int j = 0; j < kItems; ++j) {
+            const int idx = tid + kDoaBlock * j;
+            if (idx < kDoaTileFrames * NP) {
+                const int f = idx / NP, p = idx % NP, ma = 2 * p, mb = 2 * p + 1;
+                // halved packed pair: X_a = Z[k] + conj Z[N-k], X_b = -i (Z[k] - conj Z[N-k])
+                xs[f * XS + ma] = phat(za[j].x + zb[j].x, za[j].y - zb[j].y, a.eps, (fm[j] >> ma) & 1u);
+                if (mb < M) xs[f * XS + mb] = phat(za[j].y + zb[j].y, zb[j].x - za[j].x, a.eps, (fm[j] >> mb) & 1u);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kWItems; ++j) {
+            const int idx = tid + kDoaBlock * j;
+            if (idx < M * kDoaTileAngles) ws[idx] = wv[j];
+        }
+    };
+
+    const int fb = wave * 16 + lf * 4;  // first of this lane's four frames in the tile
+    double pw[2][4];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pw[j][i] = 0.0;
+    fetch(kk0);
+    for (int kk = kk0; kk < kk1; ++kk) {
+        stage();
+        __syncthreads();
+        if (kk + 1 < kk1) fetch(kk + 1);
+        double yr[2][4], yi[2][4];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) yr[j][i] = yi[j][i] = 0.0;
+#pragma unroll kUnrollM
+        for (int m = 0; m < M; ++m) {
+            const f64x2 w0 = ws[m * kDoaTileAngles + 2 * la], w1 = ws[m * kDoaTileAngles + 2 * la + 1];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const f64x2 x = xs[(fb + i) * XS + m];
+                // conj(w) x = (wr xr + wi xi) + i (wr xi - wi xr)
+                yr[0][i] = fma(w0.x, x.x, yr[0][i]);
+                yr[0][i] = fma(w0.y, x.y, yr[0][i]);
+                yi[0][i] = fma(w0.x, x.y, yi[0][i]);
+                yi[0][i] = fma(-w0.y, x.x, yi[0][i]);
+                yr[1][i] = fma(w1.x, x.x, yr[1][i]);
+                yr[1][i] = fma(w1.y, x.y, yr[1][i]);
+                yi[1][i] = fma(w1.x, x.y, yi[1][i]);
+                yi[1][i] = fma(-w1.y, x.x, yi[1][i]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) pw[j][i] = fma(yi[j][i], yi[j][i], fma(yr[j][i], yr[j][i], pw[j][i]));
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const long t = t0 + fb + i;
+        if (t >= n) continue;
+        double *row = a.part + (((long)g * a.n_streams + s) * FW + t) * D;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int d = d0 + 2 * la + j;
+            if (d < D) row[d] = pw[j][i];
+        }
+    }
+}
+
+// One workgroup per (stream, block): P = scale * sum_{t in block} (sum_g part[g][t]) in that order, then the lowest index of the maximum.
+__global__ __launch_bounds__(kDoaBlock) void doa_reduce_kernel(DoaReduceArgs a) {
+    __shared__ double bv[kDoaBlock];
+    __shared__ int bi[kDoaBlock];
+    const int tid = threadIdx.x, s = blockIdx.y, D = a.n_angles, W = a.frames_per_block;
+    const long b = blockIdx.x;
+    double best = -1.0;
+    int besti = INT_MAX;
+    for (int d = tid; d < D; d += kDoaBlock) {
+        double acc = 0.0;
+        for (int tt = 0; tt < W; ++tt) {
+            const long t = b * W + tt;
+            double v = 0.0;
+            for (int g = 0; g < a.n_segments; ++g) v += a.part[(((long)g * a.n_streams + s) * a.frames_ws + t) * D + d];
+            acc += v;
+        }
+        const double val = acc * a.scale;
+        if (a.map) a.map[((long)s * a.map_blocks + a.block0 + b) * D + d] = val;
+        if (val > best) {  // ascending d per thread: the first maximum is kept
+            best = val;
+            besti = d;
+        }
+    }
+    if (!a.peak) return;
+    bv[tid] = best;
+    bi[tid] = besti;
+    __syncthreads();
+    for (int w = kDoaBlock / 2; w > 0; w >>= 1) {
+        if (tid < w) {
+            const double v2 = bv[tid + w];
+            const int i2 = bi[tid + w];
+            if (v2 > bv[tid] || (v2 == bv[tid] && i2 < bi[tid])) {
+                bv[tid] = v2;
+                bi[tid] = i2;
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) a.peak[(long)s * a.map_blocks + a.block0 + b] = bi[0];
+}
+
+}  // namespace
+
+hipError_t launch_doa_hop_flags(const float *x, const float *hist, unsigned *flags, long n_frames, long mic_stride, long stream_stride_x,
+                                int n_streams, int n_mics, int hop, int layout, hipStream_t s) {
+    BF_LAUNCH(doa_hop_flags_kernel, dim3((unsigned)(n_frames + 1), (unsigned)n_streams), dim3(kDoaBlock), 0, s, x, hist, flags, n_frames,
+              mic_stride, stream_stride_x, n_mics, hop, layout);
+    return hipGetLastError();
+}
+
+hipError_t launch_doa_map(const DoaMapArgs &a, hipStream_t s) {
+    const long n_ft = (a.n_frames + kDoaTileFrames - 1) / kDoaTileFrames, n_at = (a.n_angles + kDoaTileAngles - 1) / kDoaTileAngles;
+    const dim3 grid((unsigned)(n_ft * n_at), (unsigned)doa_segments(a.n_bins), (unsigned)a.n_streams);
+    switch (a.n_mics) {
+        case 2: BF_LAUNCH(doa_map_kernel<2>, grid, dim3(kDoaBlock), 0, s, a); break;
+        case 4: BF_LAUNCH(doa_map_kernel<4>, grid, dim3(kDoaBlock), 0, s, a); break;
+        case 8: BF_LAUNCH(doa_map_kernel<8>, grid, dim3(kDoaBlock), 0, s, a); break;
+        case 16: BF_LAUNCH(doa_map_kernel<16>, grid, dim3(kDoaBlock), 0, s, a); break;
+        default:
+            if (a.n_mics < 1 || a.n_mics > 32) return hipErrorInvalidValue;
+            BF_LAUNCH(doa_map_kernel<0>, grid, dim3(kDoaBlock), 0, s, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_doa_reduce(const DoaReduceArgs &a, hipStream_t s) {
+    BF_LAUNCH(doa_reduce_kernel, dim3((unsigned)a.n_blocks, (unsigned)a.n_streams), dim3(kDoaBlock), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace bf

@@ -180,6 +180,43 @@ int bf_set_thetas(bf_handle *h, const double *degrees, int n);
  * steer on (scripts/energy2theta.py:23-27 get_energy_from_list), so "publish theta, wait, measure" becomes
  * "evaluate n_dirs candidates in one batch and pick". */
 int bf_stream_rms(bf_handle *h, const float *y_dev, size_t n_frames, double *rms_host, void *hip_stream);
+
+/* ---- direction-of-arrival maps: a source for /theta (SRP-PHAT over das's own beams) ---------------------------------------------
+ * The reference steers only when something publishes /theta (README "The direction of interest ... can be changed on-the-fly by
+ * writing to the topic /theta"); its publishers are the gradient scripts (scripts/energy2theta*.py).  bf_doa is a stream operator on
+ * the same multichannel input as a bf_handle that returns, per block of W frames, the PHAT-weighted steered response power of every
+ * candidate angle (Valin et al. 2007) and the index of the best one.
+ *   Frames: frame t of a stream is [hop t-1 | hop t] times the periodic sqrt-Hann window; hop -1 is zeros after create / reset and the
+ *   previous call's last hop otherwise (util.h:272-302, as in every node).  X_m(k) = forward DFT of microphone m's windowed frame (N = 2 hop).
+ *   PHAT:  X^_m(k) = X_m(k) / |X_m(k)| when |X_m(k)| > eps, else 0 (eps: bf_doa_set_phat_floor, default 1e-10).
+ *   Band:  K = the bins k in 1 .. N/2-1 with freq_lo <= f_k <= freq_hi, f_k the frequency vector das steers with (quirk Q1 included:
+ *          f_{N/2-1} = sample_rate / 2).  An empty K is BF_EINVAL.
+ *   Weights: w_m(theta, k) is exactly das's update_weights(ini = true) column for angle theta (das.cpp:27-45: microphone 0's row is 1,
+ *          the reference's delay formula): the angle of a peak is the value to pass to bf_set_theta of a das handle (das applies conj(w)).
+ *   Map:   P[s][b][d] = 1 / (W |K| M^2) * sum_{t in block b} sum_{k in K} | sum_m conj(w_m(theta_d, k)) X^_{s,m,t}(k) |^2, in [0, 1].
+ *   Peak:  peak[s][b] = argmax_d P[s][b][d], the lowest d on ties.
+ * Arithmetic is in double from the spectra to the map.  Map and peak bytes do not depend on how a stream is cut into calls (at block
+ * boundaries), on the internal chunking, or on the launch: every sum has one fixed order.  A microphone whose windowed frame is exactly
+ * zero contributes X^ = 0 in every bin.  No guarantee: a bin with |X| within rounding of eps may land on either side (the spectra of two
+ * microphones share one complex transform: a microphone 2^-40 below its pair partner keeps only its leading bits); on a linear array
+ * theta and its mirror image through the array axis have the same map value (front/back ambiguity), so the lower index wins the peak.
+ * Scratch: about 256 MiB per handle for spectra and partial sums (allocated on the first batch, kept), plus the steering table
+ * (angles x |K| x M complex doubles, at most 512 MiB: larger is BF_EINVAL).  One batch at a time per handle. */
+#define BF_DOA_MAX_ANGLES 1024
+typedef struct bf_doa bf_doa;
+/* cfg: reads n_mics (2..BF_MAX_MICS), mic_x/mic_y, hop, sample_rate, n_streams, layout, device; ignores algo and the node parameters.
+ * Bad arguments are BF_EINVAL, checked before any device work; without a HIP device BF_ENODEV. */
+int bf_doa_create(const bf_config *cfg, const double *angles_deg, int n_angles, double freq_lo, double freq_hi,
+                  int frames_per_block, bf_doa **out);
+int bf_doa_set_phat_floor(bf_doa *d, double eps);            /* >= 0; default 1e-10 */
+/* n_frames: a multiple of frames_per_block (else BF_EINVAL), 0 is a no-op.  x: as bf_process_batch_device reads it (cfg.layout).
+ * map: [n_streams][n_frames/W][n_angles] double, peak: [n_streams][n_frames/W] int32; either may be NULL, not both.
+ * Enqueued on hip_stream, no host sync.  HIP errors: BF_EIO, text in bf_last_error(NULL). */
+int bf_doa_process_device(bf_doa *d, const float *x_dev, size_t n_frames, double *map_dev, int32_t *peak_dev, void *hip_stream);
+/* The same on host buffers (staged through the device; returns when the results are in map_host / peak_host). */
+int bf_doa_process(bf_doa *d, const float *x_host, size_t n_frames, double *map_host, int32_t *peak_host);
+int bf_doa_reset(bf_doa *d);                                  /* cold start: history hop zeroed (host-synchronous) */
+void bf_doa_destroy(bf_doa *d);
 /* interf_theta_roscallback (lcmv.cpp:258-309, gss.cpp:288-339): id is 1-based.  id <= current count updates that
  * interferer (and removes it when it lands within interf_angle_threshold of another one); id > count appends a
  * new interferer unless it is that close to an existing one.  As in the reference, a structural change rebuilds
