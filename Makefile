@@ -10,7 +10,7 @@ HIP_SRCS := $(SRC)/das_fused.hip $(SRC)/das_fused_gen.hip $(SRC)/das_f64_w64.hip
 # bin-pipeline kernels: one object per supported FFT size (JACK periods 64 ... 4096 frames -> -DBF_NFFT=128 ... 8192)
 BIN_SRCS := pipeline_kernels stft_istft mask_kernels cov_kernels gsc_gss_kernels
 NFFTS := 128 256 512 1024 2048 4096 8192
-CPP_SRCS := $(SRC)/capi.cpp $(SRC)/config.cpp $(SRC)/wavio.cpp $(SRC)/doa.cpp
+CPP_SRCS := $(SRC)/capi.cpp $(SRC)/das_fused_engine.cpp $(SRC)/config.cpp $(SRC)/wavio.cpp $(SRC)/doa.cpp
 OBJS := $(patsubst $(SRC)/%.hip,$(OBJ)/%.o,$(HIP_SRCS)) $(patsubst $(SRC)/%.cpp,$(OBJ)/%.o,$(CPP_SRCS)) \
         $(foreach n,$(NFFTS),$(foreach b,$(BIN_SRCS),$(OBJ)/$(b)_n$(n).o))
 HDRS := $(wildcard $(SRC)/*.hpp) include/bfcore.h

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -17,6 +18,7 @@
 #include <cxxabi.h>
 
 #include "../../include/bfcore.h"
+#include "device_mem.hpp"
 #include "doa.hpp"
 #include "geometry.hpp"
 #include "kernels.hpp"
@@ -51,31 +53,16 @@ struct bf_handle {
     std::vector<double> interf;
     bool tables_dirty = true;
 
-    // fused-DAS device state
-    f32x2 *d_gains[2] = {nullptr, nullptr};
-    int gains_cur = 0;
-    f32x2 *d_twiddle = nullptr;
-    f32x2 *d_gains_il[2] = {nullptr, nullptr};  // hop < 512: das_pair_gains_interleaved tables (das_fused.hip, group mode), double-buffered with d_gains
-    f32x2 *d_twiddle_1024 = nullptr;            // hop < 512: twiddle_table_32x32 (the frame-interleaving kernel runs the 1024-point machinery)
-    float *d_window = nullptr;
-    float *d_zeros = nullptr;
-    float *d_hist[2] = {nullptr, nullptr};  // the hop before the next frame (the reference's ring buffer content)
-    float *d_tail[2] = {nullptr, nullptr};
-    int tail_cur = 0;  // index of the valid hist/tail pair; the kernel writes the other one
-    f32x2 *d_sdump = nullptr;
-    size_t sdump_cap = 0;
-    double *d_sumsq = nullptr;  // bf_stream_rms scratch
-
-    // bin pipeline (mvdr/lcmv/gss/phase/phasempf and DAS_BINS_F64)
-    BinPipeline *pipe = nullptr;
+    // the node's device side: the fused fp32 das kernels or the bin pipeline (pipeline.hpp); never null once bf_create has succeeded
+    std::unique_ptr<Engine> engine;
+    DeviceBuffer<double> d_sumsq;  // bf_stream_rms scratch
 
     // staging for the host-buffer entry points
-    float *d_x = nullptr, *d_y = nullptr;
-    size_t d_x_cap = 0, d_y_cap = 0;
+    DeviceBuffer<float> d_x, d_y;  // grown on demand
     // bf_process_batch pipelining: copies on their own streams, chunk by chunk, around the compute stream
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     std::vector<hipEvent_t> ev_in, ev_out;
-    float *h_pin = nullptr;  // pinned [n_mics*hop | n_out*hop]: bf_process_hop stages through it (no pageable-copy detour)
+    PinnedBuffer<float> h_pin;  // pinned [n_mics*hop | n_out*hop]: bf_process_hop stages through it (no pageable-copy detour)
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 
@@ -107,11 +94,6 @@ int fail(bf_handle *h, int code, const char *what, hipError_t e = hipSuccess) {
         if (e_ != hipSuccess) return fail((h), BF_EIO, #call, e_);       \
     } while (0)
 
-// fused fp32 das: the 512-frame period has the register-resident kernels (32 x 32 in-register FFT-1024, das_fused.hip); every
-// other period (64 ... 4096 frames) one fused kernel on LDS-staged transforms (das_fused_gen.hip)
-bool uses_fused_das(const bf_handle *h) { return h->cfg.algo == BF_DAS && h->cfg.das_impl == BF_DAS_FUSED_F32; }
-bool fused_das_gen(const bf_handle *h) { return h->cfg.hop != 512; }
-
 // update_weights(): recompute every steering column from the current angles.
 void rebuild_steering(bf_handle *h, bool first, int only_dir = -1) {
     for (int d = 0; d < h->n_dirs; ++d) {
@@ -126,35 +108,13 @@ void rebuild_steering(bf_handle *h, bool first, int only_dir = -1) {
 // already in flight keeps reading the table it was launched with.
 int sync_tables(bf_handle *h, hipStream_t s, RunSnapshot *snap) {
     std::lock_guard<std::mutex> lk(h->mu);
-    if (!h->tables_dirty) {
-        if (h->pipe) *snap = h->pipe->snapshot_for_run();
-        return BF_OK;
+    if (h->tables_dirty) {
+        int rc = h->engine->upload_steering(h->steer, s);
+        if (rc != BF_OK) return fail(h, rc, h->engine->error().c_str());
+        h->tables_dirty = false;
     }
-    if (uses_fused_das(h)) {
-        const int np = (h->M + 1) / 2;
-        std::vector<f32x2> g, gil;  // [dir][pair][1024]
-        for (int d = 0; d < h->n_dirs; ++d) {
-            if (h->d_gains_il[0]) {
-                const std::vector<f32x2> gi = das_pair_gains_interleaved(h->steer[d], np);
-                gil.insert(gil.end(), gi.begin(), gi.end());
-            }
-            const std::vector<f32x2> gd = fused_das_gen(h) ? das_pair_gains_natural(h->steer[d], np) : das_pair_gains(h->steer[d], np);
-            g.insert(g.end(), gd.begin(), gd.end());
-        }
-        const int nxt = h->gains_cur ^ 1;
-        BF_HIP(h, hipMemcpyAsync(h->d_gains[nxt], g.data(), g.size() * sizeof(f32x2), hipMemcpyHostToDevice, s));
-        if (h->d_gains_il[0])
-            BF_HIP(h, hipMemcpyAsync(h->d_gains_il[nxt], gil.data(), gil.size() * sizeof(f32x2), hipMemcpyHostToDevice, s));
-        BF_HIP(h, hipStreamSynchronize(s));  // pageable staging vectors go out of scope
-        h->gains_cur = nxt;
-    }
-    if (h->pipe) {
-        int rc = h->pipe->upload_steering(h->steer, s);
-        if (rc != BF_OK) return fail(h, rc, h->pipe->error().c_str());
-    }
-    h->tables_dirty = false;
     // one consistent view of {columns, table, pending gss resets} for this batch, taken under the same lock
-    if (h->pipe) *snap = h->pipe->snapshot_for_run();
+    *snap = h->engine->snapshot_for_run();
     return BF_OK;
 }
 
@@ -201,147 +161,25 @@ int timing_collect(bf_handle *h, float *ms_mean, int *n_launches) {
     return BF_OK;
 }
 
-int run_das_fused(bf_handle *h, const float *x_dev, size_t n_frames, float *y_dev, void *spectrum_dev, hipStream_t s,
-                  int layout, long mic_stride) {
-    const long F = (long)n_frames;
-    const int S = h->n_out;
-    // one block (16 half-wavefronts) per run of consecutive frames; runs are multiples of 16 frames and
-    // there are about as many runs as CUs
-    const bool gen = fused_das_gen(h);
-    // (periods 256 / 1024: several 256-thread blocks share a CU -- 13 / 52 KB of LDS each -- and a run costs one recomputed frame)
-    // several look directions, planar input, <= 8 microphones, no dump: one set of forward transforms per frame serves up to 16
-    // directions (das_fused_dirs_kernel); BF_DAS_SHARED_DIRS = the smallest direction count that takes it (0: never)
-    static const int shared_min = getenv("BF_DAS_SHARED_DIRS") ? atoi(getenv("BF_DAS_SHARED_DIRS")) : 6;
-    const bool shared = !gen && layout == BF_PLANAR && h->M <= 8 && !spectrum_dev && shared_min > 0 && h->n_dirs >= shared_min;
-    // (generic periods: blocks of 13 N bytes of LDS -- 26 N at N = 8192 -- share a CU: 8 at N <= 512, 3 at 2048, 1 from 4096 on)
-    const int gen_per_cu = h->N <= 512 ? 8 : h->N <= 1024 ? 6 : h->N <= 2048 ? 3 : 1;
-    // period 1024 without a dump: ONE 2048-point transform per frame on a full wavefront, eight frames in flight per block and the tails
-    // through an LDS ring (das_fused.hip das_fused_wave2048_kernel); BF_DAS_SPLIT2048=0: the generic kernel (cross-checks)
-    static const int split_env = getenv("BF_DAS_SPLIT2048") ? atoi(getenv("BF_DAS_SPLIT2048")) : 3;
-    const bool wave2048 = gen && h->N == 2048 && !spectrum_dev && split_env != 0;
-    // periods below 512 without a dump: 1024 / N frames interleaved into one pass of the 1024-point machinery -- the period-512 kernel
-    // itself in group mode: one block per run, tails through its LDS ring, HBM sees every hop once; BF_DAS_INTERLEAVE=0: the generic
-    // kernel (cross-checks)
-    static const int il_env = getenv("BF_DAS_INTERLEAVE") ? atoi(getenv("BF_DAS_INTERLEAVE")) : 1;
-    const bool small_ring = gen && h->N < 1024 && !spectrum_dev && il_env != 0 && h->d_gains_il[0] != nullptr && h->d_twiddle_1024 != nullptr;
-    const long Rg = small_ring ? 1024 / h->N : 1;
-    long runs = (small_ring || wave2048 ? (long)h->n_cus : gen ? (long)h->n_cus * gen_per_cu : (long)h->n_cus) / (shared ? h->n_streams : S);
-    if (runs < 1) runs = 1;
-    long fpc = (F + runs - 1) / runs;
-    if (!gen) fpc = ((fpc + 15) / 16) * 16;
-    if (wave2048) fpc = ((fpc + 7) / 8) * 8;                              // eight frames per pass of a block
-    else if (small_ring) fpc = ((fpc + 16 * Rg - 1) / (16 * Rg)) * (16 * Rg);  // sixteen groups per pass of a block
-    const long cps = (F + fpc - 1) / fpc;
-
-    if (spectrum_dev) {
-        const size_t need = (size_t)S * F * h->N;
-        if (need > h->sdump_cap) {
-            if (h->d_sdump) (void)hipFree(h->d_sdump);
-            h->d_sdump = nullptr;
-            h->sdump_cap = 0;
-            BF_HIP(h, hipMalloc((void **)&h->d_sdump, need * sizeof(f32x2)));
-            h->sdump_cap = need;
-        }
-    }
-
-    DasFusedArgs a;
-    a.x = x_dev;
-    a.hist_in = h->d_hist[h->tail_cur];
-    a.hist_out = h->d_hist[h->tail_cur ^ 1];
-    a.y = y_dev;
-    a.tail_in = h->d_tail[h->tail_cur];
-    a.tail_out = h->d_tail[h->tail_cur ^ 1];
-    a.gains = small_ring ? h->d_gains_il[h->gains_cur] : h->d_gains[h->gains_cur];
-    a.twiddle = small_ring ? h->d_twiddle_1024 : h->d_twiddle;
-    a.window = h->d_window;
-    a.zeros = h->d_zeros;
-    a.sdump = spectrum_dev ? h->d_sdump : nullptr;
-    a.n_frames = F;
-    a.mic_stride = mic_stride;
-    a.stream_stride_x = (long)h->M * F * h->H;
-    a.n_streams = S;
-    a.n_dirs = h->n_dirs;
-    a.n_mics = h->M;
-    a.frames_per_chunk = (int)fpc;
-    a.chunks_per_stream = (int)cps;
-    a.layout = layout;
-    a.group = small_ring ? (int)Rg : 1;
-    if (wave2048) BF_HIP(h, prepare_das_fused_wave2048(a, s));
-    else if (!gen || small_ring) BF_HIP(h, prepare_das_fused(a, s));
-    hipEvent_t k0 = nullptr, k1 = nullptr;
-    {
-        int trc = timing_acquire(h, &k0, &k1);
-        if (trc != BF_OK) return trc;
-    }
-    // (a launch that fails between the two records must not leave a half-recorded pair in the session: hand it back)
-    auto launch_all = [&]() -> hipError_t {
-        hipError_t e = hipSuccess;
-        if (k0) e = hipEventRecord(k0, s);
-        if (e != hipSuccess) return e;
-        if (shared) {
-            for (int d0 = 0; d0 < h->n_dirs && e == hipSuccess; d0 += 16)
-                e = launch_das_fused_dirs(a, d0, h->n_dirs - d0 < 16 ? h->n_dirs - d0 : 16, s);
-        } else {
-            e = wave2048 ? launch_das_fused_wave2048(a, s)
-                : small_ring ? launch_das_fused(a, s)
-                : gen     ? launch_das_fused_gen(a, h->N, s)
-                : launch_das_fused(a, s);
-        }
-        if (e == hipSuccess && k1) e = hipEventRecord(k1, s);
-        return e;
-    };
-    {
-        const hipError_t e = launch_all();
-        if (e != hipSuccess) {
-            if (k0 && h->ev_used > 0) --h->ev_used;
-            BF_HIP(h, e);
-        }
-    }
-    h->tail_cur ^= 1;
-
-    if (spectrum_dev)
-        BF_HIP(h, gen ? launch_das_hermitian_dump_gen(h->d_sdump, (f64x2 *)spectrum_dev, (long)S * F, h->N, s)
-                      : launch_das_hermitian_dump(h->d_sdump, (f64x2 *)spectrum_dev, (long)S * F, s));
-    return BF_OK;
-}
-
 int run_batch_device(bf_handle *h, const float *x_dev, size_t n_frames, float *y_dev, void *spectrum_dev, hipStream_t s,
                      int layout, long mic_stride) {
     if (n_frames == 0) return BF_OK;
     RunSnapshot snap;
     int rc = sync_tables(h, s, &snap);
     if (rc != BF_OK) return rc;
-    if (uses_fused_das(h)) return run_das_fused(h, x_dev, n_frames, y_dev, spectrum_dev, s, layout, mic_stride);
-    // the pipeline brackets its dominant kernel with this pair when it has one (das fp64 in one launch); otherwise the pair stays
-    // unrecorded and the session's mean is taken over nothing (callers fall back to the call time)
+    // the engine brackets its dominant kernel with this pair when it has one (fused fp32 das, das fp64 in one launch); otherwise the pair
+    // stays unrecorded and the session's mean is taken over nothing (callers fall back to the call time)
     hipEvent_t k0 = nullptr, k1 = nullptr;
     rc = timing_acquire(h, &k0, &k1);
     if (rc != BF_OK) return rc;
-    h->pipe->kev0 = k0;
-    h->pipe->kev1 = k1;
-    h->pipe->kev_recorded = false;
-    rc = h->pipe->run(x_dev, (long)n_frames, y_dev, (f64x2 *)spectrum_dev, s, layout, mic_stride, snap);
-    h->pipe->kev0 = h->pipe->kev1 = nullptr;
-    if (k0 && !h->pipe->kev_recorded) --h->ev_used;  // nothing was bracketed: hand the pair back
-    if (rc != BF_OK) return fail(h, rc, h->pipe->error().c_str());
-    return BF_OK;
-}
-
-int ensure_staging(bf_handle *h, size_t x_elems, size_t y_elems) {
-    if (x_elems > h->d_x_cap) {
-        if (h->d_x) (void)hipFree(h->d_x);
-        h->d_x = nullptr;
-        h->d_x_cap = 0;
-        BF_HIP(h, hipMalloc((void **)&h->d_x, x_elems * sizeof(float)));
-        h->d_x_cap = x_elems;
-    }
-    if (y_elems > h->d_y_cap) {
-        if (h->d_y) (void)hipFree(h->d_y);
-        h->d_y = nullptr;
-        h->d_y_cap = 0;
-        BF_HIP(h, hipMalloc((void **)&h->d_y, y_elems * sizeof(float)));
-        h->d_y_cap = y_elems;
-    }
+    Engine *eng = h->engine.get();
+    eng->kev0 = k0;
+    eng->kev1 = k1;
+    eng->kev_recorded = false;
+    rc = eng->run(x_dev, (long)n_frames, y_dev, (f64x2 *)spectrum_dev, s, layout, mic_stride, snap);
+    eng->kev0 = eng->kev1 = nullptr;
+    if (k0 && !eng->kev_recorded) --h->ev_used;  // nothing was bracketed, or a launch failed between the two records: hand the pair back
+    if (rc != BF_OK) return fail(h, rc, eng->error().c_str());
     return BF_OK;
 }
 
@@ -433,49 +271,15 @@ int bf_create(const bf_config *cfg, bf_handle **out) {
     BF_CREATE_HIP(hipEventCreate(&h->ev0));
     BF_CREATE_HIP(hipEventCreate(&h->ev1));
 
-    const size_t S = h->n_streams, So = h->n_out;
-    if (uses_fused_das(h)) {
-        const size_t gsz = (size_t)((h->M + 1) / 2) * h->N * h->n_dirs;
-        BF_CREATE_HIP(hipMalloc((void **)&h->d_gains[0], gsz * sizeof(f32x2)));
-        BF_CREATE_HIP(hipMalloc((void **)&h->d_gains[1], gsz * sizeof(f32x2)));
-        std::vector<f32x2> tw = twiddle_table_32x32<f32x2>();
-        if (fused_das_gen(h)) tw = stockham_twiddles<f32x2>(h->N);  // W^m, m < N/2, + the per-pass radix-4 blocks (geometry.hpp)
-        if (h->N < 1024) {
-            const std::vector<f32x2> t32 = twiddle_table_32x32<f32x2>();
-            BF_CREATE_HIP(hipMalloc((void **)&h->d_twiddle_1024, t32.size() * sizeof(f32x2)));
-            BF_CREATE_HIP(hipMemcpy(h->d_twiddle_1024, t32.data(), t32.size() * sizeof(f32x2), hipMemcpyHostToDevice));
-            const size_t gil = (size_t)((h->M + 1) / 2) * 1024 * h->n_dirs;
-            for (int i = 0; i < 2; ++i) BF_CREATE_HIP(hipMalloc((void **)&h->d_gains_il[i], gil * sizeof(f32x2)));
-        }
-        BF_CREATE_HIP(hipMalloc((void **)&h->d_twiddle, tw.size() * sizeof(f32x2)));
-        BF_CREATE_HIP(hipMemcpy(h->d_twiddle, tw.data(), tw.size() * sizeof(f32x2), hipMemcpyHostToDevice));
-        std::vector<double> hd = sqrt_hann(h->N);
-        std::vector<float> hf(h->N);
-        for (int i = 0; i < h->N; ++i) hf[i] = (float)hd[i];
-        BF_CREATE_HIP(hipMalloc((void **)&h->d_window, hf.size() * sizeof(float)));
-        BF_CREATE_HIP(hipMemcpy(h->d_window, hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice));
-        BF_CREATE_HIP(hipMalloc((void **)&h->d_zeros, 2048 * sizeof(float)));
-        BF_CREATE_HIP(hipMemset(h->d_zeros, 0, 2048 * sizeof(float)));
-        BF_CREATE_HIP(hipMalloc((void **)&h->d_hist[0], S * h->M * h->H * sizeof(float)));
-        BF_CREATE_HIP(hipMalloc((void **)&h->d_hist[1], S * h->M * h->H * sizeof(float)));
-        BF_CREATE_HIP(hipMalloc((void **)&h->d_tail[0], So * h->H * sizeof(float)));
-        BF_CREATE_HIP(hipMalloc((void **)&h->d_tail[1], So * h->H * sizeof(float)));
-    } else {
-        h->pipe = BinPipeline::create(h->cfg, h->n_cus);
-        if (!h->pipe) {
-            int rc = fail(nullptr, BF_ENOSYS, "bin pipeline for this algorithm is not built");
-            bf_destroy(h);
-            return rc;
-        }
-        int rc = h->pipe->init();
-        if (rc != BF_OK) {
-            fail(nullptr, rc, h->pipe->error().c_str());
-            bf_destroy(h);
-            return rc;
-        }
-    }
 #undef BF_CREATE_HIP
-    int rc = bf_reset(h);
+    h->engine.reset(Engine::create(h->cfg, h->n_cus));
+    int rc = h->engine->init();
+    if (rc != BF_OK) {
+        fail(nullptr, rc, h->engine->error().c_str());
+        bf_destroy(h);
+        return rc;
+    }
+    rc = bf_reset(h);
     if (rc != BF_OK) {
         bf_destroy(h);
         return rc;
@@ -488,22 +292,6 @@ void bf_destroy(bf_handle *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (int i = 0; i < 2; ++i) {
-        if (h->d_gains[i]) (void)hipFree(h->d_gains[i]);
-        if (h->d_tail[i]) (void)hipFree(h->d_tail[i]);
-        if (h->d_hist[i]) (void)hipFree(h->d_hist[i]);
-    }
-    if (h->d_twiddle) (void)hipFree(h->d_twiddle);
-    if (h->d_twiddle_1024) (void)hipFree(h->d_twiddle_1024);
-    for (int i = 0; i < 2; ++i)
-        if (h->d_gains_il[i]) (void)hipFree(h->d_gains_il[i]);
-    if (h->d_window) (void)hipFree(h->d_window);
-    if (h->d_zeros) (void)hipFree(h->d_zeros);
-    if (h->d_sdump) (void)hipFree(h->d_sdump);
-    if (h->d_sumsq) (void)hipFree(h->d_sumsq);
-    if (h->d_x) (void)hipFree(h->d_x);
-    if (h->d_y) (void)hipFree(h->d_y);
-    if (h->h_pin) (void)hipHostFree(h->h_pin);
     for (auto &pr : h->ev_pool) {
         (void)hipEventDestroy(pr.first);
         (void)hipEventDestroy(pr.second);
@@ -512,11 +300,10 @@ void bf_destroy(bf_handle *h) {
     for (hipEvent_t e : h->ev_out) (void)hipEventDestroy(e);
     if (h->s_h2d) (void)hipStreamDestroy(h->s_h2d);
     if (h->s_d2h) (void)hipStreamDestroy(h->s_d2h);
-    delete h->pipe;
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;  // the engine and every buffer are freed here: after the synchronisation above
 }
 
 // The clears are enqueued on `s` (hipMemsetAsync): they order against the batches the caller runs on the same stream -- a plain
@@ -524,20 +311,9 @@ void bf_destroy(bf_handle *h) {
 int bf_reset_async(bf_handle *h, void *hip_stream) {
     if (!h) return BF_EINVAL;
     BF_HIP(h, hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)hip_stream;
-    const size_t S = h->n_streams;
-    if (uses_fused_das(h)) {
-        // prepare_overlap_and_add: ring pre-filled with one hop of zeros, out_buff calloc'ed (util.h:272-286)
-        BF_HIP(h, hipMemsetAsync(h->d_hist[0], 0, S * h->M * h->H * sizeof(float), s));
-        BF_HIP(h, hipMemsetAsync(h->d_hist[1], 0, S * h->M * h->H * sizeof(float), s));
-        BF_HIP(h, hipMemsetAsync(h->d_tail[0], 0, (size_t)h->n_out * h->H * sizeof(float), s));
-        BF_HIP(h, hipMemsetAsync(h->d_tail[1], 0, (size_t)h->n_out * h->H * sizeof(float), s));
-        h->tail_cur = 0;
-    } else if (h->pipe) {
-        std::lock_guard<std::mutex> lk(h->mu);  // reset() re-arms the gss demixing reset, which /theta also writes
-        int rc = h->pipe->reset(s);
-        if (rc != BF_OK) return fail(h, rc, h->pipe->error().c_str());
-    }
+    std::lock_guard<std::mutex> lk(h->mu);  // reset() re-arms the gss demixing reset, which /theta also writes
+    int rc = h->engine->reset((hipStream_t)hip_stream);
+    if (rc != BF_OK) return fail(h, rc, h->engine->error().c_str());
     return BF_OK;
 }
 
@@ -558,7 +334,7 @@ int bf_set_theta_dir(bf_handle *h, int dir, double degrees) {
     std::lock_guard<std::mutex> lk(h->mu);
     h->angle[dir] = degrees;
     rebuild_steering(h, false, dir);
-    if (h->pipe) h->pipe->on_theta_changed(dir);  // gss resets that beam's demixing matrices (gss.cpp:90-93)
+    h->engine->on_theta_changed(dir);  // gss resets that beam's demixing matrices (gss.cpp:90-93)
     return BF_OK;
 }
 
@@ -571,7 +347,7 @@ int bf_set_thetas(bf_handle *h, const double *degrees, int n) {
     for (int d = 0; d < n; ++d) {
         h->angle[d] = degrees[d];
         rebuild_steering(h, false, d);
-        if (h->pipe) h->pipe->on_theta_changed(d);
+        h->engine->on_theta_changed(d);
     }
     return BF_OK;
 }
@@ -580,10 +356,10 @@ int bf_stream_rms(bf_handle *h, const float *y_dev, size_t n_frames, double *rms
     if (!h || !y_dev || !rms_host || n_frames == 0) return BF_EINVAL;
     BF_HIP(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)hip_stream;
-    if (!h->d_sumsq) BF_HIP(h, hipMalloc((void **)&h->d_sumsq, sizeof(double) * h->n_out));
+    BF_HIP(h, h->d_sumsq.reserve(h->n_out));
     const long n = (long)n_frames * h->H;
-    BF_HIP(h, launch_stream_rms(y_dev, n, h->n_out, h->d_sumsq, s));
-    BF_HIP(h, hipMemcpyAsync(rms_host, h->d_sumsq, sizeof(double) * h->n_out, hipMemcpyDeviceToHost, s));
+    BF_HIP(h, launch_stream_rms(y_dev, n, h->n_out, h->d_sumsq.get(), s));
+    BF_HIP(h, hipMemcpyAsync(rms_host, h->d_sumsq.get(), sizeof(double) * h->n_out, hipMemcpyDeviceToHost, s));
     BF_HIP(h, hipStreamSynchronize(s));
     for (int i = 0; i < h->n_out; ++i) rms_host[i] = std::sqrt(rms_host[i] / (double)n);  // energy2theta.py:23-27
     return BF_OK;
@@ -621,10 +397,10 @@ int bf_set_interference(bf_handle *h, unsigned id, double degrees) {
         h->S = (int)ia.size() + 1;
         for (auto &st : h->steer) st.allocate(h->N, h->M, h->S);
         h->row0_written = false;
-        if (h->pipe) h->pipe->set_columns(h->S);
+        h->engine->set_columns(h->S);
     }
     rebuild_steering(h, false);
-    if (h->pipe) h->pipe->on_theta_changed();  // gss: sep_matrix = weights^H (gss.cpp:90-93)
+    h->engine->on_theta_changed();  // gss: sep_matrix = weights^H (gss.cpp:90-93)
     return BF_OK;
 }
 
@@ -665,8 +441,10 @@ int bf_process_batch(bf_handle *h, const float *x_host, size_t n_frames, float *
     BF_HIP(h, hipSetDevice(h->device));
     const size_t xe = (size_t)h->n_streams * h->M * n_frames * h->H;
     const size_t ye = (size_t)h->n_out * n_frames * h->H;
-    int rc = ensure_staging(h, xe, ye);
-    if (rc != BF_OK) return rc;
+    BF_HIP(h, h->d_x.reserve(xe));
+    BF_HIP(h, h->d_y.reserve(ye));
+    float *const d_x = h->d_x.get(), *const d_y = h->d_y.get();
+    int rc = BF_OK;
     constexpr int kChunks = 8;
     if (h->n_out == 1 && n_frames >= 8192) {
         // One stream of a long batch: H2D of chunk c+1, compute of chunk c and D2H of chunk c-1 overlap (three HIP streams,
@@ -710,21 +488,21 @@ int bf_process_batch(bf_handle *h, const float *x_host, size_t n_frames, float *
             const size_t n = (c0 + cf <= F) ? cf : F - c0;
             const float *xd;
             if (h->cfg.layout == BF_PLANAR) {  // M rows of F*H samples: a chunk is a column block
-                BF_CHUNK(hipMemcpy2DAsync(h->d_x + c0 * H, F * H * sizeof(float), x_host + c0 * H, F * H * sizeof(float),
+                BF_CHUNK(hipMemcpy2DAsync(d_x + c0 * H, F * H * sizeof(float), x_host + c0 * H, F * H * sizeof(float),
                                           n * H * sizeof(float), M, hipMemcpyHostToDevice, h->s_h2d));
-                xd = h->d_x + c0 * H;
+                xd = d_x + c0 * H;
             } else {
-                BF_CHUNK(hipMemcpyAsync(h->d_x + c0 * H * M, x_host + c0 * H * M, n * H * M * sizeof(float), hipMemcpyHostToDevice,
+                BF_CHUNK(hipMemcpyAsync(d_x + c0 * H * M, x_host + c0 * H * M, n * H * M * sizeof(float), hipMemcpyHostToDevice,
                                         h->s_h2d));
-                xd = h->d_x + c0 * H * M;
+                xd = d_x + c0 * H * M;
             }
             BF_CHUNK(hipEventRecord(h->ev_in[c], h->s_h2d));
             BF_CHUNK(hipStreamWaitEvent(h->stream, h->ev_in[c], 0));
             if (e == hipSuccess)
-                rc = run_batch_device(h, xd, n, h->d_y + c0 * H, nullptr, h->stream, h->cfg.layout, (long)(F * H));
+                rc = run_batch_device(h, xd, n, d_y + c0 * H, nullptr, h->stream, h->cfg.layout, (long)(F * H));
             BF_CHUNK(hipEventRecord(h->ev_out[c], h->stream));
             BF_CHUNK(hipStreamWaitEvent(h->s_d2h, h->ev_out[c], 0));
-            BF_CHUNK(hipMemcpyAsync(y_host + c0 * H, h->d_y + c0 * H, n * H * sizeof(float), hipMemcpyDeviceToHost, h->s_d2h));
+            BF_CHUNK(hipMemcpyAsync(y_host + c0 * H, d_y + c0 * H, n * H * sizeof(float), hipMemcpyDeviceToHost, h->s_d2h));
         }
 #undef BF_CHUNK
         // success or not: nothing may still be copying from / into the caller's buffers when this returns
@@ -735,10 +513,10 @@ int bf_process_batch(bf_handle *h, const float *x_host, size_t n_frames, float *
             return fail(h, BF_EIO, "bf_process_batch: stream synchronisation", e1 != hipSuccess ? e1 : (e2 != hipSuccess ? e2 : e3));
         return BF_OK;
     }
-    BF_HIP(h, hipMemcpyAsync(h->d_x, x_host, xe * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    rc = run_batch_device(h, h->d_x, n_frames, h->d_y, nullptr, h->stream, h->cfg.layout, (long)n_frames * h->H);
+    BF_HIP(h, hipMemcpyAsync(d_x, x_host, xe * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    rc = run_batch_device(h, d_x, n_frames, d_y, nullptr, h->stream, h->cfg.layout, (long)n_frames * h->H);
     if (rc != BF_OK) return rc;
-    BF_HIP(h, hipMemcpyAsync(y_host, h->d_y, ye * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    BF_HIP(h, hipMemcpyAsync(y_host, d_y, ye * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     BF_HIP(h, hipStreamSynchronize(h->stream));
     return BF_OK;
 }
@@ -748,21 +526,22 @@ int bf_process_hop(bf_handle *h, const float *const *in, float *out, uint32_t nf
     if ((int)nframes != h->H) return fail(h, BF_EINVAL, "nframes must equal the configured hop");
     if (h->n_streams != 1) return fail(h, BF_EINVAL, "bf_process_hop drives stream 0 of a single-stream handle");
     BF_HIP(h, hipSetDevice(h->device));
-    int rc = ensure_staging(h, (size_t)h->M * h->H, (size_t)h->n_out * h->H);
-    if (rc != BF_OK) return rc;
     const size_t n_in = (size_t)h->M * h->H, n_outv = (size_t)h->n_out * h->H;
-    if (!h->h_pin) BF_HIP(h, hipHostMalloc((void **)&h->h_pin, (n_in + n_outv) * sizeof(float), hipHostMallocDefault));
-    float *packed = h->h_pin, *res = h->h_pin + n_in;
+    BF_HIP(h, h->d_x.reserve(n_in));
+    BF_HIP(h, h->d_y.reserve(n_outv));
+    BF_HIP(h, h->h_pin.reserve(n_in + n_outv));
+    float *const d_x = h->d_x.get(), *const d_y = h->d_y.get();
+    float *packed = h->h_pin.get(), *res = packed + n_in;
     if (h->cfg.layout == BF_PLANAR) {
         for (int m = 0; m < h->M; ++m) memcpy(packed + (size_t)m * h->H, in[m], sizeof(float) * h->H);
     } else {
         for (int m = 0; m < h->M; ++m)
             for (int n = 0; n < h->H; ++n) packed[(size_t)n * h->M + m] = in[m][n];
     }
-    BF_HIP(h, hipMemcpyAsync(h->d_x, packed, n_in * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    rc = run_batch_device(h, h->d_x, 1, h->d_y, nullptr, h->stream, h->cfg.layout, (long)h->H);
+    BF_HIP(h, hipMemcpyAsync(d_x, packed, n_in * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    int rc = run_batch_device(h, d_x, 1, d_y, nullptr, h->stream, h->cfg.layout, (long)h->H);
     if (rc != BF_OK) return rc;
-    BF_HIP(h, hipMemcpyAsync(res, h->d_y, n_outv * sizeof(float), hipMemcpyDeviceToHost, h->stream));  // [dir][hop]
+    BF_HIP(h, hipMemcpyAsync(res, d_y, n_outv * sizeof(float), hipMemcpyDeviceToHost, h->stream));  // [dir][hop]
     BF_HIP(h, hipStreamSynchronize(h->stream));
     memcpy(out, res, n_outv * sizeof(float));
     return BF_OK;
@@ -951,12 +730,7 @@ static uint64_t state_cfg_hash(const bf_handle *h) {
 
 size_t bf_state_size(const bf_handle *h) {
     if (!h) return 0;
-    size_t payload;
-    if (uses_fused_das(h))
-        payload = ((size_t)h->n_streams * h->M * h->H + (size_t)h->n_out * h->H) * sizeof(float);
-    else
-        payload = h->pipe ? h->pipe->state_bytes() : 0;
-    return sizeof(bf_state_header) + sizeof(bf_state_control) + payload;
+    return sizeof(bf_state_header) + sizeof(bf_state_control) + h->engine->state_bytes();
 }
 
 int bf_get_state(bf_handle *h, void *blob, size_t size) {
@@ -977,20 +751,14 @@ int bf_get_state(bf_handle *h, void *blob, size_t size) {
         ct.kp1 = (uint32_t)h->S;
         ct.row0_written = h->row0_written ? 1u : 0u;
         ct.cfg_hash = state_cfg_hash(h);
-        ct.gss_pending = h->pipe ? h->pipe->pending_resets() : 0ull;
+        ct.gss_pending = h->engine->pending_resets();
         for (int d = 0; d < h->n_dirs; ++d) ct.theta[d] = h->angle[d];
         for (size_t k = 0; k < h->interf.size(); ++k) ct.interf[k] = h->interf[k];
     }
     memcpy((char *)blob + sizeof(hd), &ct, sizeof(ct));
     char *p = (char *)blob + sizeof(hd) + sizeof(ct);
-    if (uses_fused_das(h)) {
-        const size_t hb = (size_t)h->n_streams * h->M * h->H * sizeof(float), tb = (size_t)h->n_out * h->H * sizeof(float);
-        BF_HIP(h, hipMemcpy(p, h->d_hist[h->tail_cur], hb, hipMemcpyDeviceToHost));
-        BF_HIP(h, hipMemcpy(p + hb, h->d_tail[h->tail_cur], tb, hipMemcpyDeviceToHost));
-        return BF_OK;
-    }
-    int rc = h->pipe->get_state(p);
-    return rc == BF_OK ? BF_OK : fail(h, rc, h->pipe->error().c_str());
+    int rc = h->engine->get_state(p);
+    return rc == BF_OK ? BF_OK : fail(h, rc, h->engine->error().c_str());
 }
 
 int bf_set_state(bf_handle *h, const void *blob, size_t size) {
@@ -1026,17 +794,11 @@ int bf_set_state(bf_handle *h, const void *blob, size_t size) {
             for (int c = 0; c < st.n_cols; ++c)
                 for (int j = 0; j < st.n_fft; ++j) st.at(j, 0, c) = ct.row0_written ? cplxd(1.0, 0.0) : cplxd(0.0, 0.0);
         rebuild_steering(h, false);
-        if (h->pipe) h->pipe->set_pending_resets(ct.gss_pending);
+        h->engine->set_pending_resets(ct.gss_pending);
     }
     const char *p = (const char *)blob + sizeof(hd) + sizeof(ct);
-    if (uses_fused_das(h)) {
-        const size_t hb = (size_t)h->n_streams * h->M * h->H * sizeof(float), tb = (size_t)h->n_out * h->H * sizeof(float);
-        BF_HIP(h, hipMemcpy(h->d_hist[h->tail_cur], p, hb, hipMemcpyHostToDevice));
-        BF_HIP(h, hipMemcpy(h->d_tail[h->tail_cur], p + hb, tb, hipMemcpyHostToDevice));
-        return BF_OK;
-    }
-    int rc = h->pipe->set_state(p);
-    return rc == BF_OK ? BF_OK : fail(h, rc, h->pipe->error().c_str());
+    int rc = h->engine->set_state(p);
+    return rc == BF_OK ? BF_OK : fail(h, rc, h->engine->error().c_str());
 }
 
 }  // extern "C"

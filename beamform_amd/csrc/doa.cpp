@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/bfcore.h"
+#include "device_mem.hpp"
 #include "doa.hpp"
 #include "geometry.hpp"
 #include "pipeline_kernels.hpp"
@@ -23,19 +24,18 @@ struct bf_doa {
     std::string err;
     const KernelSet *ks = nullptr;
     hipStream_t stream = nullptr;                 // bf_doa_process (host buffers)
-    f64x2 *d_steer = nullptr, *d_tw = nullptr;    // [bin - klo][mic][angle]; forward-transform twiddles
-    double *d_win = nullptr;                      // sqrt-Hann
-    float *d_hist = nullptr;                      // [stream][hop before the next frame], layout as the input
+    DeviceBuffer<f64x2> d_steer, d_tw;            // [bin - klo][mic][angle]; forward-transform twiddles
+    DeviceBuffer<double> d_win;                   // sqrt-Hann
+    DeviceBuffer<float> d_hist;                   // [stream][hop before the next frame], layout as the input
     // scratch for one chunk of `cap` frames (allocated on first use, grown up to the budget, kept)
     long cap = 0;
-    f64x2 *d_Z = nullptr;
-    unsigned *d_flags = nullptr;
-    double *d_part = nullptr;
-    // staging of bf_doa_process
-    float *d_x = nullptr;
-    double *d_map = nullptr;
-    int32_t *d_peak = nullptr;
-    size_t x_cap = 0, map_cap = 0, peak_cap = 0;
+    DeviceBuffer<f64x2> d_Z;
+    DeviceBuffer<unsigned> d_flags;
+    DeviceBuffer<double> d_part;
+    // staging of bf_doa_process (grown on demand)
+    DeviceBuffer<float> d_x;
+    DeviceBuffer<double> d_map;
+    DeviceBuffer<int32_t> d_peak;
 };
 
 namespace {
@@ -75,29 +75,15 @@ long chunk_budget(const bf_doa *d) {
 int ensure_scratch(bf_doa *d, long frames) {
     if (frames <= d->cap) return BF_OK;
     DOA_HIP(d, hipDeviceSynchronize());  // a batch still in flight may read the old buffers
-    (void)hipFree(d->d_Z);
-    (void)hipFree(d->d_flags);
-    (void)hipFree(d->d_part);
-    d->d_Z = nullptr;
-    d->d_flags = nullptr;
-    d->d_part = nullptr;
     d->cap = 0;
     const size_t S = d->S;
-    if (hipMalloc((void **)&d->d_Z, S * frames * d->NP * d->N * sizeof(f64x2)) != hipSuccess ||
-        hipMalloc((void **)&d->d_flags, S * (frames + 1) * 2 * sizeof(unsigned)) != hipSuccess ||
-        hipMalloc((void **)&d->d_part, (size_t)d->G * S * frames * d->D * sizeof(double)) != hipSuccess) {
+    if (d->d_Z.reserve(S * frames * d->NP * d->N) != hipSuccess || d->d_flags.reserve(S * (frames + 1) * 2) != hipSuccess ||
+        d->d_part.reserve((size_t)d->G * S * frames * d->D) != hipSuccess) {
         (void)hipGetLastError();
         return fail(d, BF_ENOMEM, "bf_doa scratch");
     }
     d->cap = frames;
     return BF_OK;
-}
-
-void release(bf_doa *d) {
-    void *ptrs[] = {d->d_steer, d->d_tw, d->d_win, d->d_hist, d->d_Z, d->d_flags, d->d_part, d->d_x, d->d_map, d->d_peak};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
 }
 
 }  // namespace
@@ -156,8 +142,7 @@ int bf_doa_create(const bf_config *cfg, const double *angles_deg, int n_angles, 
         hipError_t e_ = (call);                               \
         if (e_ != hipSuccess) {                               \
             int rc_ = fail(nullptr, BF_EIO, #call, e_);       \
-            release(d);                                       \
-            delete d;                                         \
+            bf_doa_destroy(d);                                \
             return rc_;                                       \
         }                                                     \
     } while (0)
@@ -185,16 +170,11 @@ int bf_doa_create(const bf_config *cfg, const double *angles_deg, int n_angles, 
                 T[((size_t)kk * M + m) * n_angles + a] = f64x2{w.real(), w.imag()};
             }
     }
-    DOA_CREATE_HIP(hipMalloc((void **)&d->d_steer, table));
-    DOA_CREATE_HIP(hipMemcpy(d->d_steer, T.data(), table, hipMemcpyHostToDevice));
-    const std::vector<f64x2> tw = N == 1024 ? twiddle_table_32x32<f64x2>() : stockham_twiddles<f64x2>(N);
-    DOA_CREATE_HIP(hipMalloc((void **)&d->d_tw, tw.size() * sizeof(f64x2)));
-    DOA_CREATE_HIP(hipMemcpy(d->d_tw, tw.data(), tw.size() * sizeof(f64x2), hipMemcpyHostToDevice));
-    const std::vector<double> win = sqrt_hann(N);
-    DOA_CREATE_HIP(hipMalloc((void **)&d->d_win, win.size() * sizeof(double)));
-    DOA_CREATE_HIP(hipMemcpy(d->d_win, win.data(), win.size() * sizeof(double), hipMemcpyHostToDevice));
-    DOA_CREATE_HIP(hipMalloc((void **)&d->d_hist, (size_t)d->S * M * H * sizeof(float)));
-    DOA_CREATE_HIP(hipMemset(d->d_hist, 0, (size_t)d->S * M * H * sizeof(float)));
+    DOA_CREATE_HIP(d->d_steer.upload(T));
+    DOA_CREATE_HIP(d->d_tw.upload(N == 1024 ? twiddle_table_32x32<f64x2>() : stockham_twiddles<f64x2>(N)));
+    DOA_CREATE_HIP(d->d_win.upload(sqrt_hann(N)));
+    DOA_CREATE_HIP(d->d_hist.alloc((size_t)d->S * M * H));
+    DOA_CREATE_HIP(hipMemset(d->d_hist.get(), 0, (size_t)d->S * M * H * sizeof(float)));
 #undef DOA_CREATE_HIP
     *out = d;
     return BF_OK;
@@ -224,13 +204,13 @@ int bf_doa_process_device(bf_doa *d, const float *x_dev, size_t n_frames, double
     for (long c0 = 0; c0 < F; c0 += CF) {
         const long n = std::min(CF, F - c0);
         const float *xc = x_dev + (d->layout == BF_PLANAR ? c0 * H : c0 * (long)H * M);
-        DOA_HIP(d, launch_doa_hop_flags(xc, d->d_hist, d->d_flags, n, mic_stride, stream_stride, d->S, M, H, d->layout, s));
+        DOA_HIP(d, launch_doa_hop_flags(xc, d->d_hist.get(), d->d_flags.get(), n, mic_stride, stream_stride, d->S, M, H, d->layout, s));
         StftArgs sa{};
         sa.x = xc;
-        sa.hist = d->d_hist;
-        sa.Z = d->d_Z;
-        sa.tw = d->d_tw;
-        sa.win = d->d_win;
+        sa.hist = d->d_hist.get();
+        sa.Z = d->d_Z.get();
+        sa.tw = d->d_tw.get();
+        sa.win = d->d_win.get();
         sa.n_frames = n;
         sa.frames_ws = CF;
         sa.frame_off = 0;
@@ -252,10 +232,10 @@ int bf_doa_process_device(bf_doa *d, const float *x_dev, size_t n_frames, double
         sa.run_len = 1;
         DOA_HIP(d, d->ks->stft(sa, d->n_cus, s));
         DoaMapArgs ma;
-        ma.Z = d->d_Z;
-        ma.flags = d->d_flags;
-        ma.steer = d->d_steer;
-        ma.part = d->d_part;
+        ma.Z = d->d_Z.get();
+        ma.flags = d->d_flags.get();
+        ma.steer = d->d_steer.get();
+        ma.part = d->d_part.get();
         ma.eps = d->eps;
         ma.n_frames = n;
         ma.frames_ws = CF;
@@ -267,7 +247,7 @@ int bf_doa_process_device(bf_doa *d, const float *x_dev, size_t n_frames, double
         ma.n_bins = d->nK;
         DOA_HIP(d, launch_doa_map(ma, s));
         DoaReduceArgs ra;
-        ra.part = d->d_part;
+        ra.part = d->d_part.get();
         ra.map = map_dev;
         ra.peak = peak_dev;
         ra.scale = 1.0 / ((double)d->W * d->nK * M * M);
@@ -280,13 +260,8 @@ int bf_doa_process_device(bf_doa *d, const float *x_dev, size_t n_frames, double
         ra.n_segments = d->G;
         ra.frames_per_block = d->W;
         DOA_HIP(d, launch_doa_reduce(ra, s));
-        // the chunk's last hop is the next chunk's (and the next call's) hop -1 (util.h:305-308)
-        if (d->layout == BF_PLANAR)
-            DOA_HIP(d, hipMemcpy2DAsync(d->d_hist, H * sizeof(float), xc + (n - 1) * H, (size_t)mic_stride * sizeof(float), H * sizeof(float),
-                                        (size_t)d->S * M, hipMemcpyDeviceToDevice, s));
-        else
-            DOA_HIP(d, hipMemcpy2DAsync(d->d_hist, (size_t)H * M * sizeof(float), xc + (n - 1) * (long)H * M, (size_t)stream_stride * sizeof(float),
-                                        (size_t)H * M * sizeof(float), (size_t)d->S, hipMemcpyDeviceToDevice, s));
+        // the chunk's last hop is the next chunk's (and the next call's) hop -1
+        DOA_HIP(d, carry_last_hop(d->d_hist.get(), xc, n, H, M, d->S, d->layout, mic_stride, stream_stride, s));
     }
     return BF_OK;
 }
@@ -299,28 +274,22 @@ int bf_doa_process(bf_doa *d, const float *x_host, size_t n_frames, double *map_
     if (!x_host) return fail(d, BF_EINVAL, "bf_doa_process: x is NULL");
     DOA_HIP(d, hipSetDevice(d->device));
     const size_t xe = (size_t)d->S * d->M * n_frames * d->H, nb = (size_t)d->S * (n_frames / d->W), me = nb * d->D;
-    auto grow = [&](void **p, size_t &cap, size_t bytes) -> int {
-        if (bytes <= cap) return BF_OK;
-        DOA_HIP(d, hipStreamSynchronize(d->stream));
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-        cap = 0;
-        if (hipMalloc(p, bytes) != hipSuccess) {
+    if (xe > d->d_x.size() || (map_host && me > d->d_map.size()) || (peak_host && nb > d->d_peak.size())) {
+        DOA_HIP(d, hipStreamSynchronize(d->stream));  // a batch still in flight may use the old staging
+        if (d->d_x.reserve(xe) != hipSuccess || (map_host && d->d_map.reserve(me) != hipSuccess) ||
+            (peak_host && d->d_peak.reserve(nb) != hipSuccess)) {
             (void)hipGetLastError();
             return fail(d, BF_ENOMEM, "bf_doa_process staging");
         }
-        cap = bytes;
-        return BF_OK;
-    };
-    int rc = grow((void **)&d->d_x, d->x_cap, xe * sizeof(float));
-    if (rc == BF_OK && map_host) rc = grow((void **)&d->d_map, d->map_cap, me * sizeof(double));
-    if (rc == BF_OK && peak_host) rc = grow((void **)&d->d_peak, d->peak_cap, nb * sizeof(int32_t));
+    }
+    float *const d_x = d->d_x.get();
+    double *const d_map = map_host ? d->d_map.get() : nullptr;
+    int32_t *const d_peak = peak_host ? d->d_peak.get() : nullptr;
+    DOA_HIP(d, hipMemcpyAsync(d_x, x_host, xe * sizeof(float), hipMemcpyHostToDevice, d->stream));
+    const int rc = bf_doa_process_device(d, d_x, n_frames, d_map, d_peak, d->stream);
     if (rc != BF_OK) return rc;
-    DOA_HIP(d, hipMemcpyAsync(d->d_x, x_host, xe * sizeof(float), hipMemcpyHostToDevice, d->stream));
-    rc = bf_doa_process_device(d, d->d_x, n_frames, map_host ? d->d_map : nullptr, peak_host ? d->d_peak : nullptr, d->stream);
-    if (rc != BF_OK) return rc;
-    if (map_host) DOA_HIP(d, hipMemcpyAsync(map_host, d->d_map, me * sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    if (peak_host) DOA_HIP(d, hipMemcpyAsync(peak_host, d->d_peak, nb * sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
+    if (map_host) DOA_HIP(d, hipMemcpyAsync(map_host, d_map, me * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if (peak_host) DOA_HIP(d, hipMemcpyAsync(peak_host, d_peak, nb * sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
     DOA_HIP(d, hipStreamSynchronize(d->stream));
     return BF_OK;
 }
@@ -329,7 +298,7 @@ int bf_doa_reset(bf_doa *d) {
     if (!d) return fail(nullptr, BF_EINVAL, "bf_doa_reset: handle is NULL");
     DOA_HIP(d, hipSetDevice(d->device));
     DOA_HIP(d, hipDeviceSynchronize());  // batches enqueued on any stream finish with the old history
-    DOA_HIP(d, hipMemset(d->d_hist, 0, (size_t)d->S * d->M * d->H * sizeof(float)));
+    DOA_HIP(d, hipMemset(d->d_hist.get(), 0, (size_t)d->S * d->M * d->H * sizeof(float)));
     return BF_OK;
 }
 
@@ -337,6 +306,6 @@ void bf_doa_destroy(bf_doa *d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();
-    release(d);
-    delete d;
+    if (d->stream) (void)hipStreamDestroy(d->stream);
+    delete d;  // the buffers are freed here: after the synchronisation above
 }

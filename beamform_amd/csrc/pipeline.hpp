@@ -1,7 +1,9 @@
-// pipeline.hpp -- the fp64 "bin pipeline" used by every node except fused DAS:
-//   STFT kernel (window + forward FFTs, spectra to HBM)
-//   -> per-bin kernel (the node's apply_weights loop body)
-//   -> ISTFT kernel (backward FFT, synthesis window, overlap-add).
+// pipeline.hpp -- the engine behind a bf_handle: what capi.cpp drives, whatever the node.  Two implementations:
+//   the fused fp32 das kernels (das_fused_engine.cpp), one launch per batch, and
+//   the fp64 "bin pipeline" of every other node (pipeline.hip):
+//     STFT kernel (window + forward FFTs, spectra to HBM)
+//     -> per-bin kernel (the node's apply_weights loop body)
+//     -> ISTFT kernel (backward FFT, synthesis window, overlap-add).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,14 +37,15 @@ struct RunSnapshot {
     const f64x2 *das_gains_w64 = nullptr;  // the same gains in the register / lane order of the 64-lane kernel (das_f64_w64.hip)
 };
 
-class BinPipeline {
+class Engine {
    public:
-    // nullptr when the algorithm is not built
-    static BinPipeline *create(const bf_config &cfg, int n_cus);
-    virtual ~BinPipeline() {}
+    // the fused fp32 das engine for BF_DAS with BF_DAS_FUSED_F32, the bin pipeline otherwise; never null
+    static Engine *create(const bf_config &cfg, int n_cus);
+    virtual ~Engine() {}
     virtual int init() = 0;
     virtual int reset(hipStream_t stream) = 0;  // clears enqueued on `stream`
-    virtual int upload_steering(const std::vector<SteeringSet> &dirs, hipStream_t stream) = 0;  // one set per look direction
+    // one set per look direction; stream-ordered and double-buffered, so a batch already in flight keeps reading the table it was launched with
+    virtual int upload_steering(const std::vector<SteeringSet> &dirs, hipStream_t stream) = 0;
     virtual void on_theta_changed(int dir = -1) = 0;  // dir < 0: every look direction
     virtual void set_columns(int kp1) = 0;  // interferer added/removed (lcmv.cpp:266-305)
     // caller holds the control-plane mutex: hands the pending demixing resets to this run and clears them
@@ -57,13 +60,26 @@ class BinPipeline {
     virtual int get_state(void *host) = 0;
     virtual int set_state(const void *host) = 0;
     const std::string &error() const { return err_; }
-    // set by the caller around run(): when non-null and the run has ONE dominant kernel (das fp64 in one launch), the two events are
-    // recorded on the run's stream right before and after that launch and kev_recorded is raised (bf_kernel_timing_begin / _end)
+    // set by the caller around run(): when non-null and the run has ONE dominant kernel (fused fp32 das; das fp64 in one launch), the two
+    // events are recorded on the run's stream right before and after that launch (or its launches, one per 16 look directions) and
+    // kev_recorded is raised once the second record has succeeded (bf_kernel_timing_begin / _end)
     hipEvent_t kev0 = nullptr, kev1 = nullptr;
     bool kev_recorded = false;
 
    protected:
     std::string err_;
 };
+
+Engine *make_das_fused_engine(const bf_config &cfg, int n_cus);  // das_fused_engine.cpp
+
+// inside a member of an Engine: a failed HIP call becomes error() = "<call>: <HIP string>" and BF_EIO
+#define ENGINE_HIP(call)                                                      \
+    do {                                                                      \
+        hipError_t e_ = (call);                                               \
+        if (e_ != hipSuccess) {                                               \
+            err_ = std::string(#call) + ": " + hipGetErrorString(e_);         \
+            return BF_EIO;                                                    \
+        }                                                                     \
+    } while (0)
 
 }  // namespace bf

@@ -67,8 +67,9 @@ enum bf_das_impl {
                              bar); also the only das path with register-resident kernels at JACK periods other than 512 and with
                              look directions that share their forward transforms */
     BF_DAS_F64 = 1        /* default: double arithmetic like das.cpp.  Period 512, <= 8 microphones, one look direction, no spectrum
-                             dump: ONE launch (das_f64_pair_kernel: planar input; das_f64_w64_kernel: [sample][mic]); anything else
-                             runs STFT -> per-bin kernel -> ISTFT and can dump the full N-bin spectrum */
+                             dump: ONE launch of the frame-pair kernel (das_f64_pair_kernel on planar input; on [sample][mic] input
+                             das_f64_ring_kernel for 2, 4 or 8 microphones, a transposition in front of das_f64_pair_kernel otherwise);
+                             anything else runs STFT -> per-bin kernel -> ISTFT and can dump the full N-bin spectrum */
 };
 
 /* Arithmetic of what lies between the transforms (every node computes its per-bin stage in double).
