@@ -2,6 +2,7 @@
 // onto lanes (thread-per-problem, row-per-lane over LDS, cyclic rows over DPP quads, row-per-lane over DPP rows).
 #include "launch_trace.hpp"
 #include "bins_common.hpp"
+#include "switches.hpp"
 
 #include <cmath>
 #include <vector>
@@ -995,9 +996,7 @@ hipError_t launch_mvdr_lcmv(const BinsArgs &a, int n_cus, hipStream_t s) {
     if (a.n_frames < tile) tile = (int)a.n_frames;
     const int tps = (int)((a.n_frames + tile - 1) / tile);
     const int M = a.n_mics, km = a.kp1 <= 1 ? 1 : 4;
-    static const bool no_fast_env = getenv("BF_MVDR_GROUP") && atoi(getenv("BF_MVDR_GROUP")) != 0;
-    const bool no_fast = no_fast_env;
-    const bool no_2d = no_fast_env;
+    const bool no_fast = switches().mvdr_group, no_2d = no_fast;
     // frequencies of the irregular problems (quirk Q1, util.h:190-199): f[N/2] = 0, f[N/2+1] = -(N/2-1) sr/N
     const double f_qx = (double)(kN / 2 - 1) * a.cfg.sample_rate / (double)kN;
     const bool band_hits_nyquist = (0.0 >= a.cfg.freq_min && 0.0 <= a.cfg.freq_max) || (f_qx >= a.cfg.freq_min && f_qx <= a.cfg.freq_max);
@@ -1064,7 +1063,7 @@ hipError_t launch_mvdr_lcmv(const BinsArgs &a, int n_cus, hipStream_t s) {
         // tile length: the wavefronts (64 lanes = 64 (tile, problem) pairs) should fill the 4 x CUs slots a whole number of times;
         // cost of a choice = rounds x (frames walked + P warm-up frames); BF_MVDR_TILE forces a length (tests: lanes that straddle tiles,
         // a short last tile)
-        static const int ft_env = getenv("BF_MVDR_TILE") ? atoi(getenv("BF_MVDR_TILE")) : 0;
+        const int ft_env = switches().mvdr_tile;
         // resident wavefronts per CU: the prefetch buffers (2 x 2 MP rows of 1 KiB in LDS) and the register count of the instantiation
         // that will run decide -- 8 microphones: one per SIMD (512 registers); fewer microphones: more
         const int mp_ = M <= 2 ? 2 : M <= 4 ? 4 : M <= 6 ? 6 : 8;

@@ -1,14 +1,18 @@
 // das_f64_w64.hip -- das at the reference's precision (double arithmetic, das.cpp:47-70 + util.h:217-314), one launch,
 // one full wavefront per transform (fft1024_w64.hpp: 64 lanes x 16 points, 16 x 16 x 4).
 //
-// Two kernels share the transform machinery:
-//   das_f64_pair_kernel  planar input (the bench headline).  A complex transform carries frames t and t + 1 of ONE microphone;
-//                        U = sum_m ce_m Z_m with the per-microphone Hermitian gains, one backward transform returns both frames
-//                        (real / imaginary part): 4.5 transforms per frame.  Frame pairs are handed out to the eight wavefronts of
-//                        a block through an LDS counter, the overlap-add between pairs is first come first served (below).
-//   das_f64_w64_kernel   [sample][mic] input.  A transform carries two microphones of one frame (one 8-byte
-//                        load per sample), S += D_p Z_p with the Hermitian-part pair gains (das_pair_gains_t), Re of the backward
-//                        transform: 5 transforms per frame; wavefront w of a block takes frame T0 + 8 it + w.
+// Two kernels share the transform machinery (das_f64_decide picks per batch, docs/DISPATCH.md):
+//   das_f64_pair_kernel  planar input (the bench headline), and [sample][mic] input behind interleaved_to_planar_kernel; as
+//   das_f64_ring_kernel  [sample][mic] input with 2, 4 or 8 microphones, transposed hop by hop into the blocks' rings.  A complex
+//                        transform carries frames t and t + 1 of ONE microphone; U = sum_m ce_m Z_m with the per-microphone
+//                        Hermitian gains, one backward transform returns both frames (real / imaginary part).  Microphone 0 (unit
+//                        weight row) is added in the time domain and identical weight rows share a transform: (n_tr + 1) / 2
+//                        transforms per frame, 4 at 8 microphones.  Frame pairs are handed out to the eight wavefronts of a block
+//                        through an LDS work word, the overlap-add between pairs is first come first served (below).
+//   das_f64_w64_kernel   [sample][mic] input the frame-pair kernels cannot take (one microphone, a non-unit row 0).  A transform
+//                        carries two microphones of one frame (one 8-byte load per sample), S += D_p Z_p with the Hermitian-part
+//                        pair gains (das_pair_gains_t), Re of the backward transform: 5 transforms per frame at 8 microphones;
+//                        wavefront w of a block takes frame T0 + 8 it + w.
 // Both: (float)Re, float x double window, float overlap-add (util.h:247-252,301-302), 1/N inside the gains.
 //
 // Mapping onto the chip (what differs from round 3's 32 x 32 half-wavefront kernel):
@@ -18,20 +22,18 @@
 //     contiguous 256-byte row; the hop two consecutive frames (pairs) share is fetched by two wavefronts of the same CU within
 //     microseconds (L1 / L2): each sample leaves HBM once.
 //   * no block barrier after the table copy.  Run boundaries: two float atomic adds into a hop zeroed beforehand
-//     (prepare_das_f64_w64), bit-exact because a + b == b + a.
+//     (enqueue_das_f64), bit-exact because a + b == b + a.
 //
 // LDS (155-159 KB): twiddles W1024^(k1 lane) + tw2' (16 KB), 8 x 8.1 KB exchange planes (16 rows x 65 doubles, one scalar plane per
 // wavefront: real parts, then imaginary parts), 64-65 KB gains, 9 KB window rows, flags.  Exchange layout: fft1024_w64.hpp
 // w64_col_rot (every ds_read_b64 / ds_write_b64 group lands on distinct bank pairs).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 #include "launch_trace.hpp"
-#include "das_f64_plan.hpp"
 #include "pipeline_kernels.hpp"
+#include "switches.hpp"
 #include "w64_f64_dev.hpp"
 
 namespace bf {
@@ -1095,21 +1097,6 @@ __global__ __launch_bounds__(256) void interleaved_to_planar_kernel(const float 
 
 }  // namespace
 
-// planar input: the frame-pair kernel; [sample][mic] input: the microphone-pair kernel
-// (the frame-pair kernel never transforms microphone 0: it needs the reference's unit weight row there -- das.cpp:33-38, always true for das
-// on a handle that started cold -- and a second microphone; anything else goes through the chain)
-static bool ring_mics(int m) { return m == 2 || m == 4 || m == 8; }  // (the ring's transposition addresses by shifts)
-static bool use_pair_kernel(const DasF64Args &a) {
-    if (!(a.gains_mic != nullptr && a.sched_ws != nullptr && a.mic0_unit != 0 && a.n_mics >= 2 && a.n_tr >= 1)) return false;
-    if (a.layout == 0) return true;
-    return a.ring != nullptr && ring_mics(a.n_mics) && a.hist_out == nullptr;  // [sample][mic]: through the blocks' hop rings
-}
-size_t das_f64_ring_bytes(int n_mics, int n_cus) {
-    return ring_mics(n_mics) ? (size_t)n_cus * kRingSlots * n_mics * kHop * sizeof(float) : 0;
-}
-
-bool das_f64_writes_hist(const DasF64Args &a) { return use_pair_kernel(a) && a.hist_out != nullptr; }
-
 // ---- the frame-pair kernel's work queue ------------------------------------------------------------------------------------------
 // Per stream: nb = blocks per stream (n_cus / n_streams, at least 1).  Level 0 gives every block one long chunk (kSchedFirst of its
 // equal share: consecutive pairs on one CU share their input hop through L1 / L2 and hand over their output hop through LDS flags),
@@ -1119,71 +1106,79 @@ bool das_f64_writes_hist(const DasF64Args &a) { return use_pair_kernel(a) && a.h
 constexpr size_t kSchedCounterBytes = 256;
 size_t das_f64_sched_ws_bytes() { return kSchedCounterBytes + (size_t)kSchedMaxChunks * sizeof(int4); }
 
-// frames per run of the microphone-pair kernel: a multiple of one step of the block (8 frames), about one run per CU
-static void das_f64_w64_runs(const DasF64Args &a, int n_cus, long *fpc, long *cps) {
-    const long step = kWaves;
-    long runs = (long)n_cus / a.n_streams;
-    if (runs < 1) runs = 1;
-    long f = (a.n_frames + runs - 1) / runs;
-    f = ((f + step - 1) / step) * step;
-    *fpc = f;
-    *cps = (a.n_frames + f - 1) / f;
-}
-
-// what has to happen on `s` before the kernel: the frame-pair kernel's chunk table, counter and zeroed chunk-boundary hops (one small
-// launch); the microphone-pair kernel: the first hop of every run but the first of a stream zeroed (it is completed by atomic adds)
-hipError_t prepare_das_f64_w64(const DasF64Args &a, int n_cus, hipStream_t s) {
-    if (a.n_mics > 8) return hipErrorNotSupported;  // the gain tables fill the LDS
-    if (use_pair_kernel(a)) {
-        if (a.sched_ws_bytes < das_f64_sched_ws_bytes() || (long)a.n_streams * ((a.n_frames + 1) / 2) >= (1L << 31)) return hipErrorNotSupported;
-        const DasSchedPlan p = das_f64_plan(a.n_frames, a.n_streams, n_cus, getenv("BF_DAS_F64_SCHED"));
-        if (p.n_chunks < 1 || p.n_chunks > kSchedMaxChunks) return hipErrorNotSupported;  // (more streams than the table has rows: the chain serves them)
-        unsigned *counter = reinterpret_cast<unsigned *>(a.sched_ws);
-        int4 *chunks = reinterpret_cast<int4 *>(reinterpret_cast<char *>(a.sched_ws) + kSchedCounterBytes);
-        BF_LAUNCH(das_f64_sched_kernel, dim3((unsigned)((p.n_chunks + kSchedPerBlock - 1) / kSchedPerBlock)), dim3(32 * kSchedPerBlock), 0, s, p, chunks, counter, a.y, a.n_frames, a.n_streams);
-        return hipGetLastError();
+// Which kernel serves a batch (docs/DISPATCH.md).  The frame-pair kernels -- das_f64_pair_kernel on planar input; on [sample][mic] input
+// das_f64_ring_kernel at 2, 4 or 8 microphones (the ring's transposition addresses by shifts; BF_DAS_IL_RING=0: never) and the
+// transposition in front of das_f64_pair_kernel otherwise -- never transform microphone 0: they need the reference's unit weight row
+// there (das.cpp:33-38, always true for das on a handle that started cold), a second microphone, and a batch their work queue can
+// hold.  [sample][mic] input without the first two: the microphone-pair kernel das_f64_w64_kernel<1>.  Anything else: the chain.
+DasF64Launch das_f64_decide(int layout, int n_mics, int n_streams, long n_frames, int n_cus, bool mic0_unit, int n_tr, bool tables) {
+    DasF64Launch d{};  // the chain
+    if (n_mics > 8) return d;  // the gain tables fill the LDS
+    const bool ring = switches().das_il_ring != 0 && (n_mics == 2 || n_mics == 4 || n_mics == 8);
+    bool frame_pair = tables && mic0_unit && n_mics >= 2 && n_tr >= 1;
+    if (layout != BF_PLANAR && !ring && ((n_frames * kHop) & 255) != 0) frame_pair = false;  // the transposition moves tiles of 256 samples
+    if (!frame_pair) {
+        if (layout == BF_PLANAR) return d;
+        // frames per run: a multiple of one step of the block (8 frames), about one run per CU
+        const long runs = n_cus > n_streams ? n_cus / n_streams : 1;
+        d.path = DasF64Path::kMicPair;
+        d.run_frames = ((n_frames + runs - 1) / runs + kWaves - 1) / kWaves * kWaves;
+        d.runs_per_stream = (n_frames + d.run_frames - 1) / d.run_frames;
+        return d;
     }
-    if (a.layout == 0) return hipErrorNotSupported;  // (planar input without the pair kernel's tables or with a non-unit row 0: the chain serves it)
-    long fpc, cps;
-    das_f64_w64_runs(a, n_cus, &fpc, &cps);
-    if (cps > 1)
-        for (int st = 0; st < a.n_streams; ++st) {
-            hipError_t e = hipMemset2DAsync(a.y + ((long)st * a.n_frames + fpc) * kHop, (size_t)fpc * kHop * sizeof(float), 0,
-                                            kHop * sizeof(float), (size_t)cps - 1, s);
-            if (e != hipSuccess) return e;
-        }
-    return hipSuccess;
+    if ((long)n_streams * ((n_frames + 1) / 2) >= (1L << 31)) return d;
+    d.plan = das_f64_plan(n_frames, n_streams, n_cus, switches().das_f64_sched);
+    if (d.plan.n_chunks < 1 || d.plan.n_chunks > kSchedMaxChunks) return d;  // (more streams than the table has rows)
+    d.path = layout == BF_PLANAR ? DasF64Path::kFramePair : ring ? DasF64Path::kRing : DasF64Path::kTranspose;
+    d.writes_hist = layout == BF_PLANAR;
+    // scratch: one ring per CU, whatever the plan's grid; the transposition: the batch and the carried hop, planar
+    const size_t hop_elems = (size_t)n_mics * kHop;
+    d.scratch_bytes = sizeof(float) * (layout == BF_PLANAR ? 0 : ring ? n_cus * kRingSlots * hop_elems : n_streams * hop_elems * (n_frames + 1));
+    return d;
 }
 
 // x = [stream][n][M] -> out = [stream][M][n] (n a multiple of 256 samples, M <= 8, both 16-byte aligned)
-hipError_t launch_interleaved_to_planar(const float *x, float *out, long n, int n_mics, int n_streams, hipStream_t s) {
-    if (n_mics < 1 || n_mics > 8 || (n & 255) != 0) return hipErrorNotSupported;
+static hipError_t launch_interleaved_to_planar(const float *x, float *out, long n, int n_mics, int n_streams, hipStream_t s) {
     const long tiles = n / 256;
     BF_LAUNCH(interleaved_to_planar_kernel, dim3((unsigned)(tiles * n_streams)), dim3(256), 0, s, x, out, tiles, n_mics, (long)n_mics * n, n, (long)n_mics * n);
     return hipGetLastError();
 }
 
-hipError_t launch_das_f64_w64(const DasF64Args &a, int n_cus, hipStream_t s) {
-    if (a.n_mics > 8) return hipErrorNotSupported;
-    if (use_pair_kernel(a)) {
-        const DasSchedPlan p = das_f64_plan(a.n_frames, a.n_streams, n_cus, getenv("BF_DAS_F64_SCHED"));
-        DasSched sc;
-        sc.counter = reinterpret_cast<unsigned *>(a.sched_ws);
-        sc.chunks = reinterpret_cast<const int4 *>(reinterpret_cast<char *>(a.sched_ws) + kSchedCounterBytes);
-        sc.n_chunks = p.n_chunks;
-        if (a.layout == 0) {
-            BF_LAUNCH(das_f64_pair_kernel, dim3((unsigned)p.grid), dim3(kBlock), 0, s, a, sc);
-        } else {
-            if (a.ring_bytes < das_f64_ring_bytes(a.n_mics, p.grid)) return hipErrorNotSupported;
-            BF_LAUNCH(das_f64_ring_kernel, dim3((unsigned)p.grid), dim3(kBlock), 0, s, a, sc);
+// Carries out d (not the chain) on `s`.  In front of the kernel: the frame-pair kernels' chunk table, counter and zeroed chunk-boundary hops
+// (one small launch, behind the transposition if there is one); the microphone-pair kernel: the first hop of every run but the first of a
+// stream zeroed (it is completed by atomic adds).  kev0 / kev1 (nullable) are recorded right around the kernel itself.
+hipError_t enqueue_das_f64(DasF64Args a, const DasF64Launch &d, float *scratch, hipStream_t s, hipEvent_t kev0, hipEvent_t kev1, bool *kev_recorded) {
+    hipError_t e = hipSuccess;
+    int4 *const chunks = reinterpret_cast<int4 *>(reinterpret_cast<char *>(a.sched_ws) + kSchedCounterBytes);
+    const DasSched sc{chunks, reinterpret_cast<unsigned *>(a.sched_ws), d.plan.n_chunks};
+    if (d.path == DasF64Path::kMicPair) {
+        for (int st = 0; st < a.n_streams && d.runs_per_stream > 1; ++st) {
+            e = hipMemset2DAsync(a.y + ((long)st * a.n_frames + d.run_frames) * kHop, (size_t)d.run_frames * kHop * sizeof(float), 0, kHop * sizeof(float), (size_t)d.runs_per_stream - 1, s);
+            if (e != hipSuccess) return e;
         }
-        return hipGetLastError();
+    } else {
+        if (d.path == DasF64Path::kRing) {
+            a.ring = scratch; a.ring_bytes = d.scratch_bytes; a.hist_out = nullptr;
+        } else if (d.path == DasF64Path::kTranspose) {
+            const long n = a.n_frames * kHop;
+            float *const hist = scratch + (size_t)a.n_streams * a.n_mics * n;
+            if ((e = launch_interleaved_to_planar(a.x, scratch, n, a.n_mics, a.n_streams, s)) != hipSuccess) return e;
+            if ((e = launch_interleaved_to_planar(a.hist, hist, kHop, a.n_mics, a.n_streams, s)) != hipSuccess) return e;
+            a.x = scratch; a.hist = hist; a.hist_out = nullptr; a.mic_stride = n; a.layout = BF_PLANAR;
+        }
+        BF_LAUNCH(das_f64_sched_kernel, dim3((unsigned)((sc.n_chunks + kSchedPerBlock - 1) / kSchedPerBlock)), dim3(32 * kSchedPerBlock), 0, s, d.plan, chunks, sc.counter, a.y, a.n_frames, a.n_streams);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    long fpc, cps;
-    das_f64_w64_runs(a, n_cus, &fpc, &cps);
-    if (a.layout == 0) return hipErrorNotSupported;  // (planar input without the pair kernel's tables: the chain serves it)
-    BF_LAUNCH(das_f64_w64_kernel<1>, dim3((unsigned)(cps * a.n_streams)), dim3(kBlock), 0, s, a, (int)fpc, (int)cps);
-    return hipGetLastError();
+    if (kev0 && (e = hipEventRecord(kev0, s)) != hipSuccess) return e;
+    if (d.path == DasF64Path::kMicPair)
+        BF_LAUNCH(das_f64_w64_kernel<1>, dim3((unsigned)(d.runs_per_stream * a.n_streams)), dim3(kBlock), 0, s, a, (int)d.run_frames, (int)d.runs_per_stream);
+    else if (d.path == DasF64Path::kRing)
+        BF_LAUNCH(das_f64_ring_kernel, dim3((unsigned)d.plan.grid), dim3(kBlock), 0, s, a, sc);
+    else
+        BF_LAUNCH(das_f64_pair_kernel, dim3((unsigned)d.plan.grid), dim3(kBlock), 0, s, a, sc);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (kev1 && (e = hipEventRecord(kev1, s)) == hipSuccess) *kev_recorded = true;
+    return e;
 }
 
 }  // namespace bf

@@ -4,13 +4,13 @@
 // control-plane only; every per-frame operation runs in the gfx950 kernels.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "device_mem.hpp"
 #include "kernels.hpp"
 #include "pipeline.hpp"
+#include "switches.hpp"
 
 namespace bf {
 namespace {
@@ -113,19 +113,17 @@ int FusedDasEngine::run(const float *x, long F, float *y, f64x2 *spectrum, hipSt
     // (periods 256 / 1024: several 256-thread blocks share a CU -- 13 / 52 KB of LDS each -- and a run costs one recomputed frame)
     // several look directions, planar input, <= 8 microphones, no dump: one set of forward transforms per frame serves up to 16
     // directions (das_fused_dirs_kernel); BF_DAS_SHARED_DIRS = the smallest direction count that takes it (0: never)
-    static const int shared_min = getenv("BF_DAS_SHARED_DIRS") ? atoi(getenv("BF_DAS_SHARED_DIRS")) : 6;
+    const int shared_min = switches().das_shared_dirs;
     const bool shared = !gen_ && layout == BF_PLANAR && M_ <= 8 && !spectrum && shared_min > 0 && D_ >= shared_min;
     // (generic periods: blocks of 13 N bytes of LDS -- 26 N at N = 8192 -- share a CU: 8 at N <= 512, 3 at 2048, 1 from 4096 on)
     const int gen_per_cu = N_ <= 512 ? 8 : N_ <= 1024 ? 6 : N_ <= 2048 ? 3 : 1;
     // period 1024 without a dump: ONE 2048-point transform per frame on a full wavefront, eight frames in flight per block and the tails
     // through an LDS ring (das_fused.hip das_fused_wave2048_kernel); BF_DAS_SPLIT2048=0: the generic kernel (cross-checks)
-    static const int split_env = getenv("BF_DAS_SPLIT2048") ? atoi(getenv("BF_DAS_SPLIT2048")) : 3;
-    const bool wave2048 = gen_ && N_ == 2048 && !spectrum && split_env != 0;
+    const bool wave2048 = gen_ && N_ == 2048 && !spectrum && switches().das_split2048 != 0;
     // periods below 512 without a dump: 1024 / N frames interleaved into one pass of the 1024-point machinery -- the period-512 kernel
     // itself in group mode: one block per run, tails through its LDS ring, HBM sees every hop once; BF_DAS_INTERLEAVE=0: the generic
     // kernel (cross-checks)
-    static const int il_env = getenv("BF_DAS_INTERLEAVE") ? atoi(getenv("BF_DAS_INTERLEAVE")) : 1;
-    const bool small_ring = gen_ && N_ < 1024 && !spectrum && il_env != 0 && d_gains_il_[0].get() != nullptr && d_twiddle_1024_.get() != nullptr;
+    const bool small_ring = gen_ && N_ < 1024 && !spectrum && switches().das_interleave != 0 && d_gains_il_[0].get() != nullptr && d_twiddle_1024_.get() != nullptr;
     const long Rg = small_ring ? 1024 / N_ : 1;
     long runs = (small_ring || wave2048 ? (long)n_cus_ : gen_ ? (long)n_cus_ * gen_per_cu : (long)n_cus_) / (shared ? S_ : So_);
     if (runs < 1) runs = 1;

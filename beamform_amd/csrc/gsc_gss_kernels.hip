@@ -1,9 +1,9 @@
 // gsc_gss_kernels.hip -- the two adaptive nodes: gss (per-bin demixing-matrix recursion) and gsc (per-microphone alignment
 // + sample-serial float32 NLMS).
-#include <cstdlib>
 
 #include "launch_trace.hpp"
 #include "bins_common.hpp"
+#include "switches.hpp"
 
 namespace bf {
 namespace BF_NTAG {
@@ -927,8 +927,7 @@ hipError_t launch_gss(const BinsArgs &a, int n_cus, hipStream_t s) {
     // One lane per problem pays once the lanes fill the chip: 256 streams x 256 frames 3.33 -> 2.10 ms (4 microphones 1.76 -> 1.24), but ONE
     // stream of 65 536 frames 69 -> 145 ms (9 wavefronts; a frame step is 2.2 us in one lane, 1.06 us spread over 8): lane kernel from two
     // wavefronts per CU on.  BF_GSS_GROUP=1 / 0 force the group / the lane kernel (tests, A/B).
-    static const int group_env = getenv("BF_GSS_GROUP") ? atoi(getenv("BF_GSS_GROUP")) : -1;
-    const bool lane_kernel = group_env >= 0 ? group_env == 0 : (long)a.n_streams * ((kNQ + 63) / 64) >= 2L * n_cus;
+    const bool lane_kernel = switches().gss_group >= 0 ? switches().gss_group == 0 : (long)a.n_streams * ((kNQ + 63) / 64) >= 2L * n_cus;
 #define BF_LAUNCH_GSS(MP_, KM_) \
     BF_LAUNCH((gss_kernel<MP_, KM_>), dim3((groups + (256 / MP_) - 1) / (256 / MP_)), dim3(256), 0, s, a)
     if (a.kp1 > 4 || M > 16) {  // beyond the tuned shapes: more interferers (up to 15) or microphones (up to 32)
@@ -962,7 +961,7 @@ hipError_t launch_gsc_nlms(const float *aligned, float *y, float *state, long n_
     // BF_GSC_SERIAL=1: the sums in the reference's tap order, one branch per lane (gsc_nlms_kernel); default: taps over the lanes, the
     // branches dealt out to 8 wavefronts per stream from five branches on, 4 from three, 2 at two, one branch: gsc_nlms_par_kernel
     // (8 microphones, 256 streams x 64 frames: 52.6 / 54.2 / 43.1 / 36.8 ms at 1 / 2 / 4 / 8 wavefronts)
-    static const bool serial = getenv("BF_GSC_SERIAL") && atoi(getenv("BF_GSC_SERIAL")) == 1;
+    const bool serial = switches().gsc_serial;
     const int nw = serial ? 1 : (nb >= 5 ? 8 : nb >= 3 ? 4 : nb >= 2 ? 2 : 1);
     const size_t lds_serial = sizeof(float) * ((size_t)nbr * ((fs + 64 * kp + 8) | 1) + (size_t)nbr * ((64 * kp + 8) | 1) + 2 * fs + 16 +
                                                (size_t)nbr * 64 + 64 + 16 + 64);

@@ -18,13 +18,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "device_mem.hpp"
 #include "fft1024.hpp"
 #include "pipeline_kernels.hpp"
+#include "switches.hpp"
 
 namespace bf {
 
@@ -43,17 +42,17 @@ class BinPipelineImpl : public Engine {
         NQ_ = problems_per_frame(N_);
         YS_ = yh_stride(N_);
         ks_ = kernel_set(N_);
-        MF_ = (c.algo == BF_MCRA) ? 1 : M_;  // the mcra node only transforms channel 0 (mcra.cpp:72-73)
+        MF_ = single_ch_ ? 1 : M_;
         NP_ = (MF_ + 1) / 2;
         S_ = c.n_streams;                                   // input streams
         D_ = c.n_dirs > 1 ? c.n_dirs : 1;                   // look directions per input stream
-        if (c.algo == BF_GSC) D_ = M_;                      // gsc: one aligned output per microphone (do_overlap_bymic)
+        if (time_node_) D_ = M_;                            // gsc: one aligned output per microphone (do_overlap_bymic)
         So_ = S_ * D_;                                      // output streams
         const bool multi = (c.algo == BF_LCMV || c.algo == BF_GSS);
         KP1_ = multi ? c.n_interf + 1 : 1;
-        Phist_ = (c.algo == BF_MVDR || c.algo == BF_LCMV) ? c.past_windows : 0;
+        Phist_ = cov_node_ ? c.past_windows : 0;
         // BF_PRECISION_MIXED: mvdr / lcmv park their spectra as 12-byte z48 elements (pipeline_kernels.hpp); the default keeps complex doubles
-        z48_ = (c.algo == BF_MVDR || c.algo == BF_LCMV) && c.precision == BF_PRECISION_MIXED;
+        z48_ = cov_node_ && c.precision == BF_PRECISION_MIXED;
         zsz_ = z48_ ? sizeof(z48) : sizeof(f64x2);
     }
 
@@ -62,7 +61,7 @@ class BinPipelineImpl : public Engine {
             err_ = "hop (JACK period) must be a power of two from 64 to 4096 frames";
             return BF_ENOSYS;
         }
-        if (M_ > 32 && (cfg_.algo == BF_MVDR || cfg_.algo == BF_LCMV || cfg_.algo == BF_GSS)) {
+        if (M_ > 32 && band_node_) {
             err_ = "mvdr/lcmv/gss kernels are built for up to 32 microphones";
             return BF_ENOSYS;
         }
@@ -70,11 +69,11 @@ class BinPipelineImpl : public Engine {
             err_ = "lcmv/gss kernels are built for up to 15 interferers";
             return BF_ENOSYS;
         }
-        if ((cfg_.algo == BF_MVDR || cfg_.algo == BF_LCMV) && (Phist_ < 1 || Phist_ > 64)) {
+        if (cov_node_ && (Phist_ < 1 || Phist_ > 64)) {
             err_ = "past_windows must be in 1..64";
             return BF_EINVAL;
         }
-        if (cfg_.algo == BF_GSC && (M_ > 16 || cfg_.gsc_filter_size < 1 || cfg_.gsc_filter_size > 256)) {
+        if (time_node_ && (M_ > 16 || cfg_.gsc_filter_size < 1 || cfg_.gsc_filter_size > 256)) {
             err_ = "gsc is built for up to 16 microphones and filter_size 1..256";
             return M_ > 16 ? BF_ENOSYS : BF_EINVAL;
         }
@@ -88,6 +87,21 @@ class BinPipelineImpl : public Engine {
         ENGINE_HIP(d_win_.upload(sqrt_hann(N_)));
         freqs_ = frequency_vector(N_, cfg_.sample_rate);
         ENGINE_HIP(d_freq_.upload(freqs_));
+        skip_lo_ = N_; band_yh_hi_ = NQ_ - 1;
+        if (band_node_) {
+            int klo = N_, khi = 0;  // the lowest and the highest in-band problem past 0 (problem q = bin q for q <= N/2 + 1)
+            for (int q = 1; q < NQ_; ++q) {
+                const double f = std::fabs(freqs_[q]);
+                if (f >= cfg_.freq_min && f <= cfg_.freq_max) { if (q < klo) klo = q; khi = q; }
+            }
+            // the STFT stores everything except, for the band-limited nodes, the bins between the highest in-band bin k and its mirror N-k
+            // (quirk Q1 makes bins 511..513 irregular: only skip when the band ends below them)
+            if (khi < N_ / 2 - 2) { skip_lo_ = khi; skip_hi_ = N_ - khi; }
+            // mvdr / lcmv rows in front of a backward transform: only problem 0 and the band's problems exist (everything else is zero,
+            // mvdr.cpp:103, and is neither written nor read)
+            if (cov_node_ && khi < N_ / 2 - 1 && klo <= khi) { band_yh_lo_ = klo; band_yh_hi_ = khi; }
+            else if (cov_node_ && klo > khi) { band_yh_lo_ = 1; band_yh_hi_ = 0; }  // empty band: only problem 0
+        }
         for (auto &b : d_steer_) ENGINE_HIP(b.alloc(steer_elems()));
         if (das_one_launch_shape()) {
             for (auto &b : d_dasg_w64_) ENGINE_HIP(b.alloc((size_t)4 * 1024));
@@ -104,7 +118,7 @@ class BinPipelineImpl : public Engine {
         }
         if (cfg_.algo == BF_PHASEMPF || cfg_.algo == BF_MCRA) ENGINE_HIP(d_mpf_.alloc(mpf_bytes() / sizeof(double)));
         if (cfg_.algo == BF_PHASEMPF) ENGINE_HIP(d_smooth_.alloc(smooth_bytes() / sizeof(double)));
-        if (cfg_.algo == BF_GSC) ENGINE_HIP(d_nlms_.alloc(nlms_bytes() / sizeof(float)));
+        if (time_node_) ENGINE_HIP(d_nlms_.alloc(nlms_bytes() / sizeof(float)));
         return BF_OK;
     }
 
@@ -206,7 +220,10 @@ class BinPipelineImpl : public Engine {
     int set_state(const void *host) override { return copy_state((char *)host, false); }
 
    private:
-    // das through this pipeline on the tuned shape: eligible for the one-launch kernels of das_f64_w64.hip (run() decides per batch)
+    static constexpr int kDeclined = 1;  // (every BF_* code is <= 0)
+    int run_das_one_launch(const float *x, long F, float *y, hipStream_t stream, int layout, long mic_stride, const RunSnapshot &snap);
+    int run_chain(const float *x, long F, float *y, f64x2 *spectrum, hipStream_t stream, int layout, long mic_stride, const RunSnapshot &snap);
+    // das through this pipeline on the tuned shape: eligible for the one-launch kernels of das_f64_w64.hip (das_f64_decide per batch)
     bool das_one_launch_shape() const { return cfg_.algo == BF_DAS && N_ == 1024 && M_ <= 8 && D_ == 1; }
     size_t steer_elems() const { return (size_t)D_ * N_ * M_ * kMaxCols; }
     size_t hist_elems() const { return (size_t)S_ * M_ * H_; }  // the carried hop of every input stream
@@ -219,7 +236,7 @@ class BinPipelineImpl : public Engine {
     }
     size_t smooth_bytes() const { return cfg_.algo == BF_PHASEMPF ? (size_t)So_ * 64 * sizeof(double) : 0; }
     size_t nlms_bytes() const {
-        return cfg_.algo == BF_GSC ? (size_t)S_ * (2 * (M_ - 1) + 1) * cfg_.gsc_filter_size * sizeof(float) : 0;
+        return time_node_ ? (size_t)S_ * (2 * (M_ - 1) + 1) * cfg_.gsc_filter_size * sizeof(float) : 0;
     }
 
     int copy_state(char *p, bool to_host) {
@@ -241,6 +258,15 @@ class BinPipelineImpl : public Engine {
 
     bf_config cfg_;
     int n_cus_, M_, MF_, NP_, S_, D_, So_, KP1_, Phist_;
+    // what kind of node this is
+    const bool cov_node_ = cfg_.algo == BF_MVDR || cfg_.algo == BF_LCMV;  // covariance over a frame history; halved (or z48) spectra, band-limited rows
+    const bool band_node_ = cov_node_ || cfg_.algo == BF_GSS;             // only the bins inside [freq_min, freq_max] are processed
+    const bool time_node_ = cfg_.algo == BF_GSC;                          // the adaptive stage runs on samples: no single y_fft
+    const bool single_ch_ = cfg_.algo == BF_MCRA;                         // only channel 0 is transformed (mcra.cpp:72-73)
+    const bool post_amp_ = band_node_;                                    // out_amp is applied behind the backward transform
+    const bool yraw_target_ = cfg_.algo == BF_PHASEMPF || time_node_;     // the backward transform feeds the smoother / the NLMS stage through d_yraw_
+    int skip_lo_, skip_hi_ = 0;        // StftArgs::skip_lo / skip_hi (init(); N_, 0 = store everything)
+    int band_yh_lo_ = 0, band_yh_hi_;  // BinsArgs::yh_lo / yh_hi of a batch with band-limited rows (init(); every problem unless mvdr / lcmv)
     bool z48_ = false;
     size_t zsz_ = sizeof(f64x2);  // bytes per packed-spectrum element
     int H_ = 512, N_ = 1024, NQ_ = 514, YS_ = 516;  // hop, FFT size, problems per frame, row stride of Yh
@@ -276,87 +302,61 @@ class BinPipelineImpl : public Engine {
     DeviceBuffer<float> d_frames_;  // N != 1024: windowed frames between the generic ISTFT and its overlap-add
 };
 
+// das at the reference's precision on the tuned shape, no spectrum dump: ONE launch, spectra never leave the CU (das_f64_w64.hip: das_f64_decide
+// picks the kernel -- the frame-pair kernel das_f64_pair_kernel on planar input, the headline -- or declines); BF_FUSED_BINS=0 keeps the chain
+// (cross-checks).  BF_OK: handled; kDeclined: run_chain serves the batch; an error otherwise.
+int BinPipelineImpl::run_das_one_launch(const float *x, long F, float *y, hipStream_t stream, int layout, long mic_stride, const RunSnapshot &snap) {
+    if (!das_one_launch_shape() || switches().fused_bins != 1 || snap.das_gains_w64 == nullptr) return kDeclined;
+    const DasF64Launch d = das_f64_decide(layout, M_, S_, F, n_cus_, snap.das_mic0_unit, snap.das_slots.n_tr,
+                                          snap.das_gains_mic != nullptr && d_das_sched_.get() != nullptr);
+    if (d.path == DasF64Path::kChain) return kDeclined;
+    ENGINE_HIP(d_planar_.reserve((d.scratch_bytes + sizeof(float) - 1) / sizeof(float)));
+    float *const hist = d_hist2_[hist_cur_].get();
+    DasF64Args da;
+    da.x = x; da.hist = hist; da.hist_out = d_hist2_[hist_cur_ ^ 1].get(); da.y = y;
+    da.tail_in = d_tail_[tail_cur_].get(); da.tail_out = d_tail_[tail_cur_ ^ 1].get();
+    da.win = d_win_.get(); da.n_frames = F; da.mic_stride = mic_stride;
+    da.stream_stride_x = (long)M_ * F * H_; da.n_streams = S_; da.n_mics = M_; da.run_len = 1;
+    da.layout = layout;
+    da.gains = snap.das_gains_w64; da.gains_mic = snap.das_gains_mic; da.tw = d_tw_w64_.get();
+    da.mic0_unit = snap.das_mic0_unit ? 1 : 0;
+    da.n_tr = snap.das_slots.n_tr; da.extra_mic = snap.das_slots.extra_mic;
+    for (int k = 0; k < 8; ++k) da.slot_mic[k] = snap.das_slots.slot_mic[k];
+    da.sched_ws = d_das_sched_.get(); da.sched_ws_bytes = d_das_sched_.get() ? das_f64_sched_ws_bytes() : 0;
+    ENGINE_HIP(enqueue_das_f64(da, d, d_planar_.get(), stream, kev0, kev1, &kev_recorded));
+    if (d.writes_hist)
+        hist_cur_ ^= 1;  // das_f64_pair_kernel stored the last hop into the other buffer
+    else  // the carried hop stays in the handle's layout
+        ENGINE_HIP(carry_last_hop(hist, x, F, H_, M_, S_, layout, mic_stride, (long)F * H_ * M_, stream));
+    tail_cur_ ^= 1;
+    return BF_OK;
+}
+
 int BinPipelineImpl::run(const float *x, long F, float *y, f64x2 *spectrum, hipStream_t stream, int layout, long mic_stride,
                          const RunSnapshot &snap) {
+    const int rc = spectrum ? kDeclined : run_das_one_launch(x, F, y, stream, layout, mic_stride, snap);
+    return rc == kDeclined ? run_chain(x, F, y, spectrum, stream, layout, mic_stride, snap) : rc;
+}
+
+int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum, hipStream_t stream, int layout, long mic_stride,
+                               const RunSnapshot &snap) {
     // One pass over the whole batch: cutting it into Infinity-Cache-sized frame tiles was measured (3.9-12 ms for mvdr instead of
     // 3.0: per-tile launches underfill the chip and the per-bin kernels lose their parallelism over time) -- DESIGN.md 3.2
     float *const hist = d_hist2_[hist_cur_].get();
-    // das at the reference's precision on the tuned shape, no spectrum dump: ONE launch, spectra never leave the CU (das_f64_w64.hip
-    // launch_das_f64_w64: the frame-pair kernel das_f64_pair_kernel on planar input); BF_FUSED_BINS=0 keeps the chain below (cross-checks)
-    static const int fuse_env0 = getenv("BF_FUSED_BINS") ? atoi(getenv("BF_FUSED_BINS")) : 1;
-    if (das_one_launch_shape() && fuse_env0 == 1 && spectrum == nullptr && snap.das_gains_w64 != nullptr) {
-        DasF64Args da;
-        da.x = x; da.hist = hist; da.hist_out = d_hist2_[hist_cur_ ^ 1].get(); da.y = y;
-        da.tail_in = d_tail_[tail_cur_].get(); da.tail_out = d_tail_[tail_cur_ ^ 1].get();
-        da.win = d_win_.get(); da.n_frames = F; da.mic_stride = mic_stride;
-        da.stream_stride_x = (long)M_ * F * H_; da.n_streams = S_; da.n_mics = M_; da.run_len = 1;
-        da.layout = layout;
-        // [sample][mic] input reaches the frame-pair kernel, with its microphone-0 and identical-row savings, in one of two ways; the
-        // carried hop stays in the handle's layout either way (BF_DAS_IL_RING=0: always the second way)
-        static const int il_ring_env = getenv("BF_DAS_IL_RING") ? atoi(getenv("BF_DAS_IL_RING")) : 1;
-        const size_t ring_bytes = il_ring_env ? das_f64_ring_bytes(M_, n_cus_) : 0;
-        if (layout == BF_INTERLEAVED && snap.das_mic0_unit && M_ >= 2 && snap.das_slots.n_tr >= 1 && d_das_sched_.get() != nullptr) {
-            if (ring_bytes > 0) {
-                // 2, 4 or 8 microphones: the ring kernel (das_f64_ring_kernel) transposes hop by hop into its blocks' rings: 160 MB of scratch
-                // instead of a planar copy of the batch, and the transposition's memory traffic runs under the other wavefronts' transforms
-                ENGINE_HIP(d_planar_.reserve((ring_bytes + sizeof(float) - 1) / sizeof(float)));
-                da.ring = d_planar_.get(); da.ring_bytes = ring_bytes; da.hist_out = nullptr;
-            } else {
-                // every other microphone count: the batch and the carried hop are transposed into a planar scratch
-                // (interleaved_to_planar_kernel) and the frame-pair kernel reads that
-                const size_t nb = (size_t)S_ * M_ * F * H_;
-                ENGINE_HIP(d_planar_.reserve(nb + hist_elems()));
-                float *const planar = d_planar_.get();
-                hipError_t te = launch_interleaved_to_planar(x, planar, F * H_, M_, S_, stream);
-                if (te == hipSuccess) te = launch_interleaved_to_planar(hist, planar + nb, H_, M_, S_, stream);
-                if (te == hipSuccess) {
-                    da.x = planar; da.hist = planar + nb; da.hist_out = nullptr; da.mic_stride = F * H_; da.layout = BF_PLANAR;
-                } else if (te != hipErrorNotSupported) {
-                    ENGINE_HIP(te);
-                } else {
-                    (void)hipGetLastError();
-                }
-            }
-        }
-        da.gains = snap.das_gains_w64; da.gains_mic = snap.das_gains_mic; da.tw = d_tw_w64_.get();
-        da.mic0_unit = snap.das_mic0_unit ? 1 : 0;
-        da.n_tr = snap.das_slots.n_tr; da.extra_mic = snap.das_slots.extra_mic;
-        for (int k = 0; k < 8; ++k) da.slot_mic[k] = snap.das_slots.slot_mic[k];
-        da.sched_ws = d_das_sched_.get(); da.sched_ws_bytes = d_das_sched_.get() ? das_f64_sched_ws_bytes() : 0;
-        hipError_t de = prepare_das_f64_w64(da, n_cus_, stream);
-        if (de == hipSuccess) {
-            if (kev0) ENGINE_HIP(hipEventRecord(kev0, stream));
-            de = launch_das_f64_w64(da, n_cus_, stream);
-            if (kev1 && de == hipSuccess) {
-                ENGINE_HIP(hipEventRecord(kev1, stream));
-                kev_recorded = true;
-            }
-        }
-        if (de == hipSuccess) {
-            if (das_f64_writes_hist(da))
-                hist_cur_ ^= 1;  // das_f64_pair_kernel stored the last hop into the other buffer
-            else
-                ENGINE_HIP(carry_last_hop(hist, x, F, H_, M_, S_, layout, mic_stride, (long)F * H_ * M_, stream));
-            tail_cur_ ^= 1;
-            return BF_OK;
-        }
-        if (de != hipErrorNotSupported) ENGINE_HIP(de);
-        (void)hipGetLastError();
-    }
     const long FT = Phist_ + F;  // frames in the Z workspace per stream
     // nodes without a frame history: STFT and per-bin stage in one launch, spectra never leave the CU (launch_stft_bins_fused;
     // BF_FUSED_BINS=0 selects the two-kernel chain) -- then the Z workspace (64 KB per frame at 8 microphones) is not needed at all
-    const bool try_fused = fuse_env0 != 0 && Phist_ == 0 && N_ <= 2048 && M_ <= 8 && MF_ == M_ && D_ == 1 &&  // (N = 128 / 256 / 512: stft_bins_small_kernel, 2048: stft_bins_split_kernel)
+    const bool try_fused = switches().fused_bins != 0 && Phist_ == 0 && N_ <= 2048 && M_ <= 8 && MF_ == M_ && D_ == 1 &&  // (N = 128 / 256 / 512: stft_bins_small_kernel, 2048: stft_bins_split_kernel)
                            (cfg_.algo == BF_DAS || cfg_.algo == BF_PHASE || cfg_.algo == BF_PHASEMPF);
     if (!try_fused)
         // (+ 512 frames of slack behind the last stream: mvdr_fast_kernel's lanes of a short last tile prefetch up to one tile
         // length past the end of their stream and never use what they fetched)
-        ENGINE_HIP(d_Z_.reserve(((size_t)S_ * FT + ((cfg_.algo == BF_MVDR || cfg_.algo == BF_LCMV) ? 512 : 0)) * NP_ * N_ * zsz_));
+        ENGINE_HIP(d_Z_.reserve(((size_t)S_ * FT + (cov_node_ ? 512 : 0)) * NP_ * N_ * zsz_));
     else  // the fused kernel parks the unpacked spectra of two bins per frame here (stream x frame x 2 x 8 microphones)
         ENGINE_HIP(d_Z_.reserve((size_t)S_ * F * 2 * 8 * sizeof(f64x2)));
     // phasempf keeps |out_int|^2 (one double per problem) behind the spectrum rows
     ENGINE_HIP(d_Yh_.reserve((size_t)So_ * F * YS_ * (sizeof(f64x2) + (cfg_.algo == BF_PHASEMPF ? sizeof(double) : 0))));
-    if (cfg_.algo == BF_PHASEMPF || cfg_.algo == BF_GSC) ENGINE_HIP(d_yraw_.reserve((size_t)So_ * F * H_));
+    if (yraw_target_) ENGINE_HIP(d_yraw_.reserve((size_t)So_ * F * H_));
     if (N_ != 1024) ENGINE_HIP(d_frames_.reserve((size_t)So_ * F * N_));
     f64x2 *Z = (f64x2 *)d_Z_.get();
     f64x2 *const Yh = (f64x2 *)d_Yh_.get();
@@ -371,20 +371,10 @@ int BinPipelineImpl::run(const float *x, long F, float *y, f64x2 *spectrum, hipS
     sa.x = x; sa.hist = hist; sa.Z = Z; sa.tw = d_tw_.get(); sa.win = d_win_.get();
     sa.n_frames = F; sa.frames_ws = FT; sa.frame_off = Phist_; sa.mic_stride = mic_stride;
     sa.stream_stride_x = (long)M_ * F * H_; sa.n_streams = S_; sa.n_mics = M_; sa.n_fft_mics = MF_; sa.layout = layout;
-    sa.skip_lo = N_; sa.skip_hi = 0;  // store everything ...
+    sa.skip_lo = skip_lo_; sa.skip_hi = skip_hi_;
     sa.z48 = z48_ ? 1 : 0; sa.run_len = 1; sa.tw_w64 = d_tw_w64_.get();
-    sa.halve = (cfg_.algo == BF_MVDR || cfg_.algo == BF_LCMV) ? 1 : 0;
-    if (cfg_.algo == BF_MVDR || cfg_.algo == BF_LCMV || cfg_.algo == BF_GSS) {
-        // ... except, for the band-limited nodes, the bins between the highest in-band bin k and its mirror N-k
-        // (quirk Q1 makes bins 511..513 irregular: only skip when the band ends below them)
-        int kmax = 0;
-        for (int k = 0; k <= N_ / 2 + 1; ++k) {
-            const double f = std::fabs(freqs_[k]);
-            if (f >= cfg_.freq_min && f <= cfg_.freq_max) kmax = k;
-        }
-        if (kmax < N_ / 2 - 2) { sa.skip_lo = kmax; sa.skip_hi = N_ - kmax; }
-    }
-    if (cfg_.algo == BF_GSC && spectrum) {  // time-domain node: there is no single y_fft; the dump reads as zeros
+    sa.halve = cov_node_ ? 1 : 0;
+    if (time_node_ && spectrum) {  // time-domain node: there is no single y_fft; the dump reads as zeros
         ENGINE_HIP(hipMemsetAsync(spectrum, 0, (size_t)S_ * F * N_ * sizeof(f64x2), stream));
         spectrum = nullptr;
     }
@@ -399,8 +389,7 @@ int BinPipelineImpl::run(const float *x, long F, float *y, f64x2 *spectrum, hipS
     // the per-bin stage can emit f32x2 rows: mvdr / lcmv (band-limited rows: half the row traffic, no zero-fill), das / phase through the
     // bin pipeline, phasempf.  gsc (its sample-serial NLMS branches on the aligned signals), a spectrum dump and the other FFT sizes: always
     // in double.
-    const bool cov_node = cfg_.algo == BF_MVDR || cfg_.algo == BF_LCMV;
-    const bool want32 = cfg_.precision == BF_PRECISION_MIXED && cfg_.algo != BF_GSC && N_ == 1024 && spectrum == nullptr;
+    const bool want32 = cfg_.precision == BF_PRECISION_MIXED && !time_node_ && N_ == 1024 && spectrum == nullptr;
     // mvdr / lcmv hand the fp32 transform f32x2 rows holding only problem 0 and the in-band problems (everything else is zero,
     // mvdr.cpp:103); das / phase through the bin pipeline: f32x2 rows too (every problem written)
     const bool pointwise32 = (cfg_.algo == BF_DAS || cfg_.algo == BF_PHASE) && want32;
@@ -408,18 +397,10 @@ int BinPipelineImpl::run(const float *x, long F, float *y, f64x2 *spectrum, hipS
     // phasempf: the recursion's y_fft has no reader but the fp32 backward transform either: f32x2 rows in the |out_int|^2 slots
     ba.mpf32 = (cfg_.algo == BF_PHASEMPF && want32) ? 1 : 0;
     const bool istft32 = ba.yh32 != 0 || ba.mpf32 != 0;
-    ba.yh_lo = 0; ba.yh_hi = NQ_ - 1;
-    // mvdr / lcmv rows in front of a backward transform (no dump): only problem 0 and the band's problems exist (everything else is zero,
-    // mvdr.cpp:103, and is neither written nor read): f32x2 rows into istft32_kernel, f64x2 rows into istft_w64_kernel<true>
-    if (cov_node && spectrum == nullptr && N_ == 1024) {
-        int klo = N_, khi = 0;
-        for (int q = 1; q < NQ_; ++q) {
-            const double f = std::fabs(freqs_[q]);  // problem q = bin q for q <= N/2 + 1
-            if (f >= cfg_.freq_min && f <= cfg_.freq_max) { if (q < klo) klo = q; if (q > khi) khi = q; }
-        }
-        if (khi < N_ / 2 - 1 && klo <= khi) { ba.yh_lo = klo; ba.yh_hi = khi; }
-        else if (klo > khi) { ba.yh_lo = 1; ba.yh_hi = 0; }  // empty band: only problem 0
-    }
+    // mvdr / lcmv rows in front of a backward transform (no dump): band-limited (init()): f32x2 rows into istft32_kernel, f64x2 rows into
+    // istft_w64_kernel<true>
+    const bool band_rows = cov_node_ && spectrum == nullptr && N_ == 1024;
+    ba.yh_lo = band_rows ? band_yh_lo_ : 0; ba.yh_hi = band_rows ? band_yh_hi_ : NQ_ - 1;
     // phasempf with at least a quarter as many streams as CUs, default precision, no dump: the recursion kernel runs the backward transform too
     // (mask_kernels.hip mpf_rec_istft_kernel: a block per stream, the y_fft rows stay in LDS); with fewer streams its blocks leave the chip empty
     const bool rec_istft = cfg_.algo == BF_PHASEMPF && N_ == 1024 && spectrum == nullptr && !ba.mpf32 && (long)So_ * 4 >= n_cus_;
@@ -455,7 +436,7 @@ int BinPipelineImpl::run(const float *x, long F, float *y, f64x2 *spectrum, hipS
                                   hipMemcpyDeviceToDevice, stream));
 
     IstftArgs ia;
-    ia.Yh = Yh; ia.y = (cfg_.algo == BF_PHASEMPF || cfg_.algo == BF_GSC) ? d_yraw_.get() : y; ia.tail_in = d_tail_[tail_cur_].get();
+    ia.Yh = Yh; ia.y = yraw_target_ ? d_yraw_.get() : y; ia.tail_in = d_tail_[tail_cur_].get();
     ia.tail_out = d_tail_[tail_cur_ ^ 1].get(); ia.tw = d_tw_.get(); ia.win = d_win_.get(); ia.n_frames = F; ia.n_streams = So_;
     ia.tw32 = istft32 ? d_tw32_.get() : nullptr;
     ia.tw_w64 = d_tw_w64_.get();
@@ -465,14 +446,14 @@ int BinPipelineImpl::run(const float *x, long F, float *y, f64x2 *spectrum, hipS
         ia.yh32 = 1; ia.yh_lo = 0; ia.yh_hi = NQ_ - 1;
     }
     ia.frames = d_frames_.get();
-    ia.post_amp = (cfg_.algo == BF_MVDR || cfg_.algo == BF_LCMV || cfg_.algo == BF_GSS) ? cfg_.out_amp : 1.0;
-    ia.use_post_amp = (cfg_.algo == BF_MVDR || cfg_.algo == BF_LCMV || cfg_.algo == BF_GSS) ? 1 : 0;
+    ia.post_amp = post_amp_ ? cfg_.out_amp : 1.0;
+    ia.use_post_amp = post_amp_ ? 1 : 0;
     if (!rec_istft) ENGINE_HIP(ks_->istft(ia, n_cus_, stream));
     tail_cur_ ^= 1;
 
     if (cfg_.algo == BF_PHASEMPF)
         ENGINE_HIP(ks_->smooth(d_yraw_.get(), y, d_smooth_.get(), F, So_, cfg_.smooth_size, stream));
-    if (cfg_.algo == BF_GSC)
+    if (time_node_)
         ENGINE_HIP(ks_->gsc_nlms(d_yraw_.get(), y, d_nlms_.get(), F * H_, S_, M_, cfg_, stream));
     return BF_OK;
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/bfcore.h"
+#include "das_f64_plan.hpp"
 #include "geometry.hpp"
 
 namespace bf {
@@ -80,8 +81,7 @@ struct BinsArgs {
     f64x2 *gssW;         // [stream][N][kp1][n_mics]
     double *mpf;         // [stream][kMpfVecs*N + 8] (the mcra node uses vectors 0..3 and the two scalars)
     unsigned long long gss_reset_mask;  // bit d: look direction d re-initialises W = C^H (gss.cpp:90-93) in this batch
-    int z48;             // mvdr / lcmv: Z holds z48 elements (the default); 0 = full f64x2 spectra (BF_Z48=0: parity debugging on
-                         // ill-conditioned scenes; only the group-per-problem kernel reads them)
+    int z48;             // mvdr / lcmv with BF_PRECISION_MIXED: Z holds z48 elements; 0 (the default) = full f64x2 spectra
     // phasempf with many streams (N = 1024, default precision, no dump): the recursion kernel runs the backward transform too
     // (mpf_rec_istft_kernel: one block per output stream; y_fft rows never reach HBM).  Set by the pipeline, which then skips its ISTFT launch.
     int rec_istft = 0;
@@ -122,7 +122,7 @@ struct DasF64Args {
     const double *win;
     long n_frames, mic_stride, stream_stride_x;
     int n_streams, n_mics, run_len;
-    int layout = 0;        // bf_layout of x and hist; 1 (interleaved) only with launch_das_f64_w64
+    int layout = 0;        // bf_layout of x and hist; 1 (interleaved): das_f64_ring_kernel, das_f64_w64_kernel<1>
     float *hist_out = nullptr;         // das_f64_pair_kernel: receives the last hop of the batch (the ring-buffer carry), layout as hist
     const f64x2 *gains_mic = nullptr;  // das_mic_gains_w64_f64: per-microphone Hermitian gains of the frame-pair kernel (planar input)
     // das_f64_pair_kernel: the microphones that get a forward transform, in the order the kernel walks them (slot k -> microphone slot_mic[k],
@@ -133,20 +133,32 @@ struct DasF64Args {
     int mic0_unit = 0;                 // the weight row of microphone 0 is identically 1 (das.cpp:33-38): das_f64_pair_kernel adds h x_0 / M in the time domain
     void *sched_ws = nullptr;          // das_f64_pair_kernel: device workspace of its work queue (das_f64_sched_ws_bytes())
     size_t sched_ws_bytes = 0;
-    float *ring = nullptr;             // das_f64_pair_kernel on [sample][mic] input: the blocks' hop rings (das_f64_ring_bytes())
+    float *ring = nullptr;             // das_f64_pair_kernel on [sample][mic] input: the blocks' hop rings (DasF64Launch::scratch_bytes)
     size_t ring_bytes = 0;
 };
 
-// the same node on one full wavefront per frame (das_f64_w64.hip; N = 1024 only): `gains` = das_pair_gains_w64_f64, `tw` =
-// twiddle_table_w64_rot.  prepare_ zeroes the run-boundary hops of y on `s` (they are completed by atomic adds) and must precede the
-// launch.  hipErrorNotSupported above 8 microphones.
-hipError_t prepare_das_f64_w64(const DasF64Args &a, int n_cus, hipStream_t s);
-hipError_t launch_das_f64_w64(const DasF64Args &a, int n_cus, hipStream_t s);
+// What one batch of that node launches (das_f64_w64.hip): das_f64_decide settles it ONCE from the batch's shape, on the host and without
+// touching the device; enqueue_das_f64 carries it out.
+enum class DasF64Path {
+    kChain,      // none of the kernels here: the STFT -> per-bin -> ISTFT chain serves the batch
+    kFramePair,  // das_f64_pair_kernel on planar input
+    kRing,       // das_f64_ring_kernel: [sample][mic] input with 2, 4 or 8 microphones, transposed hop by hop into the blocks' rings
+    kTranspose,  // interleaved_to_planar_kernel (batch, carried hop) + das_f64_pair_kernel: [sample][mic] input otherwise
+    kMicPair,    // das_f64_w64_kernel<1>: [sample][mic] input with one microphone or a non-unit weight row 0
+};
+struct DasF64Launch {
+    DasF64Path path;
+    DasSchedPlan plan;                  // frame-pair kernels: the chunk plan
+    long run_frames, runs_per_stream;   // microphone-pair kernel: its static runs
+    size_t scratch_bytes;               // device scratch of enqueue_das_f64: the blocks' hop rings (kRing), the planar batch + carried hop (kTranspose)
+    bool writes_hist;                   // the kernel stores the carried hop into DasF64Args::hist_out itself (no copy behind it)
+};
+// mic0_unit, n_tr: as in DasF64Args; tables: the frame-pair kernels' gains (gains_mic) and work-queue workspace (sched_ws) exist
+DasF64Launch das_f64_decide(int layout, int n_mics, int n_streams, long n_frames, int n_cus, bool mic0_unit, int n_tr, bool tables);
+// `a` as for planar input with hist_out set; `scratch` = d.scratch_bytes of device memory; d.path != kChain.  kev0 / kev1 (nullable)
+// are recorded on `s` right around the kernel, *kev_recorded is raised once the second record has succeeded (pipeline.hpp Engine::kev0)
+hipError_t enqueue_das_f64(DasF64Args a, const DasF64Launch &d, float *scratch, hipStream_t s, hipEvent_t kev0, hipEvent_t kev1, bool *kev_recorded);
 size_t das_f64_sched_ws_bytes();
-size_t das_f64_ring_bytes(int n_mics, int n_cus);  // 0: this microphone count has no ring kernel (the transposition in front of the planar kernel serves it)
-// [stream][n][M] -> [stream][M][n] in front of the frame-pair kernel ([sample][mic] handles); n a multiple of 256, M <= 8
-hipError_t launch_interleaved_to_planar(const float *x, float *out, long n, int n_mics, int n_streams, hipStream_t s);
-bool das_f64_writes_hist(const DasF64Args &a);  // the kernel launch_das_f64_w64 picks stores a.hist_out itself (no copy behind it)
 
 #ifdef BF_NFFT
 namespace BF_NTAG {

@@ -1,9 +1,9 @@
 // stft_istft.hip -- the two ends of the fp64 bin pipeline: STFT (window + forward FFTs, packed pair spectra to HBM), ISTFT
 // (Hermitian extension, backward FFT, synthesis window, overlap-add), the full-spectrum dump and phasempf's output smoothing.
-#include <cstdlib>
 
 #include "launch_trace.hpp"
 #include "bins_common.hpp"
+#include "switches.hpp"
 #include "fft_small.hpp"
 #if BF_NFFT == 1024
 #include "w64_f64_dev.hpp"
@@ -1231,8 +1231,7 @@ hipError_t launch_istft(const IstftArgs &a, int n_cus, hipStream_t s) {
 hipError_t launch_stft(const StftArgs &a, int n_cus, hipStream_t s) {
 #if BF_NFFT == 128 || BF_NFFT == 256 || BF_NFFT == 512
     // the in-register kernel (BF_STFT_SMALL=0: the generic one, for A/B runs)
-    static const bool small_on = !(getenv("BF_STFT_SMALL") && atoi(getenv("BF_STFT_SMALL")) == 0);
-    if (small_on) {
+    if (switches().stft_small) {
         constexpr int halves = 8;
         const long np = (a.n_fft_mics + 1) / 2;
         StftArgs b = a;
@@ -1257,8 +1256,7 @@ hipError_t launch_stft(const StftArgs &a, int n_cus, hipStream_t s) {
 #endif
 #if BF_NFFT == 2048
     // one 2048-point transform per full wavefront (BF_STFT_SPLIT=0: the generic kernel, for cross-checks)
-    static const bool split_on = !(getenv("BF_STFT_SPLIT") && atoi(getenv("BF_STFT_SPLIT")) == 0);
-    if (split_on) {
+    if (switches().stft_split) {
         constexpr int waves = 4;
         const long np = (a.n_fft_mics + 1) / 2;
         StftArgs b = a;
@@ -1293,8 +1291,7 @@ hipError_t launch_stft(const StftArgs &a, int n_cus, hipStream_t s) {
 hipError_t launch_istft(const IstftArgs &a, int n_cus, hipStream_t s) {
 #if BF_NFFT == 128 || BF_NFFT == 256 || BF_NFFT == 512
     // backward transform, window and overlap-add in registers (BF_STFT_SMALL=0: the generic pair of kernels, for A/B runs)
-    static const bool small_on = !(getenv("BF_STFT_SMALL") && atoi(getenv("BF_STFT_SMALL")) == 0);
-    if (small_on && !a.yh32) {
+    if (switches().stft_small && !a.yh32) {
         constexpr int halves = 8;
         const long slots = (long)n_cus * halves;
         long L = ((long)a.n_streams * a.n_frames + slots - 1) / slots;
@@ -1308,8 +1305,7 @@ hipError_t launch_istft(const IstftArgs &a, int n_cus, hipStream_t s) {
 #endif
 #if BF_NFFT == 2048
     // one FFT-1024 per frame, window and overlap-add in registers (BF_STFT_SPLIT=0: the generic pair of kernels, for A/B runs)
-    static const bool split_on = !(getenv("BF_STFT_SPLIT") && atoi(getenv("BF_STFT_SPLIT")) == 0);
-    if (split_on && !a.yh32) {
+    if (switches().stft_split && !a.yh32) {
         constexpr int halves = 8;
         const long slots = (long)n_cus * halves;
         long L = ((long)a.n_streams * a.n_frames + slots - 1) / slots;

@@ -47,12 +47,14 @@ const KernelSet *kernel_set_n1024() { return &g_stub_set; }
 const KernelSet *kernel_set_n2048() { return &g_stub_set; }
 const KernelSet *kernel_set_n4096() { return &g_stub_set; }
 const KernelSet *kernel_set_n8192() { return &g_stub_set; }
-hipError_t prepare_das_f64_w64(const DasF64Args &, int, hipStream_t) { return hipSuccess; }
-hipError_t launch_das_f64_w64(const DasF64Args &, int, hipStream_t) { return hipSuccess; }
-hipError_t launch_interleaved_to_planar(const float *, float *, long, int, int, hipStream_t) { return hipSuccess; }
-bool das_f64_writes_hist(const DasF64Args &) { return false; }
+// das in double in one launch: a path without scratch whose kernel leaves the carried hop to the pipeline, and an enqueue that succeeds
+DasF64Launch das_f64_decide(int, int, int, long, int, bool, int, bool) {
+    DasF64Launch d{};
+    d.path = DasF64Path::kMicPair;
+    return d;
+}
+hipError_t enqueue_das_f64(DasF64Args, const DasF64Launch &, float *, hipStream_t, hipEvent_t, hipEvent_t, bool *) { return hipSuccess; }
 size_t das_f64_sched_ws_bytes() { return 256; }
-size_t das_f64_ring_bytes(int, int) { return 0; }
 
 hipError_t prepare_das_fused(const DasFusedArgs &, hipStream_t) { return hipSuccess; }
 hipError_t launch_das_fused(const DasFusedArgs &a, hipStream_t) {
