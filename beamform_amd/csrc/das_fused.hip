@@ -1594,41 +1594,33 @@ __global__ void das_hermitian_dump_kernel(const f32x2 *s, f64x2 *out, long total
     out[idx] = f64x2{0.5 * kNfft * ((double)u.x + (double)v.x), 0.5 * kNfft * ((double)u.y - (double)v.y)};
 }
 
+// kRegs / kIl4 / kIl8 of a decision; das_fused_plan.hpp holds the table of das_fused_kernel<LAYOUT, NPL, UNR, R>.  (Group mode, the
+// 16-byte-load kernels, R = 1: the order in which the instantiations enter the code object, kept as it was.)
 template <int LAYOUT>
-void launch_layout(const DasFusedArgs &a, unsigned blocks, hipStream_t stream) {
-    const int np = (a.n_mics + 1) / 2;
-    // planar input: pair loop unrolled for the exact pair count, next pair's loads issued from inside the gain loop
-    if (a.group > 1) {  // frame groups (periods below 512): launch_das_fused checked the shape
-#define BF_DAS_GRP(NPL_, UNR_)                                                                                                              \
-    do {                                                                                                                                    \
-        if (a.group == 2) BF_LAUNCH((das_fused_kernel<LAYOUT, NPL_, UNR_, 2>), dim3(blocks), dim3(kBlock), 0, stream, a);                   \
-        else if (a.group == 4) BF_LAUNCH((das_fused_kernel<LAYOUT, NPL_, UNR_, 4>), dim3(blocks), dim3(kBlock), 0, stream, a);              \
-        else BF_LAUNCH((das_fused_kernel<LAYOUT, NPL_, UNR_, 8>), dim3(blocks), dim3(kBlock), 0, stream, a);                                \
-    } while (0)
-        if constexpr (LAYOUT == 0) {  // planar: the unrolled pair loop up to 8 microphones
-            if (np == 1) BF_DAS_GRP(1, 1); else if (np == 2) BF_DAS_GRP(2, 2); else if (np == 3) BF_DAS_GRP(4, 3); else if (np == 4) BF_DAS_GRP(4, 4);
-            else BF_DAS_GRP(0, 0);    // > 8 microphones: gains from L2
-        } else {
-            if (np == 1) BF_DAS_GRP(1, 0); else if (np == 2) BF_DAS_GRP(2, 0); else if (np <= 4) BF_DAS_GRP(4, 0); else BF_DAS_GRP(0, 0);
-        }
-#undef BF_DAS_GRP
-        return;
+void launch_regs(const DasFusedArgs &a, const DasFusedLaunch &d, hipStream_t stream) {
+    const dim3 grid(d.blocks), block(kBlock);
+    constexpr bool kUnr = LAYOUT == 0;  // planar input only: the pair loop unrolled for the exact pair count
+#define BF_DAS_VARIANT(GO_)                                 \
+    switch (d.npl) {                                        \
+        case 1: GO_(1, (kUnr ? 1 : 0)); break;              \
+        case 2: GO_(2, (kUnr ? 2 : 0)); break;              \
+        case 4: if (d.unr == 3) { GO_(4, (kUnr ? 3 : 0)); } else { GO_(4, (kUnr ? 4 : 0)); } break; \
+        default: GO_(0, 0); /* > 8 microphones: gains from L2 */ \
     }
-    if (LAYOUT == 1 && (a.n_mics == 4 || a.n_mics == 8)) {  // 16-byte loads: two pairs per sample access
-        if (a.n_mics == 4)  // one 16-byte load per sample = the whole sample: two frames per wavefront
-            BF_LAUNCH((das_fused_il_kernel<2, 1>), dim3(blocks), dim3(kBlock), 0, stream, a);
-        else                // 8 microphones: one frame per wavefront, each half-wavefront loads its 16 bytes of the 32-byte sample
-            BF_LAUNCH(das_fused_il8_kernel, dim3(blocks), dim3(kBlock), 0, stream, a);
-        return;
+#define BF_DAS_GROUP(NPL_, UNR_)                                                                                         \
+    switch (d.group) {                                                                                                  \
+        case 2: BF_LAUNCH((das_fused_kernel<LAYOUT, NPL_, UNR_, 2>), grid, block, 0, stream, a); break;                 \
+        case 4: BF_LAUNCH((das_fused_kernel<LAYOUT, NPL_, UNR_, 4>), grid, block, 0, stream, a); break;                 \
+        default: BF_LAUNCH((das_fused_kernel<LAYOUT, NPL_, UNR_, 8>), grid, block, 0, stream, a);                       \
     }
-    constexpr bool unr = LAYOUT == 0;
-#define BF_DAS_GO(NPL_, UNR_) BF_LAUNCH((das_fused_kernel<LAYOUT, NPL_, (unr ? UNR_ : 0)>), dim3(blocks), dim3(kBlock), 0, stream, a)
-    if (np <= 1) BF_DAS_GO(1, 1);
-    else if (np <= 2) BF_DAS_GO(2, 2);
-    else if (np == 3) BF_DAS_GO(4, 3);
-    else if (np == 4) BF_DAS_GO(4, 4);
-    else BF_DAS_GO(0, 0);  // > 8 mics: the gain tables no longer fit beside the transpose buffers and the tail ring
-#undef BF_DAS_GO
+#define BF_DAS_ONE(NPL_, UNR_) BF_LAUNCH((das_fused_kernel<LAYOUT, NPL_, UNR_>), grid, block, 0, stream, a)
+    if (d.group > 1) BF_DAS_VARIANT(BF_DAS_GROUP)
+    else if (d.kernel == DasFusedKernel::kIl4) BF_LAUNCH((das_fused_il_kernel<2, 1>), grid, block, 0, stream, a);
+    else if (d.kernel == DasFusedKernel::kIl8) BF_LAUNCH(das_fused_il8_kernel, grid, block, 0, stream, a);
+    else BF_DAS_VARIANT(BF_DAS_ONE)
+#undef BF_DAS_ONE
+#undef BF_DAS_GROUP
+#undef BF_DAS_VARIANT
 }
 
 // Sum of squares of every output stream (double accumulation): bf_stream_rms.
@@ -1647,104 +1639,85 @@ __global__ __launch_bounds__(256) void stream_sumsq_kernel(const float *y, long 
     if (threadIdx.x == 0) atomicAdd(sumsq + blockIdx.y, part[0] + part[1] + part[2] + part[3]);
 }
 
+#ifdef BF_DAS_STAMPS
+// the stamps of the launch of `blocks` blocks just enqueued on `stream`
+void read_out_stamps(unsigned blocks, hipStream_t stream) {
+    static int n_launch = 0;  // sums accumulate over back-to-back launches; read out only when asked (no sync otherwise)
+    ++n_launch;
+    if (getenv("BF_DAS_STAMPS_PRINT")) {
+        (void)hipStreamSynchronize(stream);
+        static unsigned long long hb[kStampBlocks][20];
+        (void)hipMemcpyFromSymbol(hb, HIP_SYMBOL(g_stamps), sizeof(hb));
+        unsigned long long h[18] = {0};
+        const int nb = (int)blocks < kStampBlocks ? (int)blocks : kStampBlocks;
+        for (int b = 0; b < nb; ++b)
+            for (int i = 0; i < 18; ++i) h[i] += hb[b][i];
+        void *sym = nullptr;
+        (void)hipGetSymbolAddress(&sym, HIP_SYMBOL(g_stamps));
+        (void)hipMemset(sym, 0, sizeof(hb));
+        fprintf(stderr, "stamps over %d launches (cycles per wave-iteration, wave 0 of each block):", n_launch);
+        for (int i = 0; i < 14; ++i) fprintf(stderr, " [%d]=%.0f", i, (double)h[i] / (double)(h[15] ? h[15] : 1));
+        {
+            unsigned long long r0min = ~0ull, r1max = 0, dmin = ~0ull, dmax = 0, dsum = 0, r0max = 0, r1min = ~0ull;
+            for (int b = 0; b < nb; ++b) {
+                const unsigned long long d = hb[b][19] - hb[b][18];
+                r0min = hb[b][18] < r0min ? hb[b][18] : r0min; r0max = hb[b][18] > r0max ? hb[b][18] : r0max;
+                r1max = hb[b][19] > r1max ? hb[b][19] : r1max; r1min = hb[b][19] < r1min ? hb[b][19] : r1min;
+                dmin = d < dmin ? d : dmin; dmax = d > dmax ? d : dmax; dsum += d;
+            }
+            fprintf(stderr, "\n  last launch, loop of wave 0 per block (us): min %.1f mean %.1f max %.1f; first start -> last end %.1f; start spread %.1f, end spread %.1f",
+                    dmin * 0.01, dsum * 0.01 / nb, dmax * 0.01, (r1max - r0min) * 0.01, (r0max - r0min) * 0.01, (r1max - r1min) * 0.01);
+        }
+        if (getenv("BF_DAS_STAMPS_BLOCKS")) {
+            fprintf(stderr, "\n  per-block loop us:");
+            for (int b = 0; b < nb; ++b) fprintf(stderr, " %.1f", (hb[b][19] - hb[b][18]) * 0.01);
+        }
+        const double nw = (double)n_launch * nb;
+        fprintf(stderr, "  clock %.3f GHz  loop %.0f cycles/wave  kernel %.0f cycles/wave\n",
+                h[16] ? 0.1 * (double)h[14] / (double)h[16] : 0.0, (double)h[14] / nw, (double)h[17] / nw);
+        n_launch = 0;
+    }
+}
+#endif
+
 }  // namespace
 
-// Runs are multiples of 16 frames; the first hop of every run but the first of a stream is completed by
-// atomic adds and must be zero beforehand (prepare_das_fused).
-hipError_t prepare_das_fused(const DasFusedArgs &a, hipStream_t stream) {
-    if (a.chunks_per_stream > 1) {
-        const int H = a.group > 1 ? kHop / a.group : kHop;  // frame groups: the hop of one frame of the period
+hipError_t enqueue_das_fused(const DasFusedArgs &a, const DasFusedLaunch &d, int n_fft, hipStream_t stream, hipEvent_t kev0, hipEvent_t kev1, bool *kev_recorded) {
+    hipError_t e = hipSuccess;
+    if (d.zero_run_heads) {  // atomic adds complete the first hop of every run but a stream's first
+        const int hop = n_fft / 2;
         for (int s = 0; s < a.n_streams; ++s) {
-            hipError_t e = hipMemset2DAsync(a.y + ((long)s * a.n_frames + a.frames_per_chunk) * H,
-                                            (size_t)a.frames_per_chunk * H * sizeof(float), 0, H * sizeof(float),
-                                            (size_t)a.chunks_per_stream - 1, stream);
+            e = hipMemset2DAsync(a.y + ((long)s * a.n_frames + d.frames_per_chunk) * hop, (size_t)d.frames_per_chunk * hop * sizeof(float), 0,
+                                 hop * sizeof(float), (size_t)d.chunks_per_stream - 1, stream);
             if (e != hipSuccess) return e;
         }
     }
-    return hipSuccess;
-}
-
-// a.group = 2 / 4 / 8 (periods 256 / 128 / 64 as groups of interleaved frames): either layout, any microphone count,
-// no spectrum dump; a.frames_per_chunk a multiple of 16 * group
-bool das_fused_takes_groups(const DasFusedArgs &a) {
-    return a.sdump == nullptr && (a.group == 2 || a.group == 4 || a.group == 8);
-}
-
-hipError_t launch_das_fused(const DasFusedArgs &a, hipStream_t stream) {
-    if (a.group > 1 && !(das_fused_takes_groups(a) && a.frames_per_chunk % (16 * a.group) == 0)) return hipErrorInvalidValue;
-    const unsigned blocks = (unsigned)((long)a.chunks_per_stream * a.n_streams);
-    if (a.layout == 0) launch_layout<0>(a, blocks, stream);
-    else launch_layout<1>(a, blocks, stream);
+    // (a launch that fails between the two records must not leave a half-recorded pair in the session: *kev_recorded stays down and the
+    // caller hands the pair back)
+    if (kev0 && (e = hipEventRecord(kev0, stream)) != hipSuccess) return e;
+    const dim3 grid(d.blocks), block(kBlock);
+    switch (d.kernel) {
+        case DasFusedKernel::kRegs: case DasFusedKernel::kIl4: case DasFusedKernel::kIl8:
+            if (a.layout == 0) launch_regs<0>(a, d, stream);
+            else launch_regs<1>(a, d, stream);
+            break;
+        case DasFusedKernel::kWave2048:
+            if (a.layout == 0) BF_LAUNCH(das_fused_wave2048_kernel<0>, grid, block, 0, stream, a);
+            else BF_LAUNCH(das_fused_wave2048_kernel<1>, grid, block, 0, stream, a);
+            break;
+        case DasFusedKernel::kDirs:
+            for (int d0 = 0; d0 < a.n_dirs; d0 += 16) BF_LAUNCH(das_fused_dirs_kernel, grid, block, 0, stream, a, d0, a.n_dirs - d0 < 16 ? a.n_dirs - d0 : 16);
+            break;
+        case DasFusedKernel::kGen:
+            if ((e = enqueue_das_fused_gen(a, n_fft, d.blocks, stream)) != hipSuccess) return e;
+            break;
+    }
 #ifdef BF_DAS_STAMPS
-    {
-        static int n_launch = 0;  // sums accumulate over back-to-back launches; read out only when asked (no sync otherwise)
-        ++n_launch;
-        if (getenv("BF_DAS_STAMPS_PRINT")) {
-            (void)hipStreamSynchronize(stream);
-            static unsigned long long hb[kStampBlocks][20];
-            (void)hipMemcpyFromSymbol(hb, HIP_SYMBOL(g_stamps), sizeof(hb));
-            unsigned long long h[18] = {0};
-            const int nb = (int)(a.chunks_per_stream * a.n_streams) < kStampBlocks ? (int)(a.chunks_per_stream * a.n_streams) : kStampBlocks;
-            for (int b = 0; b < nb; ++b)
-                for (int i = 0; i < 18; ++i) h[i] += hb[b][i];
-            void *sym = nullptr;
-            (void)hipGetSymbolAddress(&sym, HIP_SYMBOL(g_stamps));
-            (void)hipMemset(sym, 0, sizeof(hb));
-            fprintf(stderr, "stamps over %d launches (cycles per wave-iteration, wave 0 of each block):", n_launch);
-            for (int i = 0; i < 14; ++i) fprintf(stderr, " [%d]=%.0f", i, (double)h[i] / (double)(h[15] ? h[15] : 1));
-            {
-                unsigned long long r0min = ~0ull, r1max = 0, dmin = ~0ull, dmax = 0, dsum = 0, r0max = 0, r1min = ~0ull;
-                for (int b = 0; b < nb; ++b) {
-                    const unsigned long long d = hb[b][19] - hb[b][18];
-                    r0min = hb[b][18] < r0min ? hb[b][18] : r0min; r0max = hb[b][18] > r0max ? hb[b][18] : r0max;
-                    r1max = hb[b][19] > r1max ? hb[b][19] : r1max; r1min = hb[b][19] < r1min ? hb[b][19] : r1min;
-                    dmin = d < dmin ? d : dmin; dmax = d > dmax ? d : dmax; dsum += d;
-                }
-                fprintf(stderr, "\n  last launch, loop of wave 0 per block (us): min %.1f mean %.1f max %.1f; first start -> last end %.1f; start spread %.1f, end spread %.1f",
-                        dmin * 0.01, dsum * 0.01 / nb, dmax * 0.01, (r1max - r0min) * 0.01, (r0max - r0min) * 0.01, (r1max - r1min) * 0.01);
-            }
-            if (getenv("BF_DAS_STAMPS_BLOCKS")) {
-                fprintf(stderr, "\n  per-block loop us:");
-                for (int b = 0; b < nb; ++b) fprintf(stderr, " %.1f", (hb[b][19] - hb[b][18]) * 0.01);
-            }
-            const double nw = (double)n_launch * nb;
-            fprintf(stderr, "  clock %.3f GHz  loop %.0f cycles/wave  kernel %.0f cycles/wave\n",
-                    h[16] ? 0.1 * (double)h[14] / (double)h[16] : 0.0, (double)h[14] / nw, (double)h[17] / nw);
-            n_launch = 0;
-        }
-    }
+    if (d.kernel == DasFusedKernel::kRegs || d.kernel == DasFusedKernel::kIl4 || d.kernel == DasFusedKernel::kIl8) read_out_stamps(d.blocks, stream);
 #endif
-    return hipGetLastError();
-}
-
-// The 1024-frame period, a wavefront per frame (das_fused_wave2048_kernel): a.gains = das_pair_gains_natural tables [dir][pair][2048],
-// a.twiddle = exp(-2 pi i m / 2048) for m < 1024, a.window = 2048 floats, a.zeros >= 1024 floats; a.frames_per_chunk a multiple of 8; the first
-// hop of every run but the first of a stream must be zero beforehand (prepare_das_fused_wave2048); no spectrum dump
-hipError_t prepare_das_fused_wave2048(const DasFusedArgs &a, hipStream_t stream) {
-    if (a.chunks_per_stream > 1) {
-        for (int s = 0; s < a.n_streams; ++s) {
-            hipError_t e = hipMemset2DAsync(a.y + ((long)s * a.n_frames + a.frames_per_chunk) * kHop2, (size_t)a.frames_per_chunk * kHop2 * sizeof(float), 0,
-                                            kHop2 * sizeof(float), (size_t)a.chunks_per_stream - 1, stream);
-            if (e != hipSuccess) return e;
-        }
-    }
-    return hipSuccess;
-}
-hipError_t launch_das_fused_wave2048(const DasFusedArgs &a, hipStream_t stream) {
-    if (a.sdump != nullptr || a.frames_per_chunk % kWaves2 != 0) return hipErrorInvalidValue;
-    const unsigned blocks = (unsigned)((long)a.chunks_per_stream * a.n_streams);
-    if (a.layout == 0) BF_LAUNCH(das_fused_wave2048_kernel<0>, dim3(blocks), dim3(kBlock), 0, stream, a);
-    else BF_LAUNCH(das_fused_wave2048_kernel<1>, dim3(blocks), dim3(kBlock), 0, stream, a);
-    return hipGetLastError();
-}
-
-// Look directions dir0 .. dir0 + n_here - 1 (n_here <= 16) of every input stream from one set of forward transforms; planar
-// input, <= 8 microphones, no spectrum dump.  chunks_per_stream counts runs per INPUT stream here.
-hipError_t launch_das_fused_dirs(const DasFusedArgs &a, int dir0, int n_here, hipStream_t stream) {
-    if (a.layout != 0 || a.n_mics > 8 || n_here < 1 || n_here > 16 || a.sdump != nullptr) return hipErrorInvalidValue;
-    const unsigned blocks = (unsigned)((long)a.chunks_per_stream * (a.n_streams / a.n_dirs));
-    BF_LAUNCH(das_fused_dirs_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, dir0, n_here);
-    return hipGetLastError();
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (kev1 && (e = hipEventRecord(kev1, stream)) == hipSuccess) *kev_recorded = true;
+    return e;
 }
 
 hipError_t launch_stream_rms(const float *y, long n_samples, int n_streams, double *sumsq, hipStream_t stream) {

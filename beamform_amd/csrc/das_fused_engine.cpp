@@ -1,7 +1,8 @@
-// das_fused_engine.cpp -- the engine of BF_DAS with BF_DAS_FUSED_F32: tables, carried state and launch sizing of the fused fp32 das
-// kernels.  The 512-frame period has the register-resident kernels (32 x 32 in-register FFT-1024, das_fused.hip); every other
-// period (64 ... 4096 frames) one fused kernel on LDS-staged transforms (das_fused_gen.hip).  Host work here is start-up /
-// control-plane only; every per-frame operation runs in the gfx950 kernels.
+// das_fused_engine.cpp -- the engine of BF_DAS with BF_DAS_FUSED_F32: tables and carried state of the fused fp32 das kernels; which
+// kernel serves a batch and in which runs: das_fused_plan.hpp.  The 512-frame period has the register-resident kernels (32 x 32
+// in-register FFT-1024, das_fused.hip), which also take the shorter periods as groups of interleaved frames; the longer ones the
+// kernels on LDS-staged transforms (das_fused_gen.hip) or, at 1024 frames, a wavefront per 2048-point frame.  Host work here is
+// start-up / control-plane only; every per-frame operation runs in the gfx950 kernels.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -25,7 +26,7 @@ class FusedDasEngine : public Engine {
         for (auto &g : d_gains_) ENGINE_HIP(g.alloc(np * N_ * D_));
         // period 512: inter-pass twiddles of the 32 x 32 factorisation; others: W^m, m < N/2, + the per-pass radix-4 blocks (geometry.hpp)
         ENGINE_HIP(d_twiddle_.upload(gen_ ? stockham_twiddles<f32x2>(N_) : twiddle_table_32x32<f32x2>()));
-        if (N_ < 1024) {
+        if (N_ < 1024) {  // the tables of group mode (das_fused_plan.hpp: group_tables)
             ENGINE_HIP(d_twiddle_1024_.upload(twiddle_table_32x32<f32x2>()));
             for (auto &g : d_gains_il_) ENGINE_HIP(g.alloc(np * 1024 * D_));
         }
@@ -48,7 +49,7 @@ class FusedDasEngine : public Engine {
 
     int upload_steering(const std::vector<SteeringSet> &dirs, hipStream_t s) override {
         const int np = (M_ + 1) / 2;
-        const bool il = d_gains_il_[0].get() != nullptr;
+        const bool il = N_ < 1024;  // as init() allocated them
         std::vector<f32x2> g, gil;  // [dir][pair][N], [dir][pair][1024]
         for (const SteeringSet &st : dirs) {
             if (il) {
@@ -108,30 +109,8 @@ class FusedDasEngine : public Engine {
 };
 
 int FusedDasEngine::run(const float *x, long F, float *y, f64x2 *spectrum, hipStream_t s, int layout, long mic_stride, const RunSnapshot &) {
-    // one block (16 half-wavefronts) per run of consecutive frames; runs are multiples of 16 frames and
-    // there are about as many runs as CUs
-    // (periods 256 / 1024: several 256-thread blocks share a CU -- 13 / 52 KB of LDS each -- and a run costs one recomputed frame)
-    // several look directions, planar input, <= 8 microphones, no dump: one set of forward transforms per frame serves up to 16
-    // directions (das_fused_dirs_kernel); BF_DAS_SHARED_DIRS = the smallest direction count that takes it (0: never)
-    const int shared_min = switches().das_shared_dirs;
-    const bool shared = !gen_ && layout == BF_PLANAR && M_ <= 8 && !spectrum && shared_min > 0 && D_ >= shared_min;
-    // (generic periods: blocks of 13 N bytes of LDS -- 26 N at N = 8192 -- share a CU: 8 at N <= 512, 3 at 2048, 1 from 4096 on)
-    const int gen_per_cu = N_ <= 512 ? 8 : N_ <= 1024 ? 6 : N_ <= 2048 ? 3 : 1;
-    // period 1024 without a dump: ONE 2048-point transform per frame on a full wavefront, eight frames in flight per block and the tails
-    // through an LDS ring (das_fused.hip das_fused_wave2048_kernel); BF_DAS_SPLIT2048=0: the generic kernel (cross-checks)
-    const bool wave2048 = gen_ && N_ == 2048 && !spectrum && switches().das_split2048 != 0;
-    // periods below 512 without a dump: 1024 / N frames interleaved into one pass of the 1024-point machinery -- the period-512 kernel
-    // itself in group mode: one block per run, tails through its LDS ring, HBM sees every hop once; BF_DAS_INTERLEAVE=0: the generic
-    // kernel (cross-checks)
-    const bool small_ring = gen_ && N_ < 1024 && !spectrum && switches().das_interleave != 0 && d_gains_il_[0].get() != nullptr && d_twiddle_1024_.get() != nullptr;
-    const long Rg = small_ring ? 1024 / N_ : 1;
-    long runs = (small_ring || wave2048 ? (long)n_cus_ : gen_ ? (long)n_cus_ * gen_per_cu : (long)n_cus_) / (shared ? S_ : So_);
-    if (runs < 1) runs = 1;
-    long fpc = (F + runs - 1) / runs;
-    if (!gen_) fpc = ((fpc + 15) / 16) * 16;
-    if (wave2048) fpc = ((fpc + 7) / 8) * 8;                                   // eight frames per pass of a block
-    else if (small_ring) fpc = ((fpc + 16 * Rg - 1) / (16 * Rg)) * (16 * Rg);  // sixteen groups per pass of a block
-    const long cps = (F + fpc - 1) / fpc;
+    const Switches &sw = switches();
+    const DasFusedLaunch d = das_fused_decide(H_, layout, M_, S_, D_, spectrum != nullptr, F, n_cus_, sw.das_interleave, sw.das_split2048, sw.das_shared_dirs);
 
     if (spectrum) ENGINE_HIP(d_sdump_.reserve((size_t)So_ * F * N_));
 
@@ -142,8 +121,8 @@ int FusedDasEngine::run(const float *x, long F, float *y, f64x2 *spectrum, hipSt
     a.y = y;
     a.tail_in = d_tail_[tail_cur_].get();
     a.tail_out = d_tail_[tail_cur_ ^ 1].get();
-    a.gains = small_ring ? d_gains_il_[gains_cur_].get() : d_gains_[gains_cur_].get();
-    a.twiddle = small_ring ? d_twiddle_1024_.get() : d_twiddle_.get();
+    a.gains = d.group_tables ? d_gains_il_[gains_cur_].get() : d_gains_[gains_cur_].get();
+    a.twiddle = d.group_tables ? d_twiddle_1024_.get() : d_twiddle_.get();
     a.window = d_window_.get();
     a.zeros = d_zeros_.get();
     a.sdump = spectrum ? d_sdump_.get() : nullptr;
@@ -153,27 +132,11 @@ int FusedDasEngine::run(const float *x, long F, float *y, f64x2 *spectrum, hipSt
     a.n_streams = So_;
     a.n_dirs = D_;
     a.n_mics = M_;
-    a.frames_per_chunk = (int)fpc;
-    a.chunks_per_stream = (int)cps;
+    a.frames_per_chunk = d.frames_per_chunk;
+    a.chunks_per_stream = d.chunks_per_stream;
     a.layout = layout;
-    a.group = small_ring ? (int)Rg : 1;
-    if (wave2048) ENGINE_HIP(prepare_das_fused_wave2048(a, s));
-    else if (!gen_ || small_ring) ENGINE_HIP(prepare_das_fused(a, s));
-    // (a launch that fails between the two records must not leave a half-recorded pair in the session: kev_recorded stays down and the
-    // caller hands the pair back)
-    if (kev0) ENGINE_HIP(hipEventRecord(kev0, s));
-    if (shared) {
-        for (int d0 = 0; d0 < D_; d0 += 16) ENGINE_HIP(launch_das_fused_dirs(a, d0, D_ - d0 < 16 ? D_ - d0 : 16, s));
-    } else {
-        ENGINE_HIP(wave2048     ? launch_das_fused_wave2048(a, s)
-                   : small_ring ? launch_das_fused(a, s)
-                   : gen_       ? launch_das_fused_gen(a, N_, s)
-                                : launch_das_fused(a, s));
-    }
-    if (kev1) {
-        ENGINE_HIP(hipEventRecord(kev1, s));
-        kev_recorded = true;
-    }
+    a.group = d.group;
+    ENGINE_HIP(enqueue_das_fused(a, d, N_, s, kev0, kev1, &kev_recorded));
     tail_cur_ ^= 1;
 
     if (spectrum)

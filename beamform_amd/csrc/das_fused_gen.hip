@@ -197,8 +197,7 @@ __global__ void das_hermitian_dump_gen_kernel(const f32x2 *s, f64x2 *out, long t
 
 }  // namespace
 
-hipError_t launch_das_fused_gen(const DasFusedArgs &a, int n_fft, hipStream_t stream) {
-    const unsigned blocks = (unsigned)((long)a.chunks_per_stream * a.n_streams);
+hipError_t enqueue_das_fused_gen(const DasFusedArgs &a, int n_fft, unsigned blocks, hipStream_t stream) {
 #define BF_GEN(N_) case N_: BF_LAUNCH(das_fused_gen_kernel<N_>, dim3(blocks), dim3(gen_block(N_)), 0, stream, a); break
     switch (n_fft) {
         BF_GEN(128); BF_GEN(256); BF_GEN(512); BF_GEN(2048); BF_GEN(4096); BF_GEN(8192);

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "das_fused_plan.hpp"
 #include "geometry.hpp"
 
 namespace bf {
@@ -29,29 +30,27 @@ struct DasFusedArgs {
     int frames_per_chunk;
     int chunks_per_stream;
     int layout;            // bf_layout
-    int group = 1;         // launch_das_fused only: R = 1024 / n_fft frames of a period below 512 interleaved per unit of work (1: period 512)
+    int group = 1;         // das_fused_kernel only: R = 1024 / n_fft frames of a period below 512 interleaved per unit of work (1: period 512)
 };
-hipError_t prepare_das_fused(const DasFusedArgs &a, hipStream_t stream);  // zero the atomically-completed hops
-hipError_t launch_das_fused(const DasFusedArgs &a, hipStream_t stream);
-bool das_fused_takes_groups(const DasFusedArgs &a);
-// the 1024-frame period on a full wavefront per 2048-point frame (das_fused.hip das_fused_wave2048_kernel): the generic kernel's tables
-hipError_t prepare_das_fused_wave2048(const DasFusedArgs &a, hipStream_t stream);
-hipError_t launch_das_fused_wave2048(const DasFusedArgs &a, hipStream_t stream);  // whether launch_das_fused runs this shape with a.group > 1
-// look directions dir0 .. dir0 + n_here - 1 (n_here <= 16) from ONE set of forward transforms per frame (planar, <= 8 microphones, no
-// spectrum dump); a.chunks_per_stream / frames_per_chunk describe the runs of an INPUT stream; output equal to launch_das_fused's within float rounding, not bit for bit
-// (the window products are fused differently: a beam's low-order bits may change when n_dirs crosses BF_DAS_SHARED_DIRS)
-hipError_t launch_das_fused_dirs(const DasFusedArgs &a, int dir0, int n_here, hipStream_t stream);
+// Carries out d = das_fused_decide(...) (das_fused_plan.hpp) on `stream`; a.frames_per_chunk / chunks_per_stream / group are d's, a.gains /
+// a.twiddle / a.window the tables of d's kernel:
+//   kRegs, kIl4, kIl8, kDirs  das_pair_gains tables [dir][pair][1024] and twiddle_table_32x32, as above; in group mode (d.group_tables) the
+//                             das_pair_gains_interleaved tables of the period, same shape
+//   kWave2048, kGen           das_pair_gains_natural tables [dir][pair][n_fft], stockham_twiddles(n_fft), window n_fft floats; kGen's sdump
+//                             rows are n_fft long, natural order
+// The zeroing d asks for comes first, then kev0 / kev1 (nullable) are recorded right around the kernel launches (kDirs: one launch per 16
+// look directions); *kev_recorded is raised once the second record has succeeded (pipeline.hpp Engine::kev0).
+hipError_t enqueue_das_fused(const DasFusedArgs &a, const DasFusedLaunch &d, int n_fft, hipStream_t stream, hipEvent_t kev0, hipEvent_t kev1, bool *kev_recorded);
+// enqueue_das_fused's kGen launch (das_fused_gen.hip holds those kernels)
+hipError_t enqueue_das_fused_gen(const DasFusedArgs &a, int n_fft, unsigned blocks, hipStream_t stream);
 
-// S dump -> Hermitian part of the reference's y_fft as double2 [frames][1024]
 // per-stream root-mean-square of y [n_streams][n_samples] -> rms[n_streams] (double); `sumsq` = n_streams doubles of scratch
 hipError_t launch_stream_rms(const float *y, long n_samples, int n_streams, double *sumsq, hipStream_t stream);
 
+// S dump -> Hermitian part of the reference's y_fft as double2 [frames][1024]
 hipError_t launch_das_hermitian_dump(const f32x2 *sdump, f64x2 *out, long n_frames_total, hipStream_t stream);
 
-// JACK periods 256 / 1024 (FFT 512 / 2048), das_fused_gen.hip: same argument block; `gains` = das_pair_gains_natural tables [dir][pair][n_fft],
-// `twiddle` = exp(-2 pi i m / n_fft) for m < n_fft / 2, `window` n_fft floats; frames_per_chunk is free (no multiple of 16), no
-// prepare step (a run that does not start the stream recomputes its previous frame); sdump rows are n_fft long, natural order
-hipError_t launch_das_fused_gen(const DasFusedArgs &a, int n_fft, hipStream_t stream);
+// the generic periods' S dump (rows n_fft long, natural order) -> double2 [frames][n_fft]
 hipError_t launch_das_hermitian_dump_gen(const f32x2 *sdump, f64x2 *out, long n_frames_total, int n_fft, hipStream_t stream);
 
 }  // namespace bf

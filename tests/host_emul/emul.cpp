@@ -599,3 +599,13 @@ extern "C" int emul_das_plan(long n_frames, int n_streams, int n_cus, const char
     for (int k = 0; k < p.n_chunks; ++k) bf::das_f64_chunk(p, n_frames, n_streams, k, &stream[k], &t0[k], &n[k]);
     return p.n_chunks;
 }
+
+// ---- which fused fp32 das kernel serves a batch and in which runs (csrc/das_fused_plan.hpp) ---------------------------------------------------
+#include "../../beamform_amd/csrc/das_fused_plan.hpp"
+// out[9] = kernel (DasFusedKernel's order), npl, unr, group, frames_per_chunk, chunks_per_stream, blocks, zero_run_heads, group_tables
+extern "C" void emul_das_fused_plan(int hop, int layout, int n_mics, int n_streams, int n_dirs, int dump, long n_frames, int n_cus,
+                                    int das_interleave, int das_split2048, int das_shared_dirs, long *out) {
+    const bf::DasFusedLaunch d = bf::das_fused_decide(hop, layout, n_mics, n_streams, n_dirs, dump != 0, n_frames, n_cus, das_interleave, das_split2048, das_shared_dirs);
+    const long v[9] = {(long)d.kernel, d.npl, d.unr, d.group, d.frames_per_chunk, d.chunks_per_stream, (long)d.blocks, d.zero_run_heads, d.group_tables};
+    memcpy(out, v, sizeof(v));
+}

@@ -305,3 +305,113 @@ def test_bench_tables_in_the_docs_match_their_records():
     import sys
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_tables.py"), "--check"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
+
+
+# ---- the launch decision of fused fp32 das (csrc/das_fused_plan.hpp through emul_das_fused_plan) ---------------------------------------
+K_REGS, K_IL4, K_IL8, K_WAVE2048, K_DIRS, K_GEN = range(6)   # DasFusedKernel's order
+DEFAULT_SWITCHES = dict(das_interleave=1, das_split2048=3, das_shared_dirs=6)   # switches.hpp
+
+
+def _das_fused_plan(lib, hop, layout, mics, streams, dirs, dump, F, cus, das_interleave=1, das_split2048=3, das_shared_dirs=6):
+    out = (C.c_long * 9)()
+    lib.emul_das_fused_plan.restype = None
+    lib.emul_das_fused_plan.argtypes = [C.c_int] * 6 + [C.c_long] + [C.c_int] * 4 + [C.c_void_p]
+    lib.emul_das_fused_plan(hop, layout, mics, streams, dirs, int(dump), F, cus, das_interleave, das_split2048, das_shared_dirs, out)
+    keys = ("kernel", "npl", "unr", "group", "fpc", "cps", "blocks", "zero_run_heads", "group_tables")
+    return dict(zip(keys, out))
+
+
+def test_das_fused_decision_names_the_kernels_of_the_dispatch_table(emul_lib):
+    """Every das (fp32) row of docs/DISPATCH.md (traced on a GPU: 96 frames, one stream, 256 CUs, default switches): the host decision
+    must name the row's first kernel -- for das_fused_kernel<L, NPL, UNR, R> the same four integers, for das_fused_gen_kernel<N> the
+    transform the engine asks for (N = 2 * period), for das_fused_wave2048_kernel<L> the layout."""
+    rows = []
+    for line in open(os.path.join(ROOT, "docs", "DISPATCH.md")):
+        c = [f.strip() for f in line.strip().strip("|").split("|")]
+        if len(c) == 7 and c[0] == "das (fp32)":
+            rows.append(c)
+    assert len(rows) >= 14   # seven periods, and at period 512 seven more layouts / microphone counts / direction counts / a dump
+    for _, period, layout, mics, dirs, dump, kernels in rows:
+        hop, lay, M, D = int(period), {"planar": 0, "[sample][mic]": 1}[layout], int(mics), int(dirs)
+        d = _das_fused_plan(emul_lib, hop, lay, M, 1, D, dump == "yes", 96, 256)
+        first = kernels.strip("`").split(" + ")[0]
+        name, _, targs = first.partition("<")
+        targs = [int(t) for t in targs.rstrip(">").split(",")] if targs else []
+        if name == "das_fused_kernel":
+            assert (d["kernel"], [lay, d["npl"], d["unr"], d["group"]]) == (K_REGS, targs), (first, d)
+        elif name == "das_fused_gen_kernel":
+            assert (d["kernel"], [2 * hop]) == (K_GEN, targs), (first, d)
+        elif name == "das_fused_wave2048_kernel":
+            assert (d["kernel"], [lay]) == (K_WAVE2048, targs), (first, d)
+        else:
+            assert d["kernel"] == {"das_fused_il_kernel": K_IL4, "das_fused_il8_kernel": K_IL8, "das_fused_dirs_kernel": K_DIRS}[name], (first, d)
+
+
+def test_das_fused_decision_covers_every_stream_within_the_run_budget(emul_lib):
+    """A few hundred random shapes at the default switches: the runs tile a stream (no empty run, none past the end), stay within the
+    budget of blocks in flight (n_cus; the LDS-staged kernels 8 / 6 / 3 / 1 per CU at N <= 512 / 1024 / 2048 / above), keep the chosen
+    kernel's multiple of frames, and every kernel appears only for the shapes it is built for.  A spectrum dump never selects the
+    wavefront-per-frame kernel, the shared-transform kernel or group mode, none of which writes one.  (The two 16-byte-load kernels
+    of [sample][mic] input do write it and take such batches today -- tests/test_fused_bins_gpu.py runs one -- so for them the
+    dump must NOT change the choice.)"""
+    rng = np.random.default_rng(20)
+    fixed_F = [1, 2, 15, 16, 17, 96, 97, 65_536, 1_000_003]
+    shapes = []
+    for i in range(400):
+        F = fixed_F[i % len(fixed_F)] if i % 2 == 0 else int(rng.integers(1, 300_000))
+        shapes.append((int(2 ** rng.integers(6, 13)), int(rng.integers(0, 2)), int(rng.integers(1, 25)), int(rng.integers(1, 41)),
+                       int(rng.integers(1, 17)), bool(rng.integers(0, 2)), F, int(rng.choice([64, 256, 304]))))
+    # the corners a random draw may miss: the eligibility edges of every kernel
+    shapes += [(512, 1, m, 1, 1, dump, 96, 256) for m in (4, 8) for dump in (False, True)]
+    shapes += [(512, 0, m, 2, dd, False, 97, 256) for m in (8, 9) for dd in (5, 6, 16)]
+    seen = set()
+    for hop, lay, M, S, D, dump, F, cus in shapes:
+        d = _das_fused_plan(emul_lib, hop, lay, M, S, D, dump, F, cus)
+        k, fpc, cps, ctx = d["kernel"], d["fpc"], d["cps"], ((hop, lay, M, S, D, dump, F, cus), d)
+        seen.add(k)
+        N = 2 * hop
+        group_mode = k == K_REGS and hop < 512
+        budget = cus * ((8 if N <= 512 else 6 if N <= 1024 else 3 if N <= 2048 else 1) if k == K_GEN else 1)
+        streams = S if k == K_DIRS else S * D
+        assert cps >= 1 and (cps - 1) * fpc < F <= cps * fpc, ctx
+        assert cps <= max(1, budget // streams), ctx
+        multiple = 16 * d["group"] if k in (K_REGS, K_IL4, K_IL8, K_DIRS) else 8 if k == K_WAVE2048 else 1
+        assert fpc % multiple == 0, ctx
+        assert d["group"] == (1024 // N if group_mode else 1) and d["group_tables"] == group_mode, ctx
+        assert d["blocks"] == cps * streams, ctx
+        assert d["zero_run_heads"] == (cps > 1 and k != K_GEN), ctx
+        # who may appear where
+        shared_ok = hop == 512 and lay == 0 and M <= 8 and not dump and D >= DEFAULT_SWITCHES["das_shared_dirs"]
+        assert (k == K_DIRS) == shared_ok, ctx
+        assert (k == K_IL4) == (hop == 512 and lay == 1 and M == 4) and (k == K_IL8) == (hop == 512 and lay == 1 and M == 8), ctx
+        assert (k == K_WAVE2048) == (hop == 1024 and not dump), ctx
+        assert group_mode == (hop < 512 and not dump), ctx
+        assert (k == K_GEN) == (hop != 512 and k not in (K_WAVE2048, K_REGS)), ctx
+        if dump:
+            assert k not in (K_WAVE2048, K_DIRS) and not group_mode, ctx
+        if k == K_REGS:
+            np_ = (M + 1) // 2
+            assert d["npl"] == (np_ if np_ <= 2 else 4 if np_ <= 4 else 0) and d["unr"] == (np_ if lay == 0 and np_ <= 4 else 0), ctx
+    assert seen == set(range(6))
+
+
+def test_das_fused_switches_route_to_the_cross_check_kernels(emul_lib):
+    """BF_DAS_INTERLEAVE=0 / BF_DAS_SPLIT2048=0: the LDS-staged kernel instead of group mode / the wavefront-per-frame kernel;
+    BF_DAS_SHARED_DIRS=0: the per-direction kernel; each leaves the other shapes alone."""
+    shapes = [(hop, lay, 8, 2, 8, 97, 256) for hop in (64, 128, 256, 512, 1024, 2048) for lay in (0, 1)]
+    for hop, lay, M, S, D, F, cus in shapes:
+        base = _das_fused_plan(emul_lib, hop, lay, M, S, D, False, F, cus)
+        for name in DEFAULT_SWITCHES:
+            off = _das_fused_plan(emul_lib, hop, lay, M, S, D, False, F, cus, **{**DEFAULT_SWITCHES, name: 0})
+            hit = {"das_interleave": hop < 512, "das_split2048": hop == 1024, "das_shared_dirs": hop == 512 and lay == 0}[name]
+            if not hit:
+                assert off == base, (name, hop, lay)
+            elif name == "das_shared_dirs":
+                assert base["kernel"] == K_DIRS and (off["kernel"], off["npl"], off["unr"], off["group"]) == (K_REGS, 4, 4, 1), (hop, lay, off)
+                assert off["blocks"] == off["cps"] * S * D and base["blocks"] == base["cps"] * S
+            else:
+                assert base["kernel"] == (K_REGS if hop < 512 else K_WAVE2048) and off["kernel"] == K_GEN, (name, hop, lay, off)
+                assert not off["group_tables"] and off["group"] == 1 and not off["zero_run_heads"]
+    # the threshold itself: BF_DAS_SHARED_DIRS = the smallest direction count that shares the transforms
+    for thr, dirs, want in ((6, 5, K_REGS), (6, 6, K_DIRS), (2, 2, K_DIRS), (9, 8, K_REGS), (-1, 8, K_REGS)):
+        assert _das_fused_plan(emul_lib, 512, 0, 8, 1, dirs, False, 96, 256, das_shared_dirs=thr)["kernel"] == want, (thr, dirs)
