@@ -991,134 +991,101 @@ __global__ __launch_bounds__(256, WPS) void cov2d_kernel(BinsArgs a, int tile, i
 
 }  // namespace
 
-hipError_t launch_mvdr_lcmv(const BinsArgs &a, int n_cus, hipStream_t s) {
+hipError_t launch_mvdr_lcmv(const ChainPlan &p, const BinsArgs &a, int n_cus, hipStream_t s) {
     int tile = 64;
     if (a.n_frames < tile) tile = (int)a.n_frames;
     const int tps = (int)((a.n_frames + tile - 1) / tile);
-    const int M = a.n_mics, km = a.kp1 <= 1 ? 1 : 4;
-    const bool no_fast = switches().mvdr_group, no_2d = no_fast;
-    // frequencies of the irregular problems (quirk Q1, util.h:190-199): f[N/2] = 0, f[N/2+1] = -(N/2-1) sr/N
-    const double f_qx = (double)(kN / 2 - 1) * a.cfg.sample_rate / (double)kN;
-    const bool band_hits_nyquist = (0.0 >= a.cfg.freq_min && 0.0 <= a.cfg.freq_max) || (f_qx >= a.cfg.freq_min && f_qx <= a.cfg.freq_max);
-    // lcmv with up to 8 microphones rides mvdr_fast_kernel while its columns fit the register file beside R and its working copy:
-    // any K <= 3 up to 6 microphones, K <= 2 at 7-8 (K = 3 at 7-8 spills 36 registers and still beats every other kernel)
-    const bool lcmv_fast = !no_fast && a.cfg.algo == BF_LCMV && M <= 8 && a.kp1 <= 4;
-    (void)band_hits_nyquist;
+    if (p.bins == ChainBins::kMvdrLcmv) {  // a group of MP lanes per problem, padding rows / columns are identity
 #define BF_LAUNCH_ML(MP_, KM_)                                                                                   \
     BF_LAUNCH((mvdr_lcmv_kernel<MP_, KM_>), dim3(tps * a.n_streams, (kNQ + (256 / MP_) - 1) / (256 / MP_)), \
                        dim3(256), 0, s, a, tile, tps)
-    // beyond the tuned shapes -- more than 3 interferers (lcmv.cpp:258-309 appends without a cap; the yaml lists
-    // angle_interf1..15) or more than 16 microphones -- the row-per-lane group kernel runs with the next larger
-    // (lanes per problem, constraint columns) instantiation; padding rows / columns are identity
-    if (a.kp1 > 4 || M > 16) {
-        if (a.kp1 > 16 || M > 32) return hipErrorInvalidValue;
-        if (a.kp1 <= 1) {
-            BF_LAUNCH_ML(32, 1);
-        } else if (a.kp1 <= 4) {
-            BF_LAUNCH_ML(32, 4);
-        } else if (a.kp1 <= 8) {
-            if (M <= 8) BF_LAUNCH_ML(8, 8);
-            else if (M <= 16) BF_LAUNCH_ML(16, 8);
-            else BF_LAUNCH_ML(32, 8);
+        if (p.km == 1) {
+            if (p.mp == 4) BF_LAUNCH_ML(4, 1); else if (p.mp == 8) BF_LAUNCH_ML(8, 1); else if (p.mp == 16) BF_LAUNCH_ML(16, 1); else BF_LAUNCH_ML(32, 1);
+        } else if (p.km == 4) {
+            if (p.mp == 4) BF_LAUNCH_ML(4, 4); else if (p.mp == 8) BF_LAUNCH_ML(8, 4); else if (p.mp == 16) BF_LAUNCH_ML(16, 4); else BF_LAUNCH_ML(32, 4);
+        } else if (p.km == 8) {
+            if (p.mp == 8) BF_LAUNCH_ML(8, 8); else if (p.mp == 16) BF_LAUNCH_ML(16, 8); else BF_LAUNCH_ML(32, 8);
         } else {
-            if (M <= 16) BF_LAUNCH_ML(16, 16);
-            else BF_LAUNCH_ML(32, 16);
+            if (p.mp == 16) BF_LAUNCH_ML(16, 16); else BF_LAUNCH_ML(32, 16);
         }
+#undef BF_LAUNCH_ML
         return hipGetLastError();
     }
     // 9..16 microphones, up to 3 interferers: 2-D cyclic 4 x 4 lanes per problem.  Wavefronts per SIMD: with constraint columns (lcmv) the
     // three-wavefront build spills 30 registers per lane and the spill traffic alone is 6 GB per 32 768 frames of 16 microphones: two
     // wavefronts at 211 registers are 7 % faster; without constraints (mvdr) three wavefronts win by 12 %
-    if (!no_2d && M > 8 && M <= 16) {
+    if (p.bins == ChainBins::kCov2d) {
         const dim3 grid((unsigned)(((long)tps * a.n_streams + 7) / 8 * 8 * ((kNQ + 15) / 16)));  // (unit, problem group) -> XCD-aware order in the kernel
-        if (km == 1) {
-            if (a.z48) BF_LAUNCH((cov2d_kernel<1, 3, false>), grid, dim3(256), 0, s, a, tile, tps);
+        if (p.km == 1) {
+            if (p.z48) BF_LAUNCH((cov2d_kernel<1, 3, false>), grid, dim3(256), 0, s, a, tile, tps);
             else BF_LAUNCH((cov2d_kernel<1, 3, true>), grid, dim3(256), 0, s, a, tile, tps);
         } else {
-            if (a.z48) BF_LAUNCH((cov2d_kernel<4, 2, false>), grid, dim3(256), 0, s, a, tile, tps);
+            if (p.z48) BF_LAUNCH((cov2d_kernel<4, 2, false>), grid, dim3(256), 0, s, a, tile, tps);
             else BF_LAUNCH((cov2d_kernel<4, 2, true>), grid, dim3(256), 0, s, a, tile, tps);
         }
         return hipGetLastError();
     }
-    if ((a.cfg.algo == BF_MVDR || lcmv_fast) && M <= 8 && !no_fast) {
-        // the problems that need a solve (FastPlan): 0, the in-band run inside 1 .. N/2-1, and N/2 / N/2+1 when in band
-        const std::vector<double> fr = frequency_vector(kN, a.cfg.sample_rate);  // the table the other kernels read (a.freqs)
-        auto inb = [&](int q) {
-            const double f = std::fabs(fr[q_bin_host(q)]);
-            return f >= a.cfg.freq_min && f <= a.cfg.freq_max;
-        };
-        FastPlan fp;
-        fp.q_lo = 1;
-        while (fp.q_lo < kN / 2 && !inb(fp.q_lo)) ++fp.q_lo;
-        fp.n_main = 0;
-        while (fp.q_lo + fp.n_main < kN / 2 && inb(fp.q_lo + fp.n_main)) ++fp.n_main;
-        for (int q = fp.q_lo + fp.n_main; q < kN / 2; ++q)
-            if (inb(q)) return hipErrorInvalidValue;  // cannot happen: |f| rises with q below N/2
-        fp.n_extra = 0;
-        fp.extra_q[0] = fp.extra_q[1] = 0;
-        if (inb(kN / 2)) fp.extra_q[fp.n_extra++] = kN / 2;          // f[N/2] := 0 (quirk Q1): in band when 0 Hz is
-        if (inb(kN / 2 + 1)) fp.extra_q[fp.n_extra++] = kN / 2 + 1;  // the conjugate problem
-        fp.solve0 = (a.cfg.algo == BF_LCMV && inb(0)) ? 1 : 0;
-        fp.nb = 1 + fp.n_main + fp.n_extra;
-        // tile length: the wavefronts (64 lanes = 64 (tile, problem) pairs) should fill the 4 x CUs slots a whole number of times;
-        // cost of a choice = rounds x (frames walked + P warm-up frames); BF_MVDR_TILE forces a length (tests: lanes that straddle tiles,
-        // a short last tile)
-        const int ft_env = switches().mvdr_tile;
-        // resident wavefronts per CU: the prefetch buffers (2 x 2 MP rows of 1 KiB in LDS) and the register count of the instantiation
-        // that will run decide -- 8 microphones: one per SIMD (512 registers); fewer microphones: more
-        const int mp_ = M <= 2 ? 2 : M <= 4 ? 4 : M <= 6 ? 6 : 8;
-        const int kc_ = (!lcmv_fast || a.kp1 <= 1) ? 1 : a.kp1;
-        const int wpc = mp_ == 2 ? 16 : mp_ == 4 ? (kc_ <= 2 ? 9 : 8) : mp_ == 6 ? (kc_ == 1 ? 6 : 4) : 4;
-        const long slots = (long)n_cus * wpc, F = a.n_frames;
-        long best_t = 1;
-        double best_c = 1e300;
-        for (long t = 1; t <= 512 && t <= F; ++t) {
-            const long tiles = (F + t - 1) / t;
-            const long waves = (long)a.n_streams * ((tiles * fp.nb + 63) / 64);
-            const long rounds = (waves + slots - 1) / slots;
-            const double c = (double)rounds * (double)(t + a.cfg.past_windows + 2);
-            if (c <= best_c) { best_c = c; best_t = t; }
-        }
-        if (ft_env > 0) best_t = ft_env < F ? ft_env : F;
-        fp.tile = (int)best_t;
-        fp.tiles = (int)((F + best_t - 1) / best_t);
-        fp.waves_per_stream = (int)(((long)fp.tiles * fp.nb + 63) / 64);
-        const bool band_rows = a.yh_lo > 0 || a.yh_hi < a.yh_lo;  // the consumer reads problem 0 and yh_lo..yh_hi only (a band below the Nyquist problems, no dump)
-        if (!a.yh32 && !band_rows)  // f64x2 rows read in full (spectrum dump, other FFT sizes, a band up to Nyquist): the rows nobody solves read as zero (mvdr.cpp:103)
-            (void)hipMemsetAsync(a.Yh, 0, (size_t)a.n_streams * a.n_frames * kYhStride * sizeof(f64x2), s);
-        else if (a.yh32 && a.yh_lo == 0 && fp.nb < kNQ)  // f32x2 rows that the backward transform reads in full (a band up to the Nyquist problems) while part of them is out of band
-            (void)hipMemsetAsync(a.Yh, 0, (size_t)a.n_streams * a.n_frames * kYhStride * sizeof(f32x2), s);
-        const dim3 grid((unsigned)((long)fp.waves_per_stream * a.n_streams));
+    // kMvdrFast.  The problems that need a solve (FastPlan): 0, the in-band run inside 1 .. N/2-1, and N/2 / N/2+1 when in band
+    // (the irregular problems of quirk Q1, util.h:190-199: f[N/2] = 0, f[N/2+1] = -(N/2-1) sr/N)
+    const std::vector<double> fr = frequency_vector(kN, a.cfg.sample_rate);  // the table the other kernels read (a.freqs)
+    auto inb = [&](int q) {
+        const double f = std::fabs(fr[q_bin_host(q)]);
+        return f >= a.cfg.freq_min && f <= a.cfg.freq_max;
+    };
+    FastPlan fp;
+    fp.q_lo = 1;
+    while (fp.q_lo < kN / 2 && !inb(fp.q_lo)) ++fp.q_lo;
+    fp.n_main = 0;
+    while (fp.q_lo + fp.n_main < kN / 2 && inb(fp.q_lo + fp.n_main)) ++fp.n_main;
+    for (int q = fp.q_lo + fp.n_main; q < kN / 2; ++q)
+        if (inb(q)) return hipErrorInvalidValue;  // cannot happen: |f| rises with q below N/2
+    fp.n_extra = 0;
+    fp.extra_q[0] = fp.extra_q[1] = 0;
+    if (inb(kN / 2)) fp.extra_q[fp.n_extra++] = kN / 2;          // f[N/2] := 0 (quirk Q1): in band when 0 Hz is
+    if (inb(kN / 2 + 1)) fp.extra_q[fp.n_extra++] = kN / 2 + 1;  // the conjugate problem
+    fp.solve0 = (a.cfg.algo == BF_LCMV && inb(0)) ? 1 : 0;
+    fp.nb = 1 + fp.n_main + fp.n_extra;
+    // tile length: the wavefronts (64 lanes = 64 (tile, problem) pairs) should fill the 4 x CUs slots a whole number of times;
+    // cost of a choice = rounds x (frames walked + P warm-up frames); BF_MVDR_TILE forces a length (tests: lanes that straddle tiles,
+    // a short last tile)
+    const int ft_env = switches().mvdr_tile;
+    // resident wavefronts per CU: the prefetch buffers (2 x 2 MP rows of 1 KiB in LDS) and the register count of the instantiation
+    // that will run decide -- 8 microphones: one per SIMD (512 registers); fewer microphones: more
+    const int wpc = p.mp == 2 ? 16 : p.mp == 4 ? (p.km <= 2 ? 9 : 8) : p.mp == 6 ? (p.km == 1 ? 6 : 4) : 4;
+    const long slots = (long)n_cus * wpc, F = a.n_frames;
+    long best_t = 1;
+    double best_c = 1e300;
+    for (long t = 1; t <= 512 && t <= F; ++t) {
+        const long tiles = (F + t - 1) / t;
+        const long waves = (long)a.n_streams * ((tiles * fp.nb + 63) / 64);
+        const long rounds = (waves + slots - 1) / slots;
+        const double c = (double)rounds * (double)(t + a.cfg.past_windows + 2);
+        if (c <= best_c) { best_c = c; best_t = t; }
+    }
+    if (ft_env > 0) best_t = ft_env < F ? ft_env : F;
+    fp.tile = (int)best_t;
+    fp.tiles = (int)((F + best_t - 1) / best_t);
+    fp.waves_per_stream = (int)(((long)fp.tiles * fp.nb + 63) / 64);
+    if (!p.yh32 && !p.band_rows)  // f64x2 rows read in full (spectrum dump, other FFT sizes, a band up to Nyquist): the rows nobody solves read as zero (mvdr.cpp:103)
+        (void)hipMemsetAsync(a.Yh, 0, (size_t)a.n_streams * a.n_frames * kYhStride * sizeof(f64x2), s);
+    else if (p.yh32 && p.yh_lo == 0 && fp.nb < kNQ)  // f32x2 rows that the backward transform reads in full (a band up to the Nyquist problems) while part of them is out of band
+        (void)hipMemsetAsync(a.Yh, 0, (size_t)a.n_streams * a.n_frames * kYhStride * sizeof(f32x2), s);
+    const dim3 grid((unsigned)((long)fp.waves_per_stream * a.n_streams));
 #define BF_FAST_GO(MP_, KC_)                                                                     \
     do {                                                                                         \
-        if (a.z48) BF_LAUNCH((mvdr_fast_kernel<MP_, KC_, false>), grid, dim3(64), 0, s, a, fp);  \
+        if (p.z48) BF_LAUNCH((mvdr_fast_kernel<MP_, KC_, false>), grid, dim3(64), 0, s, a, fp);  \
         else BF_LAUNCH((mvdr_fast_kernel<MP_, KC_, true>), grid, dim3(64), 0, s, a, fp);         \
     } while (0)
-        if (!lcmv_fast || a.kp1 <= 1) {  // lcmv without interferers = mvdr except problem 0
-            if (M <= 2) BF_FAST_GO(2, 1);
-            else if (M <= 4) BF_FAST_GO(4, 1);
-            else if (M <= 6) BF_FAST_GO(6, 1);
-            else BF_FAST_GO(8, 1);
-        } else if (M <= 2) {
-            BF_FAST_GO(2, 2);
-        } else if (M <= 4) {
-            if (a.kp1 <= 2) BF_FAST_GO(4, 2); else BF_FAST_GO(4, 4);
-        } else if (M <= 6) {
-            if (a.kp1 <= 2) BF_FAST_GO(6, 2); else BF_FAST_GO(6, 4);
-        } else {
-            if (a.kp1 <= 2) BF_FAST_GO(8, 2); else if (a.kp1 == 3) BF_FAST_GO(8, 3); else BF_FAST_GO(8, 4);
-        }
-#undef BF_FAST_GO
-        return hipGetLastError();
-    }
-    if (M <= 4) {
-        if (km == 1) BF_LAUNCH_ML(4, 1); else BF_LAUNCH_ML(4, 4);
-    } else if (M <= 8) {
-        if (km == 1) BF_LAUNCH_ML(8, 1); else BF_LAUNCH_ML(8, 4);
+    if (p.km == 1) {  // mvdr; lcmv without interferers = mvdr except problem 0
+        if (p.mp == 2) BF_FAST_GO(2, 1); else if (p.mp == 4) BF_FAST_GO(4, 1); else if (p.mp == 6) BF_FAST_GO(6, 1); else BF_FAST_GO(8, 1);
+    } else if (p.km == 2) {
+        if (p.mp == 2) BF_FAST_GO(2, 2); else if (p.mp == 4) BF_FAST_GO(4, 2); else if (p.mp == 6) BF_FAST_GO(6, 2); else BF_FAST_GO(8, 2);
+    } else if (p.km == 3) {
+        BF_FAST_GO(8, 3);
     } else {
-        if (km == 1) BF_LAUNCH_ML(16, 1); else BF_LAUNCH_ML(16, 4);
+        if (p.mp == 4) BF_FAST_GO(4, 4); else if (p.mp == 6) BF_FAST_GO(6, 4); else BF_FAST_GO(8, 4);
     }
-#undef BF_LAUNCH_ML
+#undef BF_FAST_GO
     return hipGetLastError();
 }
 

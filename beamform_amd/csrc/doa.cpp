@@ -14,6 +14,7 @@
 #include "doa.hpp"
 #include "geometry.hpp"
 #include "pipeline_kernels.hpp"
+#include "switches.hpp"
 
 using namespace bf;
 
@@ -230,7 +231,10 @@ int bf_doa_process_device(bf_doa *d, const float *x_dev, size_t n_frames, double
         sa.z48 = 0;
         sa.halve = 1;  // X_a = Z[k] + conj Z[N-k], X_b = -i (Z[k] - conj Z[N-k])
         sa.run_len = 1;
-        DOA_HIP(d, d->ks->stft(sa, d->n_cus, s));
+        ChainPlan front{};  // only the STFT of the chain runs here
+        front.layout = d->layout;
+        front.front = chain_stft_front(d->N, switches().stft_small, switches().stft_split);
+        DOA_HIP(d, d->ks->stft(front, sa, d->n_cus, s));
         DoaMapArgs ma;
         ma.Z = d->d_Z.get();
         ma.flags = d->d_flags.get();

@@ -3,7 +3,6 @@
 
 #include "launch_trace.hpp"
 #include "bins_common.hpp"
-#include "switches.hpp"
 
 namespace bf {
 namespace BF_NTAG {
@@ -921,63 +920,56 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 
 }  // namespace
 
-hipError_t launch_gss(const BinsArgs &a, int n_cus, hipStream_t s) {
-    const int M = a.n_mics, km = a.kp1 <= 1 ? 1 : 4;
-    const int groups = a.n_streams * kNQ;
+hipError_t launch_gss(const ChainPlan &p, const BinsArgs &a, hipStream_t s) {
     // One lane per problem pays once the lanes fill the chip: 256 streams x 256 frames 3.33 -> 2.10 ms (4 microphones 1.76 -> 1.24), but ONE
-    // stream of 65 536 frames 69 -> 145 ms (9 wavefronts; a frame step is 2.2 us in one lane, 1.06 us spread over 8): lane kernel from two
-    // wavefronts per CU on.  BF_GSS_GROUP=1 / 0 force the group / the lane kernel (tests, A/B).
-    const bool lane_kernel = switches().gss_group >= 0 ? switches().gss_group == 0 : (long)a.n_streams * ((kNQ + 63) / 64) >= 2L * n_cus;
+    // stream of 65 536 frames 69 -> 145 ms (9 wavefronts; a frame step is 2.2 us in one lane, 1.06 us spread over 8): the plan takes the lane
+    // kernel from two wavefronts per CU on
+    if (p.bins == ChainBins::kGssLane) {
+        const dim3 grid((unsigned)(a.n_streams * ((kNQ + 63) / 64)));
+        if (p.mp == 4) {
+            if (p.km == 1) BF_LAUNCH((gss_lane_kernel<4, 1>), grid, dim3(64), 0, s, a); else BF_LAUNCH((gss_lane_kernel<4, 4>), grid, dim3(64), 0, s, a);
+        } else {
+            if (p.km == 1) BF_LAUNCH((gss_lane_kernel<8, 1>), grid, dim3(64), 0, s, a); else BF_LAUNCH((gss_lane_kernel<8, 4>), grid, dim3(64), 0, s, a);
+        }
+        return hipGetLastError();
+    }
+    const int groups = a.n_streams * kNQ;
 #define BF_LAUNCH_GSS(MP_, KM_) \
     BF_LAUNCH((gss_kernel<MP_, KM_>), dim3((groups + (256 / MP_) - 1) / (256 / MP_)), dim3(256), 0, s, a)
-    if (a.kp1 > 4 || M > 16) {  // beyond the tuned shapes: more interferers (up to 15) or microphones (up to 32)
-        if (a.kp1 > 16 || M > 32) return hipErrorInvalidValue;
-        if (a.kp1 <= 1) BF_LAUNCH_GSS(32, 1);
-        else if (a.kp1 <= 4) BF_LAUNCH_GSS(32, 4);
-        else if (a.kp1 <= 8) { if (M <= 8) BF_LAUNCH_GSS(8, 8); else if (M <= 16) BF_LAUNCH_GSS(16, 8); else BF_LAUNCH_GSS(32, 8); }
-        else { if (M <= 16) BF_LAUNCH_GSS(16, 16); else BF_LAUNCH_GSS(32, 16); }
-    } else if (M <= 8 && lane_kernel) {  // one lane per problem
-        const dim3 grid((unsigned)(a.n_streams * ((kNQ + 63) / 64)));
-        if (M <= 4) {
-            if (km == 1) BF_LAUNCH((gss_lane_kernel<4, 1>), grid, dim3(64), 0, s, a); else BF_LAUNCH((gss_lane_kernel<4, 4>), grid, dim3(64), 0, s, a);
-        } else {
-            if (km == 1) BF_LAUNCH((gss_lane_kernel<8, 1>), grid, dim3(64), 0, s, a); else BF_LAUNCH((gss_lane_kernel<8, 4>), grid, dim3(64), 0, s, a);
-        }
-    } else if (M <= 4) {
-        if (km == 1) BF_LAUNCH_GSS(4, 1); else BF_LAUNCH_GSS(4, 4);
-    } else if (M <= 8) {
-        if (km == 1) BF_LAUNCH_GSS(8, 1); else BF_LAUNCH_GSS(8, 4);
+    if (p.km == 1) {
+        if (p.mp == 4) BF_LAUNCH_GSS(4, 1); else if (p.mp == 8) BF_LAUNCH_GSS(8, 1); else if (p.mp == 16) BF_LAUNCH_GSS(16, 1); else BF_LAUNCH_GSS(32, 1);
+    } else if (p.km == 4) {
+        if (p.mp == 4) BF_LAUNCH_GSS(4, 4); else if (p.mp == 8) BF_LAUNCH_GSS(8, 4); else if (p.mp == 16) BF_LAUNCH_GSS(16, 4); else BF_LAUNCH_GSS(32, 4);
+    } else if (p.km == 8) {  // beyond the tuned shapes: more interferers (up to 15) or microphones (up to 32)
+        if (p.mp == 8) BF_LAUNCH_GSS(8, 8); else if (p.mp == 16) BF_LAUNCH_GSS(16, 8); else BF_LAUNCH_GSS(32, 8);
     } else {
-        if (km == 1) BF_LAUNCH_GSS(16, 1); else BF_LAUNCH_GSS(16, 4);
+        if (p.mp == 16) BF_LAUNCH_GSS(16, 16); else BF_LAUNCH_GSS(32, 16);
     }
 #undef BF_LAUNCH_GSS
     return hipGetLastError();
 }
 
-hipError_t launch_gsc_nlms(const float *aligned, float *y, float *state, long n_samples, int n_streams, int n_mics,
+hipError_t launch_gsc_nlms(const ChainPlan &p, const float *aligned, float *y, float *state, long n_samples, int n_streams, int n_mics,
                            const bf_config &cfg, hipStream_t s) {
     const int fs = cfg.gsc_filter_size, nb = n_mics - 1, nbr = nb > 0 ? nb : 1;
-    const int kpl = (fs + 63) / 64, kp = kpl <= 1 ? 1 : kpl <= 2 ? 2 : 4;
-    // BF_GSC_SERIAL=1: the sums in the reference's tap order, one branch per lane (gsc_nlms_kernel); default: taps over the lanes, the
-    // branches dealt out to 8 wavefronts per stream from five branches on, 4 from three, 2 at two, one branch: gsc_nlms_par_kernel
-    // (8 microphones, 256 streams x 64 frames: 52.6 / 54.2 / 43.1 / 36.8 ms at 1 / 2 / 4 / 8 wavefronts)
-    const bool serial = switches().gsc_serial;
-    const int nw = serial ? 1 : (nb >= 5 ? 8 : nb >= 3 ? 4 : nb >= 2 ? 2 : 1);
+    const bool serial = p.tail == ChainTail::kNlms;
+    const int kp = serial || p.tail == ChainTail::kNlmsPar ? p.t1 : p.t2;  // KPL
     const size_t lds_serial = sizeof(float) * ((size_t)nbr * ((fs + 64 * kp + 8) | 1) + (size_t)nbr * ((64 * kp + 8) | 1) + 2 * fs + 16 +
                                                (size_t)nbr * 64 + 64 + 16 + 64);
     const size_t lds_par = sizeof(float) * ((size_t)nbr * ((fs + 64 * kp + 8) | 1) + 2 * fs + 64 * kp + 16 + (size_t)nbr * 64 + 64 + 64 + 64);
     const size_t lds = serial ? lds_serial : lds_par;
-    if (nw > 1 && nb <= 15) {
-        const int nbl = (nb + nw - 1) / nw;  // <= 4 at nw = 4, <= 8 at nw = 2
+#define BF_BY_KPL(GO_, ...)                  \
+    do {                                     \
+        if (kp == 1) GO_(__VA_ARGS__, 1);    \
+        else if (kp == 2) GO_(__VA_ARGS__, 2);\
+        else GO_(__VA_ARGS__, 4);            \
+    } while (0)
+    if (p.tail == ChainTail::kNlmsMw) {  // the branches dealt out to NW wavefronts per stream, NBL branches each
+        const int nw = p.t0, nbl = p.t1;
 #define BF_MW(NW_, NBL_, KPL_)                                                                                                     \
     BF_LAUNCH((gsc_nlms_mw_kernel<NW_, NBL_, KPL_>), dim3((unsigned)n_streams), dim3(64 * NW_), lds, s, aligned, y, state, \
                        n_samples, n_mics, fs, cfg.gsc_use_vad, cfg.gsc_vad_threshold, cfg.gsc_mu0, cfg.gsc_mu_max)
-#define BF_MW_K(NW_, NBL_)                     \
-    do {                                       \
-        if (kpl <= 1) BF_MW(NW_, NBL_, 1);     \
-        else if (kpl <= 2) BF_MW(NW_, NBL_, 2);\
-        else BF_MW(NW_, NBL_, 4);              \
-    } while (0)
+#define BF_MW_K(NW_, NBL_) BF_BY_KPL(BF_MW, NW_, NBL_)
         if (nw == 8) {
             if (nbl <= 1) BF_MW_K(8, 1); else BF_MW_K(8, 2);
         } else if (nw == 4) {
@@ -998,18 +990,12 @@ hipError_t launch_gsc_nlms(const float *aligned, float *y, float *state, long n_
             BF_LAUNCH((gsc_nlms_par_kernel<NBM_, KPL_>), dim3((unsigned)n_streams), dim3(64), lds, s, aligned, y, state,   \
                                n_samples, n_mics, fs, cfg.gsc_use_vad, cfg.gsc_vad_threshold, cfg.gsc_mu0, cfg.gsc_mu_max);         \
     } while (0)
-#define BF_NLMS_K(NBM_)                     \
-    do {                                    \
-        if (kpl <= 1) BF_NLMS(NBM_, 1);     \
-        else if (kpl <= 2) BF_NLMS(NBM_, 2);\
-        else BF_NLMS(NBM_, 4);              \
-    } while (0)
-    if (nb <= 1) BF_NLMS_K(1);
-    else if (nb <= 3) BF_NLMS_K(3);
-    else if (nb <= 7) BF_NLMS_K(7);
-    else BF_NLMS_K(15);
-#undef BF_NLMS_K
+    if (p.t0 == 1) BF_BY_KPL(BF_NLMS, 1);
+    else if (p.t0 == 3) BF_BY_KPL(BF_NLMS, 3);
+    else if (p.t0 == 7) BF_BY_KPL(BF_NLMS, 7);
+    else BF_BY_KPL(BF_NLMS, 15);
 #undef BF_NLMS
+#undef BF_BY_KPL
     return hipGetLastError();
 }
 

@@ -1379,159 +1379,106 @@ __global__ __launch_bounds__(256, 1) void stft_bins_split_kernel(StftArgs a, Bin
 
 }  // namespace
 
-// stft + per-bin stage of the history-free nodes in one launch; hipErrorNotSupported = use the two-kernel chain
-hipError_t launch_stft_bins_fused(const StftArgs &a, const BinsArgs &b, int n_cus, hipStream_t s) {
+// what follows the per-bin kernel, after launch_bins and after launch_stft_bins_fused alike
+hipError_t launch_bins_end(const ChainPlan &p, const BinsArgs &a, hipStream_t s) {
+    // aux (|out_int|^2 per problem) lives behind the Yh rows: the plan sizes Yh for it
+    double *aux = reinterpret_cast<double *>(a.Yh + (long)a.n_streams * a.n_frames * kYhStride);
+    if (p.rec == ChainRec::kRecursion) {
+        const int nthr = a.n_streams * kNQ;
+        BF_LAUNCH(mpf_recursion_kernel, dim3((nthr + 63) / 64), dim3(64), 0, s, a, aux);
+    }
 #if BF_NFFT == 1024
-    const int algo = b.cfg.algo;
-    if (!(algo == BF_DAS || algo == BF_PHASE || algo == BF_PHASEMPF)) return hipErrorNotSupported;
-    if (a.n_mics > 8 || a.n_fft_mics != a.n_mics || b.n_dirs != 1 || a.frame_off != 0 || b.n_streams != a.n_streams)
-        return hipErrorNotSupported;
-    double *aux = reinterpret_cast<double *>(b.Yh + (long)b.n_streams * b.n_frames * kYhStride);
-    f64x2 *xtail = a.Z;  // [stream][frame][2][MP]: the caller sizes the Z workspace for it (fused_tail_elems)
-    if (!xtail) return hipErrorInvalidValue;
-    const long tail_items = (long)b.n_streams * b.n_frames * 2;
-    const unsigned tail_blocks = (unsigned)((tail_items + 255) / 256);
-    if (a.tw_w64 == nullptr) return hipErrorNotSupported;
-    const long wtotal = a.n_frames * a.n_streams;  // frames, numbered stream * n_frames + frame; one contiguous range per block
-    long wblocks = wtotal < n_cus ? wtotal : n_cus;
-    if (wblocks < 1) wblocks = 1;
-    const long wfpb = (wtotal + wblocks - 1) / wblocks;
-    wblocks = (wtotal + wfpb - 1) / wfpb;
-#define BF_FUSED_GO(L_, MP_, A_)                                                                                             \
-    do {                                                                                                                      \
-        BF_LAUNCH((stft_bins_w64_kernel<L_, MP_, A_>), dim3((unsigned)wblocks), dim3(512), 0, s, a, b, wfpb, wtotal, aux, xtail);   \
-        BF_LAUNCH((fused_tail_kernel<MP_, A_>), dim3(tail_blocks), dim3(256), 0, s, b, (const f64x2 *)xtail, aux);   \
-    } while (0)
-#define BF_FUSED_ALGO(L_, MP_)                                   \
-    do {                                                          \
-        if (algo == BF_DAS) BF_FUSED_GO(L_, MP_, BF_DAS);         \
-        else if (algo == BF_PHASE) BF_FUSED_GO(L_, MP_, BF_PHASE); \
-        else BF_FUSED_GO(L_, MP_, BF_PHASEMPF);                   \
-    } while (0)
-    if (a.layout == 0) {
-        if (a.n_mics <= 4) BF_FUSED_ALGO(0, 4); else BF_FUSED_ALGO(0, 8);
-    } else {
-        if (a.n_mics <= 4) BF_FUSED_ALGO(1, 4); else BF_FUSED_ALGO(1, 8);
-    }
-#undef BF_FUSED_ALGO
-#undef BF_FUSED_GO
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (algo == BF_PHASEMPF) {  // second pass of launch_phasempf: the recursion over frames (with many streams: and the backward transform)
-        if (b.rec_istft) {
-            BF_LAUNCH(mpf_rec_istft_kernel, dim3((unsigned)b.n_streams), dim3(kRiThreads), 0, s, b, aux);
-        } else {
-            const int nthr = b.n_streams * kNQ;
-            BF_LAUNCH(mpf_recursion_kernel, dim3((nthr + 63) / 64), dim3(64), 0, s, b, aux);
-        }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && b.spectrum) e = launch_expand_spectrum(b.Yh, b.spectrum, (long)b.n_streams * b.n_frames, s);
-    return e;
-#elif BF_NFFT == 128 || BF_NFFT == 256 || BF_NFFT == 512 || BF_NFFT == 2048
-    const int algo = b.cfg.algo;
-    if (!(algo == BF_DAS || algo == BF_PHASE || algo == BF_PHASEMPF)) return hipErrorNotSupported;
-    if (a.n_mics > 8 || a.n_fft_mics != a.n_mics || b.n_dirs != 1 || a.frame_off != 0 || b.n_streams != a.n_streams)
-        return hipErrorNotSupported;
-#if BF_NFFT == 2048
-    const int fpr = a.n_mics <= 4 ? 2 : 1;  // frames per round
-#define BF_FUSED_KERNEL stft_bins_split_kernel
-#else
-    const int fpr = (a.n_mics <= 4 ? 4 : 2) * (1024 / kN);  // frames per round
-#define BF_FUSED_KERNEL stft_bins_small_kernel
+    if (p.rec == ChainRec::kRecIstft) BF_LAUNCH(mpf_rec_istft_kernel, dim3((unsigned)a.n_streams), dim3(kRiThreads), 0, s, a, aux);
 #endif
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess && p.expand ? launch_expand_spectrum(a.Yh, a.spectrum, (long)a.n_streams * a.n_frames, s) : e;
+}
+
+// The fused front of this FFT size: frames per round of a block, and the kernel with its block size.  N = 1024 walks single frames.
+#if BF_NFFT == 1024
+#define BF_FUSED_FPR 1
+#define BF_FUSED_FRONT(L_, MP_, A_) BF_LAUNCH((stft_bins_w64_kernel<L_, MP_, A_>), grid, dim3(512), 0, s, a, b, rpb, total, aux, xtail)
+#elif BF_NFFT == 2048
+#define BF_FUSED_FPR (p.mp == 4 ? 2 : 1)
+#define BF_FUSED_FRONT(L_, MP_, A_) BF_LAUNCH((stft_bins_split_kernel<L_, MP_, A_>), grid, dim3(256), 0, s, a, b, rps, total, rpb, aux, xtail)
+#elif BF_NFFT < 1024
+#define BF_FUSED_FPR ((p.mp == 4 ? 4 : 2) * (1024 / kN))
+#define BF_FUSED_FRONT(L_, MP_, A_) BF_LAUNCH((stft_bins_small_kernel<L_, MP_, A_>), grid, dim3(256), 0, s, a, b, rps, total, rpb, aux, xtail)
+#endif
+
+// stft + per-bin stage of the history-free nodes in one launch (ChainPlan::fused())
+hipError_t launch_stft_bins_fused(const ChainPlan &p, const StftArgs &a, const BinsArgs &b, int n_cus, hipStream_t s) {
+#ifdef BF_FUSED_FRONT
+    const int fpr = BF_FUSED_FPR;
     const long rps = (a.n_frames + fpr - 1) / fpr;
-    const long total = rps * a.n_streams;
+    const long total = rps * a.n_streams;  // rounds, numbered stream * rps + round; one contiguous range per block
     long blocks = total < n_cus ? total : n_cus;
     if (blocks < 1) blocks = 1;
     const long rpb = (total + blocks - 1) / blocks;
-    blocks = (total + rpb - 1) / rpb;
+    const dim3 grid((unsigned)((total + rpb - 1) / rpb));
     double *aux = reinterpret_cast<double *>(b.Yh + (long)b.n_streams * b.n_frames * kYhStride);
-    f64x2 *xtail = a.Z;  // [stream][frame][2][MP]: the caller sizes the Z workspace for it
-    if (!xtail) return hipErrorInvalidValue;
+    f64x2 *xtail = a.Z;  // [stream][frame][2][MP]: the plan sizes the Z workspace for it
     const long tail_items = (long)b.n_streams * b.n_frames * 2;
     const unsigned tail_blocks = (unsigned)((tail_items + 255) / 256);
-#define BF_FUSED_GO(L_, MP_, A_)                                                                                                                  \
-    do {                                                                                                                                          \
-        BF_LAUNCH((BF_FUSED_KERNEL<L_, MP_, A_>), dim3((unsigned)blocks), dim3(256), 0, s, a, b, rps, total, rpb, aux, xtail);           \
-        BF_LAUNCH((fused_tail_kernel<MP_, A_>), dim3(tail_blocks), dim3(256), 0, s, b, (const f64x2 *)xtail, aux);                       \
+#define BF_FUSED_GO(L_, MP_, A_)                                                                                     \
+    do {                                                                                                             \
+        BF_FUSED_FRONT(L_, MP_, A_);                                                                                 \
+        BF_LAUNCH((fused_tail_kernel<MP_, A_>), dim3(tail_blocks), dim3(256), 0, s, b, (const f64x2 *)xtail, aux);   \
     } while (0)
-#define BF_FUSED_ALGO(L_, MP_)                                   \
-    do {                                                          \
-        if (algo == BF_DAS) BF_FUSED_GO(L_, MP_, BF_DAS);         \
-        else if (algo == BF_PHASE) BF_FUSED_GO(L_, MP_, BF_PHASE); \
-        else BF_FUSED_GO(L_, MP_, BF_PHASEMPF);                   \
+#define BF_FUSED_ALGO(L_, MP_)                                       \
+    do {                                                             \
+        if (p.algo == BF_DAS) BF_FUSED_GO(L_, MP_, BF_DAS);          \
+        else if (p.algo == BF_PHASE) BF_FUSED_GO(L_, MP_, BF_PHASE); \
+        else BF_FUSED_GO(L_, MP_, BF_PHASEMPF);                      \
     } while (0)
-    if (a.layout == 0) {
-        if (a.n_mics <= 4) BF_FUSED_ALGO(0, 4); else BF_FUSED_ALGO(0, 8);
+    if (p.layout == 0) {
+        if (p.mp == 4) BF_FUSED_ALGO(0, 4); else BF_FUSED_ALGO(0, 8);
     } else {
-        if (a.n_mics <= 4) BF_FUSED_ALGO(1, 4); else BF_FUSED_ALGO(1, 8);
+        if (p.mp == 4) BF_FUSED_ALGO(1, 4); else BF_FUSED_ALGO(1, 8);
     }
 #undef BF_FUSED_ALGO
 #undef BF_FUSED_GO
-#undef BF_FUSED_KERNEL
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (algo == BF_PHASEMPF) {  // second pass of launch_phasempf: the recursion over frames
-        const int nthr = b.n_streams * kNQ;
-        BF_LAUNCH(mpf_recursion_kernel, dim3((nthr + 63) / 64), dim3(64), 0, s, b, aux);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && b.spectrum) e = launch_expand_spectrum(b.Yh, b.spectrum, (long)b.n_streams * b.n_frames, s);
-    return e;
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : launch_bins_end(p, b, s);
 #else
-    (void)a; (void)b; (void)n_cus; (void)s;
-    return hipErrorNotSupported;
+    (void)p; (void)a; (void)b; (void)n_cus; (void)s;
+    return hipErrorInvalidValue;  // no fused front at this size: the plan never names one
 #endif
 }
+#undef BF_FUSED_FRONT
+#undef BF_FUSED_FPR
 
-hipError_t launch_phasempf(const BinsArgs &a, int n_cus, hipStream_t s) {
-    // aux (|out_int|^2 per problem) lives behind the Yh rows: Yh was allocated with 2x room by the pipeline
+// MP_ = 4 / 8 / 16 / 32 of the plan -> the instantiation
+#define BF_BY_MP(GO_)                \
+    do {                             \
+        if (p.mp == 4) GO_(4);       \
+        else if (p.mp == 8) GO_(8);  \
+        else if (p.mp == 16) GO_(16);\
+        else GO_(32);                \
+    } while (0)
+
+hipError_t launch_mpf_mask(const ChainPlan &p, const BinsArgs &a, hipStream_t s) {
     double *aux = reinterpret_cast<double *>(a.Yh + (long)a.n_streams * a.n_frames * kYhStride);
     const long total = (long)a.n_streams * a.n_frames * kNQ;
     const unsigned blocks = (unsigned)((total + 255) / 256);
-    if (a.n_mics <= 4)
-        BF_LAUNCH((mpf_mask_kernel<4>), dim3(blocks), dim3(256), 0, s, a, aux);
-    else if (a.n_mics <= 8)
-        BF_LAUNCH((mpf_mask_kernel<8>), dim3(blocks), dim3(256), 0, s, a, aux);
-    else if (a.n_mics <= 16)
-        BF_LAUNCH((mpf_mask_kernel<16>), dim3(blocks), dim3(256), 0, s, a, aux);
-    else
-        BF_LAUNCH((mpf_mask_kernel<32>), dim3(blocks), dim3(256), 0, s, a, aux);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-#if BF_NFFT == 1024
-    if (a.rec_istft) {
-        BF_LAUNCH(mpf_rec_istft_kernel, dim3((unsigned)a.n_streams), dim3(kRiThreads), 0, s, a, aux);
-        return hipGetLastError();
-    }
-#endif
-    const int nthr = a.n_streams * kNQ;
-    BF_LAUNCH(mpf_recursion_kernel, dim3((nthr + 63) / 64), dim3(64), 0, s, a, aux);
+#define BF_MASK(MP_) BF_LAUNCH((mpf_mask_kernel<MP_>), dim3(blocks), dim3(256), 0, s, a, aux)
+    BF_BY_MP(BF_MASK);
+#undef BF_MASK
     return hipGetLastError();
 }
 
-template <int ALGO>
-static void launch_pointwise_t(const BinsArgs &a, hipStream_t s) {
+hipError_t launch_pointwise(const ChainPlan &p, const BinsArgs &a, hipStream_t s) {
     const long total = (long)a.n_streams * a.n_frames * kNQ;
     const unsigned blocks = (unsigned)((total + 255) / 256);
-    if (a.n_mics <= 4)
-        BF_LAUNCH((pointwise_bins_kernel<4, ALGO>), dim3(blocks), dim3(256), 0, s, a);
-    else if (a.n_mics <= 8)
-        BF_LAUNCH((pointwise_bins_kernel<8, ALGO>), dim3(blocks), dim3(256), 0, s, a);
-    else if (a.n_mics <= 16)
-        BF_LAUNCH((pointwise_bins_kernel<16, ALGO>), dim3(blocks), dim3(256), 0, s, a);
-    else
-        BF_LAUNCH((pointwise_bins_kernel<32, ALGO>), dim3(blocks), dim3(256), 0, s, a);
-}
-
-hipError_t launch_pointwise(const BinsArgs &a, hipStream_t s) {
-    if (a.cfg.algo == BF_DAS)
-        launch_pointwise_t<BF_DAS>(a, s);
-    else
-        launch_pointwise_t<BF_PHASE>(a, s);
+#define BF_PW_DAS(MP_) BF_LAUNCH((pointwise_bins_kernel<MP_, BF_DAS>), dim3(blocks), dim3(256), 0, s, a)
+#define BF_PW_PHASE(MP_) BF_LAUNCH((pointwise_bins_kernel<MP_, BF_PHASE>), dim3(blocks), dim3(256), 0, s, a)
+    if (p.algo == BF_DAS) BF_BY_MP(BF_PW_DAS);
+    else BF_BY_MP(BF_PW_PHASE);
+#undef BF_PW_PHASE
+#undef BF_PW_DAS
     return hipGetLastError();
 }
+#undef BF_BY_MP
 
 hipError_t launch_mcra_node(const BinsArgs &a, hipStream_t s) {
     BF_LAUNCH(mcra_node_kernel, dim3((a.n_streams * kNQ + 63) / 64), dim3(64), 0, s, a);

@@ -342,23 +342,19 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
                                const RunSnapshot &snap) {
     // One pass over the whole batch: cutting it into Infinity-Cache-sized frame tiles was measured (3.9-12 ms for mvdr instead of
     // 3.0: per-tile launches underfill the chip and the per-bin kernels lose their parallelism over time) -- DESIGN.md 3.2
+    const Switches &sw = switches();
+    // everything this batch launches, its row formats and workspace sizes: decided once, from values (chain_plan.hpp)
+    const ChainPlan p = chain_decide(ChainShape{cfg_.algo, N_, layout, M_, S_, cfg_.n_dirs > 1 ? cfg_.n_dirs : 1, snap.kp1, cfg_.past_windows,
+                                                cfg_.precision, spectrum != nullptr, F, n_cus_, cfg_.gsc_filter_size, cfg_.smooth_size,
+                                                band_yh_lo_, band_yh_hi_, (reinterpret_cast<size_t>(y) & 15) == 0, sw.fused_bins,
+                                                sw.stft_small, sw.stft_split, sw.mvdr_group, sw.gss_group, sw.gsc_serial});
     float *const hist = d_hist2_[hist_cur_].get();
     const long FT = Phist_ + F;  // frames in the Z workspace per stream
-    // nodes without a frame history: STFT and per-bin stage in one launch, spectra never leave the CU (launch_stft_bins_fused;
-    // BF_FUSED_BINS=0 selects the two-kernel chain) -- then the Z workspace (64 KB per frame at 8 microphones) is not needed at all
-    const bool try_fused = switches().fused_bins != 0 && Phist_ == 0 && N_ <= 2048 && M_ <= 8 && MF_ == M_ && D_ == 1 &&  // (N = 128 / 256 / 512: stft_bins_small_kernel, 2048: stft_bins_split_kernel)
-                           (cfg_.algo == BF_DAS || cfg_.algo == BF_PHASE || cfg_.algo == BF_PHASEMPF);
-    if (!try_fused)
-        // (+ 512 frames of slack behind the last stream: mvdr_fast_kernel's lanes of a short last tile prefetch up to one tile
-        // length past the end of their stream and never use what they fetched)
-        ENGINE_HIP(d_Z_.reserve(((size_t)S_ * FT + (cov_node_ ? 512 : 0)) * NP_ * N_ * zsz_));
-    else  // the fused kernel parks the unpacked spectra of two bins per frame here (stream x frame x 2 x 8 microphones)
-        ENGINE_HIP(d_Z_.reserve((size_t)S_ * F * 2 * 8 * sizeof(f64x2)));
-    // phasempf keeps |out_int|^2 (one double per problem) behind the spectrum rows
-    ENGINE_HIP(d_Yh_.reserve((size_t)So_ * F * YS_ * (sizeof(f64x2) + (cfg_.algo == BF_PHASEMPF ? sizeof(double) : 0))));
-    if (yraw_target_) ENGINE_HIP(d_yraw_.reserve((size_t)So_ * F * H_));
-    if (N_ != 1024) ENGINE_HIP(d_frames_.reserve((size_t)So_ * F * N_));
-    f64x2 *Z = (f64x2 *)d_Z_.get();
+    ENGINE_HIP(d_Z_.reserve(p.z_bytes));
+    ENGINE_HIP(d_Yh_.reserve(p.yh_bytes));
+    ENGINE_HIP(d_yraw_.reserve(p.yraw_elems));
+    ENGINE_HIP(d_frames_.reserve(p.frames_elems));
+    f64x2 *const Z = (f64x2 *)d_Z_.get();
     f64x2 *const Yh = (f64x2 *)d_Yh_.get();
     const size_t frame_elems = (size_t)NP_ * N_;
 
@@ -372,89 +368,59 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
     sa.n_frames = F; sa.frames_ws = FT; sa.frame_off = Phist_; sa.mic_stride = mic_stride;
     sa.stream_stride_x = (long)M_ * F * H_; sa.n_streams = S_; sa.n_mics = M_; sa.n_fft_mics = MF_; sa.layout = layout;
     sa.skip_lo = skip_lo_; sa.skip_hi = skip_hi_;
-    sa.z48 = z48_ ? 1 : 0; sa.run_len = 1; sa.tw_w64 = d_tw_w64_.get();
+    sa.z48 = p.z48 ? 1 : 0; sa.run_len = 1; sa.tw_w64 = d_tw_w64_.get();
     sa.halve = cov_node_ ? 1 : 0;
     if (time_node_ && spectrum) {  // time-domain node: there is no single y_fft; the dump reads as zeros
         ENGINE_HIP(hipMemsetAsync(spectrum, 0, (size_t)S_ * F * N_ * sizeof(f64x2), stream));
         spectrum = nullptr;
     }
-    BinsArgs ba;
-    ba.Z = Z; ba.Yh = Yh; ba.spectrum = spectrum; ba.steer = snap.steer; ba.freqs = d_freq_.get();
-    ba.n_frames = F; ba.frames_ws = FT; ba.frame_off = Phist_; ba.n_streams = So_; ba.n_mics = MF_; ba.kp1 = snap.kp1;
-    ba.n_dirs = D_; ba.steer_dir_stride = snap.steer_dir_stride;
-    ba.z48 = z48_ ? 1 : 0;
-    ba.cfg = cfg_; ba.gssW = d_gssW_.get(); ba.mpf = d_mpf_.get(); ba.gss_reset_mask = snap.gss_reset_mask;
     // Backward transform.  BF_PRECISION_REFERENCE (the default): in double behind every node (istft_w64_kernel at N = 1024: with it the float
     // output of das, phase, phasempf, gss and mcra equals the oracle's bit for bit).  BF_PRECISION_MIXED: in fp32 (istft32_kernel) wherever
     // the per-bin stage can emit f32x2 rows: mvdr / lcmv (band-limited rows: half the row traffic, no zero-fill), das / phase through the
     // bin pipeline, phasempf.  gsc (its sample-serial NLMS branches on the aligned signals), a spectrum dump and the other FFT sizes: always
     // in double.
-    const bool want32 = cfg_.precision == BF_PRECISION_MIXED && !time_node_ && N_ == 1024 && spectrum == nullptr;
-    // mvdr / lcmv hand the fp32 transform f32x2 rows holding only problem 0 and the in-band problems (everything else is zero,
-    // mvdr.cpp:103); das / phase through the bin pipeline: f32x2 rows too (every problem written)
-    const bool pointwise32 = (cfg_.algo == BF_DAS || cfg_.algo == BF_PHASE) && want32;
-    ba.yh32 = ((z48_ && want32) || pointwise32) ? 1 : 0;
-    // phasempf: the recursion's y_fft has no reader but the fp32 backward transform either: f32x2 rows in the |out_int|^2 slots
-    ba.mpf32 = (cfg_.algo == BF_PHASEMPF && want32) ? 1 : 0;
-    const bool istft32 = ba.yh32 != 0 || ba.mpf32 != 0;
-    // mvdr / lcmv rows in front of a backward transform (no dump): band-limited (init()): f32x2 rows into istft32_kernel, f64x2 rows into
-    // istft_w64_kernel<true>
-    const bool band_rows = cov_node_ && spectrum == nullptr && N_ == 1024;
-    ba.yh_lo = band_rows ? band_yh_lo_ : 0; ba.yh_hi = band_rows ? band_yh_hi_ : NQ_ - 1;
-    // phasempf with at least a quarter as many streams as CUs, default precision, no dump: the recursion kernel runs the backward transform too
-    // (mask_kernels.hip mpf_rec_istft_kernel: a block per stream, the y_fft rows stay in LDS); with fewer streams its blocks leave the chip empty
-    const bool rec_istft = cfg_.algo == BF_PHASEMPF && N_ == 1024 && spectrum == nullptr && !ba.mpf32 && (long)So_ * 4 >= n_cus_;
-    if (rec_istft) {
+    BinsArgs ba;
+    ba.Z = Z; ba.Yh = Yh; ba.spectrum = spectrum; ba.steer = snap.steer; ba.freqs = d_freq_.get();
+    ba.n_frames = F; ba.frames_ws = FT; ba.frame_off = Phist_; ba.n_streams = So_; ba.n_mics = MF_; ba.kp1 = snap.kp1;
+    ba.n_dirs = D_; ba.steer_dir_stride = snap.steer_dir_stride;
+    ba.z48 = p.z48 ? 1 : 0;
+    ba.cfg = cfg_; ba.gssW = d_gssW_.get(); ba.mpf = d_mpf_.get(); ba.gss_reset_mask = snap.gss_reset_mask;
+    ba.yh32 = p.yh32 ? 1 : 0; ba.mpf32 = p.mpf32 ? 1 : 0; ba.yh_lo = p.yh_lo; ba.yh_hi = p.yh_hi;
+    if (p.rec_istft()) {  // mpf_rec_istft_kernel: a block per stream, the y_fft rows stay in LDS
         ba.rec_istft = 1;
         ba.rec_y = d_yraw_.get(); ba.rec_tail_in = d_tail_[tail_cur_].get(); ba.rec_tail_out = d_tail_[tail_cur_ ^ 1].get();
         ba.rec_tw_w64 = d_tw_w64_.get(); ba.rec_win = d_win_.get();
     }
-    bool fused = false;
-    if (try_fused) {
-        const hipError_t fe = ks_->stft_bins(sa, ba, n_cus_, stream);
-        if (fe == hipSuccess) {
-            fused = true;
-        } else if (fe != hipErrorNotSupported) {
-            ENGINE_HIP(fe);
-        } else {  // the launcher declined: fall back to the two-kernel chain
-            (void)hipGetLastError();
-            ENGINE_HIP(d_Z_.reserve((size_t)S_ * FT * NP_ * N_ * sizeof(f64x2)));
-            Z = (f64x2 *)d_Z_.get();
-            sa.Z = Z;
-            ba.Z = Z;
-        }
-    }
-    if (!fused) ENGINE_HIP(ks_->stft(sa, n_cus_, stream));
-
-    ENGINE_HIP(carry_last_hop(hist, x, F, H_, M_, S_, layout, mic_stride, (long)F * H_ * M_, stream));
-
-    if (!fused) ENGINE_HIP(ks_->bins(ba, n_cus_, stream));
-
-    if (Phist_ > 0)  // keep the last Phist frames' spectra for the next call
-        ENGINE_HIP(hipMemcpy2DAsync(d_zhist_.get(), (size_t)Phist_ * frame_elems * zsz_, (const char *)Z + (size_t)F * frame_elems * zsz_,
-                                  (size_t)FT * frame_elems * zsz_, (size_t)Phist_ * frame_elems * zsz_, (size_t)S_,
-                                  hipMemcpyDeviceToDevice, stream));
-
     IstftArgs ia;
     ia.Yh = Yh; ia.y = yraw_target_ ? d_yraw_.get() : y; ia.tail_in = d_tail_[tail_cur_].get();
     ia.tail_out = d_tail_[tail_cur_ ^ 1].get(); ia.tw = d_tw_.get(); ia.win = d_win_.get(); ia.n_frames = F; ia.n_streams = So_;
-    ia.tw32 = istft32 ? d_tw32_.get() : nullptr;
+    ia.tw32 = d_tw32_.get();
     ia.tw_w64 = d_tw_w64_.get();
     ia.yh32 = ba.yh32; ia.yh_lo = ba.yh_lo; ia.yh_hi = ba.yh_hi;
-    if (ba.mpf32) {  // rows of 8-byte elements behind the f64x2 rows (where aux lives), every problem written
+    if (p.mpf32) {  // rows of 8-byte elements behind the f64x2 rows (where aux lives), every problem written
         ia.Yh = Yh + (size_t)So_ * F * YS_;
         ia.yh32 = 1; ia.yh_lo = 0; ia.yh_hi = NQ_ - 1;
     }
     ia.frames = d_frames_.get();
     ia.post_amp = post_amp_ ? cfg_.out_amp : 1.0;
     ia.use_post_amp = post_amp_ ? 1 : 0;
-    if (!rec_istft) ENGINE_HIP(ks_->istft(ia, n_cus_, stream));
-    tail_cur_ ^= 1;
 
-    if (cfg_.algo == BF_PHASEMPF)
-        ENGINE_HIP(ks_->smooth(d_yraw_.get(), y, d_smooth_.get(), F, So_, cfg_.smooth_size, stream));
-    if (time_node_)
-        ENGINE_HIP(ks_->gsc_nlms(d_yraw_.get(), y, d_nlms_.get(), F * H_, S_, M_, cfg_, stream));
+    if (p.fused())
+        ENGINE_HIP(ks_->stft_bins(p, sa, ba, n_cus_, stream));
+    else
+        ENGINE_HIP(ks_->stft(p, sa, n_cus_, stream));
+    ENGINE_HIP(carry_last_hop(hist, x, F, H_, M_, S_, layout, mic_stride, (long)F * H_ * M_, stream));
+    if (!p.fused()) ENGINE_HIP(ks_->bins(p, ba, n_cus_, stream));
+    if (Phist_ > 0)  // keep the last Phist frames' spectra for the next call
+        ENGINE_HIP(hipMemcpy2DAsync(d_zhist_.get(), (size_t)Phist_ * frame_elems * zsz_, (const char *)Z + (size_t)F * frame_elems * zsz_,
+                                  (size_t)FT * frame_elems * zsz_, (size_t)Phist_ * frame_elems * zsz_, (size_t)S_,
+                                  hipMemcpyDeviceToDevice, stream));
+    if (p.istft != ChainIstft::kNone) ENGINE_HIP(ks_->istft(p, ia, n_cus_, stream));
+    tail_cur_ ^= 1;
+    if (p.tail == ChainTail::kSmooth4 || p.tail == ChainTail::kSmooth)
+        ENGINE_HIP(ks_->smooth(p, d_yraw_.get(), y, d_smooth_.get(), F, So_, stream));
+    else if (p.tail != ChainTail::kNone)
+        ENGINE_HIP(ks_->gsc_nlms(p, d_yraw_.get(), y, d_nlms_.get(), F * H_, S_, M_, cfg_, stream));
     return BF_OK;
 }
 

@@ -8,22 +8,21 @@
 namespace bf {
 namespace BF_NTAG {
 
-hipError_t launch_bins(const BinsArgs &a, int n_cus, hipStream_t s) {
-    hipError_t e = hipSuccess;
-    switch (a.cfg.algo) {
-        case BF_DAS:
-        case BF_PHASE: e = launch_pointwise(a, s); break;
-        case BF_MVDR:
-        case BF_LCMV: e = launch_mvdr_lcmv(a, n_cus, s); break;
-        case BF_PHASEMPF: e = launch_phasempf(a, n_cus, s); break;
-        case BF_GSS: e = launch_gss(a, n_cus, s); break;
-        case BF_GSC: e = launch_gsc_align(a, s); break;
-        case BF_MCRA: e = launch_mcra_node(a, s); break;
-        default: e = hipErrorInvalidValue; break;
+hipError_t launch_bins(const ChainPlan &p, const BinsArgs &a, int n_cus, hipStream_t s) {
+    hipError_t e = hipErrorInvalidValue;  // (kFusedTail: the fused front ran the per-bin stage)
+    switch (p.bins) {
+        case ChainBins::kFusedTail: break;
+        case ChainBins::kPointwise: e = launch_pointwise(p, a, s); break;
+        case ChainBins::kMpfMask: e = launch_mpf_mask(p, a, s); break;
+        case ChainBins::kMcra: e = launch_mcra_node(a, s); break;
+        case ChainBins::kGscAlign: e = launch_gsc_align(a, s); break;
+        case ChainBins::kMvdrFast:
+        case ChainBins::kCov2d:
+        case ChainBins::kMvdrLcmv: e = launch_mvdr_lcmv(p, a, n_cus, s); break;
+        case ChainBins::kGss:
+        case ChainBins::kGssLane: e = launch_gss(p, a, s); break;
     }
-    if (e != hipSuccess) return e;
-    if (a.spectrum) e = launch_expand_spectrum(a.Yh, a.spectrum, (long)a.n_streams * a.n_frames, s);
-    return e;
+    return e != hipSuccess ? e : launch_bins_end(p, a, s);
 }
 
 }  // namespace BF_NTAG
@@ -36,7 +35,4 @@ const KernelSet *BF_CAT2(kernel_set_n, BF_NFFT)() {
     return &ks;
 }
 
-namespace BF_NTAG {
-
-}  // namespace BF_NTAG
 }  // namespace bf

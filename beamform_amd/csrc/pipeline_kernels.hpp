@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/bfcore.h"
+#include "chain_plan.hpp"
 #include "das_f64_plan.hpp"
 #include "geometry.hpp"
 
@@ -101,8 +102,8 @@ struct IstftArgs {
     const float *tail_in;  // [stream][hop]
     float *tail_out;
     const f64x2 *tw;
-    const f32x2 *tw32;     // non-null: backward FFT in fp32, one frame per transform (istft32_kernel; N = 1024 only)
-    const f64x2 *tw_w64 = nullptr;  // non-null (N = 1024): twiddle_table_w64_rot, the fp64 backward transform runs istft_w64_kernel
+    const f32x2 *tw32;     // twiddle_table_32x32 in fp32: istft32_kernel (N = 1024)
+    const f64x2 *tw_w64 = nullptr;  // twiddle_table_w64_rot: istft_w64_kernel (N = 1024)
     float *frames;         // N != 1024: [stream][n_frames][N] windowed frames (generic kernel), overlap-added by a second pass
     const double *win;
     long n_frames;
@@ -161,41 +162,44 @@ hipError_t enqueue_das_f64(DasF64Args a, const DasF64Launch &d, float *scratch, 
 size_t das_f64_sched_ws_bytes();
 
 #ifdef BF_NFFT
+// Every launcher carries out its stage of a ChainPlan (chain_plan.hpp): the plan names the kernel and its template arguments, the launcher
+// maps them to an instantiation and computes the launch geometry.
 namespace BF_NTAG {
-hipError_t launch_stft(const StftArgs &a, int n_cus, hipStream_t s);
-hipError_t launch_bins(const BinsArgs &a, int n_cus, hipStream_t s);
-// stft + per-bin stage in one launch for the nodes without a frame history (das fp64, phase, phasempf; N = 1024, <= 8 mics,
-// one look direction): the spectra stay in LDS.  hipErrorNotSupported = run launch_stft + launch_bins instead.  mask_kernels.hip
-hipError_t launch_stft_bins_fused(const StftArgs &a, const BinsArgs &b, int n_cus, hipStream_t s);
+hipError_t launch_stft(const ChainPlan &p, const StftArgs &a, int n_cus, hipStream_t s);
+hipError_t launch_bins(const ChainPlan &p, const BinsArgs &a, int n_cus, hipStream_t s);
+// stft + per-bin stage in one launch for the nodes without a frame history (das fp64, phase, phasempf; N = 128 ... 2048, <= 8 mics,
+// one look direction): the spectra stay in LDS.  mask_kernels.hip
+hipError_t launch_stft_bins_fused(const ChainPlan &p, const StftArgs &a, const BinsArgs &b, int n_cus, hipStream_t s);
 // per-node launchers behind launch_bins (one translation unit per kernel family)
-hipError_t launch_pointwise(const BinsArgs &a, hipStream_t s);              // das (fp64), phase: mask_kernels.hip
-hipError_t launch_phasempf(const BinsArgs &a, int n_cus, hipStream_t s);    // mask_kernels.hip
-hipError_t launch_mcra_node(const BinsArgs &a, hipStream_t s);              // mask_kernels.hip
-hipError_t launch_mvdr_lcmv(const BinsArgs &a, int n_cus, hipStream_t s);   // cov_kernels.hip
-hipError_t launch_gss(const BinsArgs &a, int n_cus, hipStream_t s);         // gsc_gss_kernels.hip
-hipError_t launch_gsc_align(const BinsArgs &a, hipStream_t s);              // gsc_gss_kernels.hip
+hipError_t launch_pointwise(const ChainPlan &p, const BinsArgs &a, hipStream_t s);              // das (fp64), phase: mask_kernels.hip
+hipError_t launch_mpf_mask(const ChainPlan &p, const BinsArgs &a, hipStream_t s);               // phasempf: mask_kernels.hip
+hipError_t launch_mcra_node(const BinsArgs &a, hipStream_t s);                                  // mask_kernels.hip
+hipError_t launch_mvdr_lcmv(const ChainPlan &p, const BinsArgs &a, int n_cus, hipStream_t s);   // cov_kernels.hip
+hipError_t launch_gss(const ChainPlan &p, const BinsArgs &a, hipStream_t s);                    // gsc_gss_kernels.hip
+hipError_t launch_gsc_align(const BinsArgs &a, hipStream_t s);                                  // gsc_gss_kernels.hip
+// what follows the per-bin kernel on the chained and on the fused route: phasempf's recursion over the frames, the spectrum dump.  mask_kernels.hip
+hipError_t launch_bins_end(const ChainPlan &p, const BinsArgs &a, hipStream_t s);
 hipError_t launch_expand_spectrum(const f64x2 *Yh, f64x2 *spectrum, long frames, hipStream_t s);  // stft_istft.hip
-hipError_t launch_istft(const IstftArgs &a, int n_cus, hipStream_t s);
+hipError_t launch_istft(const ChainPlan &p, const IstftArgs &a, int n_cus, hipStream_t s);
 // gsc.cpp:120-181: the sample-serial float32 NLMS sidelobe canceller over the phase-aligned microphone signals.
 // aligned = [stream][mic][n_samples] (ISTFT output of the align pass), y = [stream][n_samples],
 // state = [stream][(2*(M-1) + 1) * filter_size] floats: block_matrix rows, filter rows, last_outputs (reference order).
-hipError_t launch_gsc_nlms(const float *aligned, float *y, float *state, long n_samples, int n_streams, int n_mics,
+hipError_t launch_gsc_nlms(const ChainPlan &p, const float *aligned, float *y, float *state, long n_samples, int n_streams, int n_mics,
                            const bf_config &cfg, hipStream_t s);
 // phasempf.cpp:331-334: moving average over the output samples, state = last 63 raw samples
-hipError_t launch_smooth(const float *yraw, float *y, double *state, long n_frames, int n_streams, int smooth_size,
-                         hipStream_t s);
+hipError_t launch_smooth(const ChainPlan &p, const float *yraw, float *y, double *state, long n_frames, int n_streams, hipStream_t s);
 }  // namespace BF_NTAG
 #endif
 
 // What the host pipeline calls: the launchers of one FFT size.
 struct KernelSet {
     int nfft;
-    hipError_t (*stft)(const StftArgs &, int, hipStream_t);
-    hipError_t (*bins)(const BinsArgs &, int, hipStream_t);
-    hipError_t (*stft_bins)(const StftArgs &, const BinsArgs &, int, hipStream_t);
-    hipError_t (*istft)(const IstftArgs &, int, hipStream_t);
-    hipError_t (*smooth)(const float *, float *, double *, long, int, int, hipStream_t);
-    hipError_t (*gsc_nlms)(const float *, float *, float *, long, int, int, const bf_config &, hipStream_t);
+    hipError_t (*stft)(const ChainPlan &, const StftArgs &, int, hipStream_t);
+    hipError_t (*bins)(const ChainPlan &, const BinsArgs &, int, hipStream_t);
+    hipError_t (*stft_bins)(const ChainPlan &, const StftArgs &, const BinsArgs &, int, hipStream_t);
+    hipError_t (*istft)(const ChainPlan &, const IstftArgs &, int, hipStream_t);
+    hipError_t (*smooth)(const ChainPlan &, const float *, float *, double *, long, int, hipStream_t);
+    hipError_t (*gsc_nlms)(const ChainPlan &, const float *, float *, float *, long, int, int, const bf_config &, hipStream_t);
 };
 const KernelSet *kernel_set_n128();
 const KernelSet *kernel_set_n256();

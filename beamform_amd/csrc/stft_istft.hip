@@ -3,7 +3,6 @@
 
 #include "launch_trace.hpp"
 #include "bins_common.hpp"
-#include "switches.hpp"
 #include "fft_small.hpp"
 #if BF_NFFT == 1024
 #include "w64_f64_dev.hpp"
@@ -1170,71 +1169,43 @@ __global__ void smooth_state_kernel(const float *yraw, double *state, long n, in
 
 }  // namespace
 
-#if BF_NFFT == 1024
-hipError_t launch_stft(const StftArgs &a, int n_cus, hipStream_t s) {
-    const long np = (a.n_fft_mics + 1) / 2;
-    // 256 threads, twiddles in LDS: a 512-thread block spills (44 VGPRs) and twiddles read from global memory cost 40 % (measured)
-    constexpr int nb = 256, halves = nb / 32;
-    // frames per run: one run per half-wavefront slot (one block per CU) when the batch is long enough -- the first frame of a
-    // run fetches its leading hop a second time (1/run_len of the input)
-    StftArgs b = a;
-    const long slots = (long)n_cus * halves;  // (1 / 2 / 4 / 8 runs per slot measured: 0.713 / 0.720 / 0.732 / 0.739 ms)
-    long L = ((long)a.n_streams * a.n_frames * np + slots - 1) / slots;
-    if (L < 1) L = 1;
-    if (L > 256) L = 256;
-    b.run_len = (int)L;
-    const long total = (long)a.n_streams * ((a.n_frames + L - 1) / L) * np;
-    long blocks = (total + halves - 1) / halves;
-    const long cap = (long)n_cus * 4;
-    if (blocks > cap) blocks = cap;
-    if (a.layout == 0) {
-        if (a.z48) BF_LAUNCH((stft_kernel<0, true>), dim3((unsigned)blocks), dim3(nb), 0, s, b);
-        else BF_LAUNCH((stft_kernel<0, false>), dim3((unsigned)blocks), dim3(nb), 0, s, b);
-    } else {
-        if (a.z48) BF_LAUNCH((stft_kernel<1, true>), dim3((unsigned)blocks), dim3(nb), 0, s, b);
-        else BF_LAUNCH((stft_kernel<1, false>), dim3((unsigned)blocks), dim3(nb), 0, s, b);
-    }
-    return hipGetLastError();
-}
+// the layout x z48 instantiations of one STFT kernel family, `blocks` blocks of 256 threads on the arguments b
+#define BF_STFT_GO(K_)                                                                       \
+    do {                                                                                     \
+        if (p.layout == 0) {                                                                 \
+            if (p.z48) BF_LAUNCH((K_<0, true>), dim3((unsigned)blocks), dim3(256), 0, s, b); \
+            else BF_LAUNCH((K_<0, false>), dim3((unsigned)blocks), dim3(256), 0, s, b);      \
+        } else {                                                                             \
+            if (p.z48) BF_LAUNCH((K_<1, true>), dim3((unsigned)blocks), dim3(256), 0, s, b); \
+            else BF_LAUNCH((K_<1, false>), dim3((unsigned)blocks), dim3(256), 0, s, b);      \
+        }                                                                                    \
+    } while (0)
 
-hipError_t launch_istft(const IstftArgs &a, int n_cus, hipStream_t s) {
-    if (a.tw32 != nullptr) {  // fp32 backward transform, one frame per FFT
-        // two blocks per CU are resident (213-228 VGPRs): one chunk per half-wavefront slot = one round; every chunk recomputes one
-        // warm-up frame.  Measured per 65 536 frames: x1 0.181, x2 0.127, x3 0.160 (round 2's value), x4 0.134, x8 0.148 ms
-        long slots = (long)n_cus * kI32Halves * 2 / a.n_streams;
-        if (slots < 1) slots = 1;
-        long cps = slots < a.n_frames ? slots : a.n_frames;
-        const long fpc = (a.n_frames + cps - 1) / cps;
-        cps = (a.n_frames + fpc - 1) / fpc;
-        const long chunks = cps * a.n_streams;
-        const dim3 grid((unsigned)((chunks + kI32Halves - 1) / kI32Halves));
-        if (!a.yh32) return hipErrorInvalidValue;  // (f64x2 rows go through istft_w64_kernel)
-        BF_LAUNCH(istft32_kernel, grid, dim3(kI32Block), 0, s, a, (int)fpc, (int)cps);
+hipError_t launch_stft(const ChainPlan &p, const StftArgs &a, int n_cus, hipStream_t s) {
+    const long np = (a.n_fft_mics + 1) / 2;
+    StftArgs b = a;
+#if BF_NFFT == 1024
+    if (p.front == ChainFront::kStft) {
+        // 256 threads, twiddles in LDS: a 512-thread block spills (44 VGPRs) and twiddles read from global memory cost 40 % (measured)
+        constexpr int halves = 256 / 32;
+        // frames per run: one run per half-wavefront slot (one block per CU) when the batch is long enough -- the first frame of a
+        // run fetches its leading hop a second time (1/run_len of the input)
+        const long slots = (long)n_cus * halves;  // (1 / 2 / 4 / 8 runs per slot measured: 0.713 / 0.720 / 0.732 / 0.739 ms)
+        long L = ((long)a.n_streams * a.n_frames * np + slots - 1) / slots;
+        if (L < 1) L = 1;
+        if (L > 256) L = 256;
+        b.run_len = (int)L;
+        const long total = (long)a.n_streams * ((a.n_frames + L - 1) / L) * np;
+        long blocks = (total + halves - 1) / halves;
+        const long cap = (long)n_cus * 4;
+        if (blocks > cap) blocks = cap;
+        BF_STFT_GO(stft_kernel);
         return hipGetLastError();
     }
-    const long pairs = (a.n_frames + 1) / 2;
-    if (a.tw_w64 == nullptr) return hipErrorInvalidValue;
-    // one run per wavefront slot (2 blocks x 4 wavefronts per CU), every run recomputes one warm-up frame
-    long slots = (long)n_cus * kIw64Waves * 2 / a.n_streams;
-    if (slots < 1) slots = 1;
-    long rps = slots < pairs ? slots : pairs;
-    const long ppr = (pairs + rps - 1) / rps;
-    rps = (pairs + ppr - 1) / ppr;
-    const long runs = rps * a.n_streams;
-    const dim3 grid((unsigned)((runs + kIw64Waves - 1) / kIw64Waves));
-    if (a.yh_lo > 0 || a.yh_hi < a.yh_lo) BF_LAUNCH(istft_w64_kernel<true>, grid, dim3(kIw64Block), 0, s, a, (int)ppr, (int)rps);  // band-limited rows (mvdr / lcmv)
-    else BF_LAUNCH(istft_w64_kernel<false>, grid, dim3(kIw64Block), 0, s, a, (int)ppr, (int)rps);
-    return hipGetLastError();
-}
-
 #else
-hipError_t launch_stft(const StftArgs &a, int n_cus, hipStream_t s) {
 #if BF_NFFT == 128 || BF_NFFT == 256 || BF_NFFT == 512
-    // the in-register kernel (BF_STFT_SMALL=0: the generic one, for A/B runs)
-    if (switches().stft_small) {
+    if (p.front == ChainFront::kStftSmall) {  // the in-register kernel
         constexpr int halves = 8;
-        const long np = (a.n_fft_mics + 1) / 2;
-        StftArgs b = a;
         const long slots = (long)n_cus * halves * 2;  // two rounds of runs per half-wavefront slot
         long L = ((long)a.n_streams * a.n_frames * np + slots - 1) / slots;
         L = ((L + kG - 1) / kG) * kG;  // whole groups of frames
@@ -1244,22 +1215,13 @@ hipError_t launch_stft(const StftArgs &a, int n_cus, hipStream_t s) {
         const long items = (long)a.n_streams * ((a.n_frames + L - 1) / L) * np;
         long blocks = (items + halves - 1) / halves;
         if (blocks > (long)n_cus * 4) blocks = (long)n_cus * 4;
-        if (a.layout == 0) {
-            if (a.z48) BF_LAUNCH((stft_small_kernel<0, true>), dim3((unsigned)blocks), dim3(256), 0, s, b);
-            else BF_LAUNCH((stft_small_kernel<0, false>), dim3((unsigned)blocks), dim3(256), 0, s, b);
-        } else {
-            if (a.z48) BF_LAUNCH((stft_small_kernel<1, true>), dim3((unsigned)blocks), dim3(256), 0, s, b);
-            else BF_LAUNCH((stft_small_kernel<1, false>), dim3((unsigned)blocks), dim3(256), 0, s, b);
-        }
+        BF_STFT_GO(stft_small_kernel);
         return hipGetLastError();
     }
 #endif
 #if BF_NFFT == 2048
-    // one 2048-point transform per full wavefront (BF_STFT_SPLIT=0: the generic kernel, for cross-checks)
-    if (switches().stft_split) {
+    if (p.front == ChainFront::kStftWave2048) {  // one 2048-point transform per full wavefront
         constexpr int waves = 4;
-        const long np = (a.n_fft_mics + 1) / 2;
-        StftArgs b = a;
         const long slots = (long)n_cus * waves * 2;
         long L = ((long)a.n_streams * a.n_frames * np + slots - 1) / slots;
         if (L > 256) L = 256;
@@ -1268,83 +1230,110 @@ hipError_t launch_stft(const StftArgs &a, int n_cus, hipStream_t s) {
         const long items = (long)a.n_streams * ((a.n_frames + L - 1) / L) * np;
         long blocks = (items + waves - 1) / waves;
         if (blocks > (long)n_cus * 4) blocks = (long)n_cus * 4;
-        if (a.layout == 0) {
-            if (a.z48) BF_LAUNCH((stft_wave2048_kernel<0, true>), dim3((unsigned)blocks), dim3(256), 0, s, b);
-            else BF_LAUNCH((stft_wave2048_kernel<0, false>), dim3((unsigned)blocks), dim3(256), 0, s, b);
-        } else {
-            if (a.z48) BF_LAUNCH((stft_wave2048_kernel<1, true>), dim3((unsigned)blocks), dim3(256), 0, s, b);
-            else BF_LAUNCH((stft_wave2048_kernel<1, false>), dim3((unsigned)blocks), dim3(256), 0, s, b);
-        }
+        BF_STFT_GO(stft_wave2048_kernel);
         return hipGetLastError();
     }
 #endif
-    const long total = (long)a.n_streams * a.n_frames * ((a.n_fft_mics + 1) / 2);
-    long blocks = total < (long)n_cus * 8 ? total : (long)n_cus * 8;
-    if (blocks < 1) blocks = 1;
-    if (a.layout == 0)
-        BF_LAUNCH(stft_generic_kernel<0>, dim3((unsigned)blocks), dim3(kGenBlock), 0, s, a);
-    else
-        BF_LAUNCH(stft_generic_kernel<1>, dim3((unsigned)blocks), dim3(kGenBlock), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_istft(const IstftArgs &a, int n_cus, hipStream_t s) {
-#if BF_NFFT == 128 || BF_NFFT == 256 || BF_NFFT == 512
-    // backward transform, window and overlap-add in registers (BF_STFT_SMALL=0: the generic pair of kernels, for A/B runs)
-    if (switches().stft_small && !a.yh32) {
-        constexpr int halves = 8;
-        const long slots = (long)n_cus * halves;
-        long L = ((long)a.n_streams * a.n_frames + slots - 1) / slots;
-        L = ((L + kG - 1) / kG) * kG;  // whole groups of frames
-        if (L < 4 * kG) L = 4 * kG;    // a run recomputes one group
-        const long items = (long)a.n_streams * ((a.n_frames + L - 1) / L);
-        long blocks = (items + halves - 1) / halves;
-        BF_LAUNCH(istft_small_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, (int)L);
+    if (p.front == ChainFront::kStftGeneric) {
+        const long total = (long)a.n_streams * a.n_frames * np;
+        long blocks = total < (long)n_cus * 8 ? total : (long)n_cus * 8;
+        if (blocks < 1) blocks = 1;
+        if (p.layout == 0)
+            BF_LAUNCH(stft_generic_kernel<0>, dim3((unsigned)blocks), dim3(kGenBlock), 0, s, b);
+        else
+            BF_LAUNCH(stft_generic_kernel<1>, dim3((unsigned)blocks), dim3(kGenBlock), 0, s, b);
         return hipGetLastError();
     }
+#endif
+    return hipErrorInvalidValue;  // a front this size does not have: the plan never names one
+}
+#undef BF_STFT_GO
+
+hipError_t launch_istft(const ChainPlan &p, const IstftArgs &a, int n_cus, hipStream_t s) {
+    switch (p.istft) {
+#if BF_NFFT == 1024
+        case ChainIstft::kF32: {  // fp32 backward transform of f32x2 rows, one frame per FFT
+            // two blocks per CU are resident (213-228 VGPRs): one chunk per half-wavefront slot = one round; every chunk recomputes one
+            // warm-up frame.  Measured per 65 536 frames: x1 0.181, x2 0.127, x3 0.160 (round 2's value), x4 0.134, x8 0.148 ms
+            long slots = (long)n_cus * kI32Halves * 2 / a.n_streams;
+            if (slots < 1) slots = 1;
+            long cps = slots < a.n_frames ? slots : a.n_frames;
+            const long fpc = (a.n_frames + cps - 1) / cps;
+            cps = (a.n_frames + fpc - 1) / fpc;
+            const long chunks = cps * a.n_streams;
+            const dim3 grid((unsigned)((chunks + kI32Halves - 1) / kI32Halves));
+            BF_LAUNCH(istft32_kernel, grid, dim3(kI32Block), 0, s, a, (int)fpc, (int)cps);
+            break;
+        }
+        case ChainIstft::kW64: {
+            const long pairs = (a.n_frames + 1) / 2;
+            // one run per wavefront slot (2 blocks x 4 wavefronts per CU), every run recomputes one warm-up frame
+            long slots = (long)n_cus * kIw64Waves * 2 / a.n_streams;
+            if (slots < 1) slots = 1;
+            long rps = slots < pairs ? slots : pairs;
+            const long ppr = (pairs + rps - 1) / rps;
+            rps = (pairs + ppr - 1) / ppr;
+            const long runs = rps * a.n_streams;
+            const dim3 grid((unsigned)((runs + kIw64Waves - 1) / kIw64Waves));
+            if (p.band_rows) BF_LAUNCH(istft_w64_kernel<true>, grid, dim3(kIw64Block), 0, s, a, (int)ppr, (int)rps);  // band-limited rows (mvdr / lcmv)
+            else BF_LAUNCH(istft_w64_kernel<false>, grid, dim3(kIw64Block), 0, s, a, (int)ppr, (int)rps);
+            break;
+        }
+#else
+#if BF_NFFT == 128 || BF_NFFT == 256 || BF_NFFT == 512
+        case ChainIstft::kSmall: {  // backward transform, window and overlap-add in registers
+            constexpr int halves = 8;
+            const long slots = (long)n_cus * halves;
+            long L = ((long)a.n_streams * a.n_frames + slots - 1) / slots;
+            L = ((L + kG - 1) / kG) * kG;  // whole groups of frames
+            if (L < 4 * kG) L = 4 * kG;    // a run recomputes one group
+            const long items = (long)a.n_streams * ((a.n_frames + L - 1) / L);
+            long blocks = (items + halves - 1) / halves;
+            BF_LAUNCH(istft_small_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, (int)L);
+            break;
+        }
 #endif
 #if BF_NFFT == 2048
-    // one FFT-1024 per frame, window and overlap-add in registers (BF_STFT_SPLIT=0: the generic pair of kernels, for A/B runs)
-    if (switches().stft_split && !a.yh32) {
-        constexpr int halves = 8;
-        const long slots = (long)n_cus * halves;
-        long L = ((long)a.n_streams * a.n_frames + slots - 1) / slots;
-        if (L < 8) L = 8;  // a run recomputes one frame
-        const long items = (long)a.n_streams * ((a.n_frames + L - 1) / L);
-        BF_LAUNCH(istft_split_kernel, dim3((unsigned)((items + halves - 1) / halves)), dim3(256), 0, s, a, (int)L);
-        return hipGetLastError();
-    }
+        case ChainIstft::kSplit: {  // one FFT-1024 per frame, window and overlap-add in registers
+            constexpr int halves = 8;
+            const long slots = (long)n_cus * halves;
+            long L = ((long)a.n_streams * a.n_frames + slots - 1) / slots;
+            if (L < 8) L = 8;  // a run recomputes one frame
+            const long items = (long)a.n_streams * ((a.n_frames + L - 1) / L);
+            BF_LAUNCH(istft_split_kernel, dim3((unsigned)((items + halves - 1) / halves)), dim3(256), 0, s, a, (int)L);
+            break;
+        }
 #endif
-    if (a.frames == nullptr) return hipErrorInvalidValue;
-    const long total = (long)a.n_streams * a.n_frames;
-    long blocks = total < (long)n_cus * 8 ? total : (long)n_cus * 8;
-    if (blocks < 1) blocks = 1;
-    BF_LAUNCH(istft_generic_kernel, dim3((unsigned)blocks), dim3(kGenBlock), 0, s, a);
-    const long samples = total * kHop;
-    BF_LAUNCH(ola_generic_kernel, dim3((unsigned)((samples + 255) / 256)), dim3(256), 0, s, a);
+        case ChainIstft::kGeneric: {  // windowed frames through a.frames, overlap-added by a second pass
+            const long total = (long)a.n_streams * a.n_frames;
+            long blocks = total < (long)n_cus * 8 ? total : (long)n_cus * 8;
+            if (blocks < 1) blocks = 1;
+            BF_LAUNCH(istft_generic_kernel, dim3((unsigned)blocks), dim3(kGenBlock), 0, s, a);
+            const long samples = total * kHop;
+            BF_LAUNCH(ola_generic_kernel, dim3((unsigned)((samples + 255) / 256)), dim3(256), 0, s, a);
+            break;
+        }
+#endif
+        default: return hipErrorInvalidValue;  // a backward transform this size does not have: the plan never names one
+    }
     return hipGetLastError();
 }
 
-#endif
-
-hipError_t launch_smooth(const float *yraw, float *y, double *state, long n_frames, int n_streams, int smooth_size,
-                         hipStream_t s) {
+hipError_t launch_smooth(const ChainPlan &p, const float *yraw, float *y, double *state, long n_frames, int n_streams, hipStream_t s) {
     const long n = n_frames * kHop;
     const long total = n * n_streams;
-    const bool al = ((reinterpret_cast<size_t>(yraw) | reinterpret_cast<size_t>(y)) & 15) == 0 && (n & 3) == 0;
     const dim3 g4((unsigned)((total / 4 + 255) / 256));
 #define BF_SM4(SZ_) BF_LAUNCH((smooth4_kernel<SZ_>), g4, dim3(256), 0, s, yraw, y, state, n, n_streams)
-    if (al && smooth_size == 1) BF_SM4(1);
-    else if (al && smooth_size == 2) BF_SM4(2);
-    else if (al && smooth_size == 3) BF_SM4(3);
-    else if (al && smooth_size == 4) BF_SM4(4);
-    else if (al && smooth_size == 5) BF_SM4(5);
-    else if (al && smooth_size == 6) BF_SM4(6);
-    else if (al && smooth_size == 7) BF_SM4(7);
-    else if (al && smooth_size == 8) BF_SM4(8);
-    else
-        BF_LAUNCH(smooth_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, yraw, y, state, n, n_streams,
-                           smooth_size);
+    if (p.tail == ChainTail::kSmooth)
+        BF_LAUNCH(smooth_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, yraw, y, state, n, n_streams, p.t0);
+    else if (p.t0 == 1) BF_SM4(1);
+    else if (p.t0 == 2) BF_SM4(2);
+    else if (p.t0 == 3) BF_SM4(3);
+    else if (p.t0 == 4) BF_SM4(4);
+    else if (p.t0 == 5) BF_SM4(5);
+    else if (p.t0 == 6) BF_SM4(6);
+    else if (p.t0 == 7) BF_SM4(7);
+    else BF_SM4(8);
 #undef BF_SM4
     BF_LAUNCH(smooth_state_kernel, dim3((unsigned)((64 * n_streams + 255) / 256)), dim3(256), 0, s, yraw, state, n,
                        n_streams);

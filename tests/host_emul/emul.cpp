@@ -609,3 +609,17 @@ extern "C" void emul_das_fused_plan(int hop, int layout, int n_mics, int n_strea
     const long v[9] = {(long)d.kernel, d.npl, d.unr, d.group, d.frames_per_chunk, d.chunks_per_stream, (long)d.blocks, d.zero_run_heads, d.group_tables};
     memcpy(out, v, sizeof(v));
 }
+
+// ---- what a batch of the STFT -> per-bin -> ISTFT chain launches (csrc/chain_plan.hpp) -----------------------------------------------------
+#include "../../beamform_amd/csrc/chain_plan.hpp"
+// in[23] = ChainShape's members in order; out[25] = ChainPlan's members in order (enums as integers, sizes last)
+extern "C" void emul_chain_plan(const long *in, long *out) {
+    const bf::ChainShape c{(int)in[0], (int)in[1], (int)in[2], (int)in[3], (int)in[4], (int)in[5], (int)in[6], (int)in[7], (int)in[8], in[9] != 0,
+                           in[10], (int)in[11], (int)in[12], (int)in[13], (int)in[14], (int)in[15], in[16] != 0, (int)in[17], in[18] != 0,
+                           in[19] != 0, in[20] != 0, (int)in[21], in[22] != 0};
+    const bf::ChainPlan p = bf::chain_decide(c);
+    const long v[25] = {p.algo, p.layout, (long)p.front, p.z48, (long)p.bins, p.mp, p.km, p.wps, (long)p.rec, p.expand, (long)p.istft, (long)p.tail,
+                        p.t0, p.t1, p.t2, p.yh32, p.mpf32, p.band_rows, p.yh_lo, p.yh_hi, (long)p.z_bytes, (long)p.yh_bytes, (long)p.yraw_elems,
+                        (long)p.frames_elems, p.fused()};
+    memcpy(out, v, sizeof(v));
+}

@@ -13,15 +13,15 @@ std::atomic<long> g_launches{0};
 
 namespace bf {
 
-static hipError_t launch_stft(const StftArgs &, int, hipStream_t) { return hipSuccess; }
-static hipError_t launch_istft(const IstftArgs &, int, hipStream_t) { return hipSuccess; }
-static hipError_t launch_smooth(const float *, float *, double *, long, int, int, hipStream_t) { return hipSuccess; }
-static hipError_t launch_gsc_nlms(const float *, float *, float *, long, int, int, const bf_config &, hipStream_t) { return hipSuccess; }
+static hipError_t launch_stft(const ChainPlan &, const StftArgs &, int, hipStream_t) { return hipSuccess; }
+static hipError_t launch_istft(const ChainPlan &, const IstftArgs &, int, hipStream_t) { return hipSuccess; }
+static hipError_t launch_smooth(const ChainPlan &, const float *, float *, double *, long, int, hipStream_t) { return hipSuccess; }
+static hipError_t launch_gsc_nlms(const ChainPlan &, const float *, float *, float *, long, int, int, const bf_config &, hipStream_t) { return hipSuccess; }
 
 // The per-bin stage: the batch must see ONE consistent {column count, steering table}.  The table is laid out
 // [dir][col][mic][bin] with kp1 columns; every uploaded steering entry of mic >= 1 has modulus 1, memory that was never
 // uploaded reads 0 (the stub's hipMalloc zero-fills).
-static hipError_t launch_bins(const BinsArgs &a, int, hipStream_t) {
+static hipError_t launch_bins(const ChainPlan &, const BinsArgs &a, int, hipStream_t) {
     g_launches++;
     const int M = a.n_mics, kp1 = a.kp1;
     if (a.steer_dir_stride != (long)kp1 * M * 1024) g_inconsistent++;
@@ -35,8 +35,8 @@ static hipError_t launch_bins(const BinsArgs &a, int, hipStream_t) {
     return hipSuccess;
 }
 
-// the fused STFT + per-bin launcher declines: the harness exercises the two-kernel chain's host logic
-static hipError_t launch_stft_bins(const StftArgs &, const BinsArgs &, int, hipStream_t) { return hipErrorNotSupported; }
+// the fused STFT + per-bin launcher (the chain decision itself is pure host arithmetic, chain_plan.hpp): the per-bin stage's checks
+static hipError_t launch_stft_bins(const ChainPlan &p, const StftArgs &, const BinsArgs &b, int n, hipStream_t s) { return launch_bins(p, b, n, s); }
 
 // the harness runs at hop 512; the other sizes share the same host code
 static const KernelSet g_stub_set = {1024, &launch_stft, &launch_bins, &launch_stft_bins, &launch_istft, &launch_smooth, &launch_gsc_nlms};

@@ -415,3 +415,143 @@ def test_das_fused_switches_route_to_the_cross_check_kernels(emul_lib):
     # the threshold itself: BF_DAS_SHARED_DIRS = the smallest direction count that shares the transforms
     for thr, dirs, want in ((6, 5, K_REGS), (6, 6, K_DIRS), (2, 2, K_DIRS), (9, 8, K_REGS), (-1, 8, K_REGS)):
         assert _das_fused_plan(emul_lib, 512, 0, 8, 1, dirs, False, 96, 256, das_shared_dirs=thr)["kernel"] == want, (thr, dirs)
+
+
+# ---- the launch plan of the STFT -> per-bin -> ISTFT chain (csrc/chain_plan.hpp through emul_chain_plan) ---------------------------------
+from chain_plan_util import (ALGO, CHAIN_SWITCHES, NODES, chain_kernels, chain_plan, dispatch_rows, row_plan)   # noqa: E402
+
+
+def test_chain_plan_names_the_kernels_of_the_dispatch_table(emul_lib):
+    """Every chain row of docs/DISPATCH.md (traced on a GPU: 96 frames, 256 CUs, default switches, make_params' defaults, 1 or 64 streams):
+    the plan's kernel list, formatted as the table prints it, equals the row exactly and in order.  Left out, and nothing else: fused fp32
+    das, the one-launch das in double (das_f64_*), and shapes the node refuses."""
+    compared, skipped = 0, []
+    for row in dispatch_rows():
+        node, kernels = row[0], row[6]
+        if node == "das (fp32)" or kernels.startswith("das_f64_") or kernels.startswith("(refused:"):
+            skipped.append(row)
+            continue
+        d, nfft = row_plan(emul_lib, row, 96, 256)
+        assert " + ".join(chain_kernels(d, nfft)) == kernels, (row, d)
+        compared += 1
+    assert compared >= 80, compared
+    assert all(r[0] == "das (fp32)" or r[6].startswith(("das_f64_", "(refused:")) for r in skipped)
+    assert compared + len(skipped) == len(dispatch_rows())
+
+
+def test_chain_plan_is_consistent_on_random_shapes(emul_lib):
+    """Seeded random shapes over all eight nodes, every hop, 1-32 microphones (gsc <= 16), 1-16 columns, both precisions, dump on / off,
+    1-300 streams, 1-304 CUs: the template arguments cover the shape, every kernel appears only where it is built for, and the workspace
+    sizes are the pipeline's expressions (written out here on their own)."""
+    rng = np.random.default_rng(23)
+    seen = set()
+    for i in range(480):
+        algo = NODES[i % 8]
+        a = ALGO[algo]
+        hop = int(2 ** rng.integers(6, 13))
+        N = 2 * hop
+        M = int(rng.integers(1, 17 if algo == "gsc" else 33))
+        kp1 = int(rng.integers(1, 17)) if algo in ("lcmv", "gss") else 1
+        mixed, dump = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
+        S, cus, F = int(rng.integers(1, 301)), int(rng.integers(1, 305)), int(rng.integers(1, 200))
+        dirs = int(rng.integers(1, 5)) if algo != "gsc" and i % 3 == 0 else 1
+        fs, sz, P = int(rng.integers(1, 257)), int(rng.integers(1, 65)), int(rng.integers(1, 65))
+        blo = int(rng.integers(1, 40))
+        bhi = int(rng.integers(blo, N // 2 - 2))
+        al = bool(rng.integers(0, 4))
+        d = chain_plan(emul_lib, algo=a, n_fft=N, layout=int(rng.integers(0, 2)), n_mics=M, n_streams=S, n_dirs=dirs, kp1=kp1, past_windows=P,
+                       precision=int(mixed), dump=dump, n_frames=F, n_cus=cus, gsc_filter_size=fs, smooth_size=sz, band_yh_lo=blo, band_yh_hi=bhi,
+                       aligned16=al)
+        ctx = ((algo, hop, M, kp1, mixed, dump, S, cus, F, dirs, fs, sz, P, al), d)
+        names = chain_kernels(d, N)
+        seen.update(n.split("::")[1].split("<")[0] for n in names)
+        cov, gsc, mpf = algo in ("mvdr", "lcmv"), algo == "gsc", algo == "phasempf"
+        D = M if gsc else dirs
+        So, MF = S * D, (1 if algo == "mcra" else M)
+        # template arguments cover the shape
+        bins = d["bins"]
+        if bins == 6:
+            assert 8 < M <= 16, ctx      # cov2d_kernel: 4 x 4 lanes per problem, no MP argument
+        elif algo not in ("mcra", "gsc"):
+            assert d["mp"] >= M, ctx
+        if algo in ("mvdr", "lcmv", "gss"):
+            assert d["km"] >= kp1, ctx
+        if gsc:
+            if d["tail"] == 5:
+                assert d["t0"] * d["t1"] >= M - 1 and 64 * d["t2"] >= fs, ctx      # (filter sizes stop at 256 = 64 * 4)
+            else:
+                assert d["t0"] >= M - 1 and 64 * d["t1"] >= fs, ctx
+        # who may appear where
+        is32 = d["istft"] == 2
+        assert is32 == bool(d["yh32"] or d["mpf32"]), ctx
+        if is32:
+            assert N == 1024 and mixed and not dump and not gsc, ctx
+        assert bool(d["z48"]) == (cov and mixed), ctx
+        rec_istft = d["rec"] == 2
+        if rec_istft:
+            assert d["istft"] == 0 and not d["mpf32"] and mpf and N == 1024 and not dump and So * 4 >= cus, ctx
+        else:
+            assert d["istft"] != 0, ctx
+        assert (d["rec"] != 0) == mpf, ctx
+        if d["band_rows"] or (d["yh_lo"], d["yh_hi"]) != (0, N // 2 + 1):
+            assert cov and not dump and N == 1024 and (d["yh_lo"], d["yh_hi"]) == (blo, bhi), ctx
+        if d["fused"]:
+            assert algo in ("das", "phase", "phasempf") and M <= 8 and dirs == 1 and N <= 2048 and bins == 0, ctx
+        else:
+            assert bins != 0, ctx
+        assert bool(d["expand"]) == (dump and not gsc), ctx
+        assert (d["tail"] in (1, 2)) == mpf and (d["tail"] in (3, 4, 5)) == gsc, ctx
+        if d["tail"] == 1:
+            assert al and 1 <= sz <= 8 and d["t0"] == sz, ctx
+        # workspace sizes: the expressions of BinPipelineImpl::run_chain
+        NP, YS, zsz = (MF + 1) // 2, N // 2 + 4, (12 if cov and mixed else 16)
+        FT = (P if cov else 0) + F
+        z = S * F * 2 * 8 * 16 if d["fused"] else (S * FT + (512 if cov else 0)) * NP * N * zsz
+        assert d["z_bytes"] == z, ctx
+        assert d["yh_bytes"] == So * F * YS * (16 + (8 if mpf else 0)), ctx
+        assert d["yraw_elems"] == (So * F * hop if mpf or gsc else 0), ctx
+        assert d["frames_elems"] == (So * F * N if N != 1024 else 0), ctx
+    assert {"stft_kernel", "stft_small_kernel", "stft_wave2048_kernel", "stft_generic_kernel", "stft_bins_w64_kernel", "stft_bins_small_kernel",
+            "stft_bins_split_kernel", "pointwise_bins_kernel", "mpf_mask_kernel", "mcra_node_kernel", "gsc_align_kernel", "mvdr_fast_kernel",
+            "cov2d_kernel", "mvdr_lcmv_kernel", "gss_kernel", "gss_lane_kernel", "mpf_recursion_kernel", "mpf_rec_istft_kernel",
+            "istft_w64_kernel", "istft32_kernel", "istft_small_kernel", "istft_split_kernel", "istft_generic_kernel", "smooth4_kernel",
+            "smooth_kernel", "gsc_nlms_par_kernel", "gsc_nlms_mw_kernel", "expand_spectrum_kernel"} <= seen, seen
+
+
+def test_chain_switches_route_as_documented(emul_lib):
+    """Each switch away from its default: BF_FUSED_BINS=0 no fused front; BF_STFT_SMALL=0 / BF_STFT_SPLIT=0 the generic
+    STFT and ISTFT at their sizes and no effect on the fused front; BF_MVDR_GROUP=1 only mvdr_lcmv_kernel; BF_GSS_GROUP 0 / 1 the lane /
+    the group kernel; BF_GSC_SERIAL=1 gsc_nlms_kernel."""
+    def names(algo, hop=512, M=8, kp1=1, S=1, **sw):
+        d = chain_plan(emul_lib, algo=ALGO[algo], n_fft=2 * hop, n_mics=M, n_streams=S, kp1=kp1, n_frames=96, n_cus=256, band_yh_lo=3, band_yh_hi=341, **sw)
+        return [n.split("::")[1] for n in chain_kernels(d, 2 * hop)], d
+    for hop in (64, 128, 256, 512, 1024):
+        for algo in ("das", "phase", "phasempf"):
+            on, d_on = names(algo, hop)
+            off, d_off = names(algo, hop, fused_bins=0)
+            assert d_on["fused"] and on[0].startswith("stft_bins_") and not d_off["fused"], (hop, algo)
+            assert not any("stft_bins_" in n or "fused_tail" in n for n in off), (hop, algo, off)
+            assert d_off["z_bytes"] == 96 * 4 * 2 * hop * 16    # the packed spectra of four microphone pairs
+    for hop, sw in ((64, "stft_small"), (128, "stft_small"), (256, "stft_small"), (1024, "stft_split")):
+        base, _ = names("mvdr", hop)
+        off, _ = names("mvdr", hop, **{sw: 0})
+        assert base[0].startswith("stft_small_kernel" if hop < 512 else "stft_wave2048_kernel") and base[-1] == ("istft_small_kernel" if hop < 512 else "istft_split_kernel")
+        assert off[0] == "stft_generic_kernel<0>" and off[-2:] == ["istft_generic_kernel", "ola_generic_kernel"], (hop, off)
+        assert names("phase", hop, **{sw: 0})[0][0] == names("phase", hop)[0][0]              # the fused front has no generic twin ...
+        assert names("phase", hop, **{sw: 0})[0][-2:] == ["istft_generic_kernel", "ola_generic_kernel"]   # ... its backward transform has
+        other = "stft_split" if sw == "stft_small" else "stft_small"
+        assert names("mvdr", hop, **{other: 0})[0] == base                                    # the other sizes' switch leaves this one alone
+    assert names("mvdr", 512, stft_small=0, stft_split=0)[0] == names("mvdr", 512)[0]
+    for algo, kp1 in (("mvdr", 1), ("lcmv", 3)):
+        for M in (2, 3, 8, 12, 16, 24):
+            assert names(algo, 512, M, kp1, mvdr_group=1)[0][1].startswith("mvdr_lcmv_kernel<"), (algo, M)
+    assert names("mvdr", 512, 8)[0][1].startswith("mvdr_fast_kernel<") and names("mvdr", 512, 12)[0][1].startswith("cov2d_kernel<")
+    for S in (1, 64):
+        assert names("gss", 512, 8, 3, S, gss_group=0)[0][1] == "gss_lane_kernel<8, 4>"
+        assert names("gss", 512, 8, 3, S, gss_group=1)[0][1] == "gss_kernel<8, 4>"
+    assert names("gss", 512, 8, 3, 1)[0][1] == "gss_kernel<8, 4>" and names("gss", 512, 8, 3, 64)[0][1] == "gss_lane_kernel<8, 4>"
+    assert names("gss", 512, 12, 3, 64, gss_group=0)[0][1] == "gss_kernel<16, 4>"             # the lane kernel is built for up to 8 microphones
+    for M, want in ((2, "gsc_nlms_kernel<1, 2>"), (8, "gsc_nlms_kernel<7, 2>"), (16, "gsc_nlms_kernel<15, 2>")):
+        assert names("gsc", 512, M, gsc_serial=1)[0][-1] == want, M
+    assert names("gsc", 512, 2)[0][-1] == "gsc_nlms_par_kernel<1, 2>" and names("gsc", 512, 8)[0][-1] == "gsc_nlms_mw_kernel<8, 1, 2>"
+    assert set(CHAIN_SWITCHES) == {"fused_bins", "stft_small", "stft_split", "mvdr_group", "gss_group", "gsc_serial"}
