@@ -56,11 +56,12 @@ class BfConfig(C.Structure):
         ("device", C.c_int), ("n_streams", C.c_int), ("layout", C.c_int), ("das_impl", C.c_int), ("precision", C.c_int), ("n_dirs", C.c_int),
         ("gsc_use_vad", C.c_int), ("gsc_vad_threshold", C.c_double), ("gsc_mu0", C.c_double), ("gsc_mu_max", C.c_double),
         ("gsc_filter_size", C.c_int),
+        ("gss_out_sources", C.c_int),
     ]
 
 
 #: defaults of parameters added after the first golden fixtures were written (launch/gsc.launch:6-11)
-_LATER_KEYS = dict(gsc_use_vad=0, gsc_vad_threshold=0.1, gsc_mu0=0.0001, gsc_mu_max=0.1, gsc_filter_size=128)
+_LATER_KEYS = dict(gsc_use_vad=0, gsc_vad_threshold=0.1, gsc_mu0=0.0001, gsc_mu_max=0.1, gsc_filter_size=128, gss_out_sources=0)
 
 
 class BfError(RuntimeError):
@@ -389,8 +390,9 @@ def resampler_default_table():
 
 
 def config_from_params(p: dict, device: int = 0, n_streams: int = 1, layout: int = BF_PLANAR,
-                       das_impl: int = BF_DAS_F64, n_dirs: int = 1, precision: int = BF_PRECISION_REFERENCE) -> BfConfig:
-    """bf_config from a beamform_amd.params dict (launch defaults first, then overrides)."""
+                       das_impl: int = BF_DAS_F64, n_dirs: int = 1, precision: int = BF_PRECISION_REFERENCE,
+                       gss_out_sources: int = None) -> BfConfig:
+    """bf_config from a beamform_amd.params dict (launch defaults first, then overrides).  gss_out_sources: the dict's value unless given."""
     L = load()
     c = BfConfig()
     rc = L.bf_config_init(C.byref(c), ALGO_ID[p["algo"]])
@@ -409,8 +411,10 @@ def config_from_params(p: dict, device: int = 0, n_streams: int = 1, layout: int
               "mag_mult", "mag_threshold", "min_mag", "smooth_size", "mcra_alphaS", "mcra_alphaD", "mcra_alphaD2",
               "mcra_delta", "mcra_L", "mpf_alphaS", "mpf_eta", "mpf_rev_gamma", "mpf_rev_delta", "noise_floor",
               "out_only_noise", "out_only_mcra", "gsc_use_vad", "gsc_vad_threshold", "gsc_mu0", "gsc_mu_max",
-              "gsc_filter_size"):
+              "gsc_filter_size", "gss_out_sources"):
         setattr(c, k, p[k] if k in p else _LATER_KEYS[k])  # fixtures written before a key existed
+    if gss_out_sources is not None:
+        c.gss_out_sources = gss_out_sources
     c.device, c.n_streams, c.layout, c.das_impl, c.n_dirs = device, n_streams, layout, das_impl, n_dirs
     c.precision = precision
     return c
@@ -434,11 +438,14 @@ class Beamformer:
     """One beamformer node behind the C ABI (das|mvdr|lcmv|gss|phase|phasempf|mcra|gsc)."""
 
     def __init__(self, params: dict, device: int = 0, n_streams: int = 1, layout: int = BF_PLANAR,
-                 das_impl: int = BF_DAS_F64, n_dirs: int = 1, precision: int = BF_PRECISION_REFERENCE):
+                 das_impl: int = BF_DAS_F64, n_dirs: int = 1, precision: int = BF_PRECISION_REFERENCE, gss_out_sources: int = None):
+        """gss_out_sources = R > 1 (gss only): every beam yields its R separated sources, not only the first (bf_config.gss_out_sources);
+        the outputs gain an axis of length R, innermost among the stream axes."""
         self._L = load()
-        self.cfg = config_from_params(params, device, n_streams, layout, das_impl, n_dirs, precision)
+        self.cfg = config_from_params(params, device, n_streams, layout, das_impl, n_dirs, precision, gss_out_sources)
         self.n_dirs = max(1, n_dirs)
-        self.n_out = n_streams * self.n_dirs  # output streams: [stream][dir]
+        self.n_rows = max(1, self.cfg.gss_out_sources)
+        self.n_out = n_streams * self.n_dirs * self.n_rows  # output streams: [stream][dir][row]
         self.M, self.H, self.N = params["n_mics"], params["hop"], 2 * params["hop"]
         self.S = len(params["interf"]) + 1 if params["algo"] in ("lcmv", "gss") else 1
         self.n_streams = n_streams
@@ -471,10 +478,12 @@ class Beamformer:
         self._chk(self._L.bf_set_thetas(self._h, a, len(degs)), "bf_set_thetas")
 
     def stream_rms(self, y_ptr: int, n_frames: int, stream: int = 0) -> np.ndarray:
-        """RMS of every output stream of a device-resident batch -> [n_streams, n_dirs] float64."""
+        """RMS of every output stream of a device-resident batch -> [n_streams, n_dirs] float64 ([n_streams, n_dirs, R] with
+        gss_out_sources = R > 1)."""
         out = (C.c_double * self.n_out)()
         self._chk(self._L.bf_stream_rms(self._h, y_ptr, n_frames, out, stream or None), "bf_stream_rms")
-        return np.array(out[:], np.float64).reshape(self.n_streams, self.n_dirs)
+        shape = (self.n_streams, self.n_dirs) + ((self.n_rows,) if self.n_rows > 1 else ())
+        return np.array(out[:], np.float64).reshape(shape)
 
     def set_interference(self, idx: int, deg: float) -> int:
         """interf_theta_roscallback; returns the interferer count afterwards."""
@@ -505,22 +514,29 @@ class Beamformer:
         return w
 
     def process_hop(self, x: np.ndarray) -> np.ndarray:
-        """x [M, H] float32 (host) -> [H] float32: one jack_callback."""
+        """x [M, H] float32 (host) -> [H] float32: one jack_callback ([n_dirs, H] with look directions, [n_dirs, R, H] or [R, H] with
+        gss_out_sources = R > 1)."""
         x = np.ascontiguousarray(x, np.float32)
         assert x.shape == (self.M, self.H)
         ptrs = (C.c_void_p * self.M)(*[x[m].ctypes.data for m in range(self.M)])
-        out = np.empty((self.n_dirs, self.H), np.float32)
+        out = np.empty((self.n_dirs, self.n_rows, self.H), np.float32)
         self._chk(self._L.bf_process_hop(self._h, ptrs, out.ctypes.data, self.H), "bf_process_hop")
+        out = out if self.n_rows > 1 else out[:, 0]
         return out[0] if self.n_dirs == 1 else out
 
     def process(self, x: np.ndarray, out: np.ndarray = None) -> np.ndarray:
-        """Host batch. planar: x [S, M, F*H] (or [M, F*H] when S == 1); interleaved: [S, F*H, M]."""
+        """Host batch. planar: x [S, M, F*H] (or [M, F*H] when S == 1); interleaved: [S, F*H, M].  -> [output streams, F*H] ([F*H] when
+        there is one), output stream = stream * n_dirs + dir; with gss_out_sources = R > 1 the rows are an axis of their own behind it:
+        [n_streams * n_dirs, R, F*H], or [R, F*H] for one beam."""
         x = np.ascontiguousarray(x, np.float32)
         n = x.size // (self.n_streams * self.M * self.H)
         y = np.empty((self.n_out, n * self.H), np.float32) if out is None else out
         assert y.dtype == np.float32 and y.size == self.n_out * n * self.H and y.flags.c_contiguous
         self._chk(self._L.bf_process_batch(self._h, x.ctypes.data, n, y.ctypes.data), "bf_process_batch")
         y = y.reshape(self.n_out, n * self.H)
+        if self.n_rows > 1:
+            y = y.reshape(self.n_out // self.n_rows, self.n_rows, n * self.H)
+            return y[0] if y.shape[0] == 1 else y
         return y[0] if self.n_out == 1 else y
 
     def process_device(self, x_ptr: int, n_frames: int, y_ptr: int, spectrum_ptr: int = 0, stream: int = 0):

@@ -40,7 +40,8 @@ void bf::trace_note(const void *host_fn) {
 struct bf_handle {
     bf_config cfg;
     int M = 0, H = 0, N = 0, S = 1, n_streams = 1;  // n_streams: input streams
-    int n_dirs = 1, n_out = 1;                      // look directions per input stream; output streams = n_streams * n_dirs
+    int n_dirs = 1, n_out = 1;                      // look directions per input stream; output streams = n_streams * n_dirs * n_rows
+    int n_rows = 1;                                 // gss: separated sources emitted per beam (bf_config.gss_out_sources)
     int device = 0, n_cus = 256;
     std::string err;
 
@@ -222,6 +223,9 @@ int bf_create(const bf_config *cfg, bf_handle **out) {
     if (cfg->n_dirs > 1 && (cfg->algo == BF_MCRA || cfg->algo == BF_GSC))
         return fail(nullptr, BF_ENOSYS, "look-direction batches: mcra has no look direction, gsc is not built for them");
     if (cfg->n_interf < 0 || cfg->n_interf > BF_MAX_INTERF) return fail(nullptr, BF_EINVAL, "n_interf out of range");
+    if (cfg->gss_out_sources < 0 || cfg->gss_out_sources > BF_MAX_INTERF + 1) return fail(nullptr, BF_EINVAL, "gss_out_sources out of range");
+    if (cfg->gss_out_sources > 1 && cfg->algo != BF_GSS)
+        return fail(nullptr, BF_EINVAL, "gss_out_sources: only gss separates sources (the other nodes have one output per beam)");
     if (cfg->layout != BF_PLANAR && cfg->layout != BF_INTERLEAVED) return fail(nullptr, BF_EINVAL, "layout");
     if (cfg->precision != BF_PRECISION_REFERENCE && cfg->precision != BF_PRECISION_MIXED) return fail(nullptr, BF_EINVAL, "precision");
     if (cfg->das_impl != BF_DAS_FUSED_F32 && cfg->das_impl != BF_DAS_F64) return fail(nullptr, BF_EINVAL, "das_impl");
@@ -239,7 +243,8 @@ int bf_create(const bf_config *cfg, bf_handle **out) {
     h->n_streams = cfg->n_streams;
     h->n_dirs = cfg->n_dirs > 1 ? cfg->n_dirs : 1;
     h->cfg.n_dirs = h->n_dirs;
-    h->n_out = h->n_streams * h->n_dirs;
+    h->n_rows = cfg->gss_out_sources > 1 ? cfg->gss_out_sources : 1;
+    h->n_out = h->n_streams * h->n_dirs * h->n_rows;
     h->device = cfg->device;
     h->angle.assign(h->n_dirs, cfg->theta);
     for (int k = 0; k < h->S - 1; ++k) h->interf.push_back(cfg->interf_angle[k]);
@@ -541,7 +546,7 @@ int bf_process_hop(bf_handle *h, const float *const *in, float *out, uint32_t nf
     BF_HIP(h, hipMemcpyAsync(d_x, packed, n_in * sizeof(float), hipMemcpyHostToDevice, h->stream));
     int rc = run_batch_device(h, d_x, 1, d_y, nullptr, h->stream, h->cfg.layout, (long)h->H);
     if (rc != BF_OK) return rc;
-    BF_HIP(h, hipMemcpyAsync(res, d_y, n_outv * sizeof(float), hipMemcpyDeviceToHost, h->stream));  // [dir][hop]
+    BF_HIP(h, hipMemcpyAsync(res, d_y, n_outv * sizeof(float), hipMemcpyDeviceToHost, h->stream));  // [dir][row][hop]
     BF_HIP(h, hipStreamSynchronize(h->stream));
     memcpy(out, res, n_outv * sizeof(float));
     return BF_OK;
@@ -728,6 +733,10 @@ static uint64_t state_cfg_hash(const bf_handle *h) {
     return x;
 }
 
+// header word `das_impl`: the das arithmetic, and above it gss's rows per beam minus one (the blob carries that many overlap-add tails per
+// beam: a handle of another row count must refuse it; one row leaves the word, and so the blob, as it always was)
+static uint32_t state_impl_word(const bf_handle *h) { return (uint32_t)h->cfg.das_impl | ((uint32_t)(h->n_rows - 1) << 16); }
+
 size_t bf_state_size(const bf_handle *h) {
     if (!h) return 0;
     return sizeof(bf_state_header) + sizeof(bf_state_control) + h->engine->state_bytes();
@@ -742,7 +751,7 @@ int bf_get_state(bf_handle *h, void *blob, size_t size) {
     BF_HIP(h, hipSetDevice(h->device));
     BF_HIP(h, hipDeviceSynchronize());
     bf_state_header hd = {kStateMagic, (uint32_t)h->cfg.algo, (uint32_t)h->M, (uint32_t)h->n_streams | ((uint32_t)h->n_dirs << 20),
-                          (uint32_t)h->H, (uint32_t)h->cfg.das_impl, (uint64_t)(bf_state_size(h) - sizeof(bf_state_header))};
+                          (uint32_t)h->H, state_impl_word(h), (uint64_t)(bf_state_size(h) - sizeof(bf_state_header))};
     memcpy(blob, &hd, sizeof(hd));
     bf_state_control ct;
     memset(&ct, 0, sizeof(ct));
@@ -770,7 +779,7 @@ int bf_set_state(bf_handle *h, const void *blob, size_t size) {
     bf_state_header hd;
     memcpy(&hd, blob, sizeof(hd));
     if (hd.magic != kStateMagic || hd.algo != (uint32_t)h->cfg.algo || hd.n_mics != (uint32_t)h->M ||
-        hd.n_streams != ((uint32_t)h->n_streams | ((uint32_t)h->n_dirs << 20)) || hd.hop != (uint32_t)h->H || hd.das_impl != (uint32_t)h->cfg.das_impl)
+        hd.n_streams != ((uint32_t)h->n_streams | ((uint32_t)h->n_dirs << 20)) || hd.hop != (uint32_t)h->H || hd.das_impl != state_impl_word(h))
         return fail(h, BF_EINVAL, "state blob does not match this handle");
     bf_state_control ct;
     memcpy(&ct, (const char *)blob + sizeof(hd), sizeof(ct));

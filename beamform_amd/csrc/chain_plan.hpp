@@ -14,7 +14,8 @@ namespace bf {
 // One batch, as values.  n_streams counts INPUT streams and n_dirs look directions per input stream (>= 1); kp1 = constraint columns of the
 // batch (look direction + interferers; 1 unless lcmv / gss).  band_yh_lo / band_yh_hi: the in-band problems of mvdr / lcmv
 // (BinPipelineImpl::init).  aligned16: the output pointer is 16-byte aligned (device workspaces always are).  The last six: the switches of
-// those names (switches.hpp).
+// those names (switches.hpp).  gss_rows (last, so that a shape written without it means one): separated sources gss emits per beam
+// (bf_config.gss_out_sources; 0 = 1, ignored by every other node).
 struct ChainShape {
     int algo, n_fft, layout, n_mics, n_streams, n_dirs, kp1, past_windows, precision;
     bool dump;
@@ -25,6 +26,7 @@ struct ChainShape {
     bool stft_small, stft_split, mvdr_group;
     int gss_group;
     bool gsc_serial;
+    int gss_rows;
 };
 
 // The kernels of each stage, template arguments behind them as ChainPlan holds them:
@@ -57,6 +59,9 @@ struct ChainPlan {
     bool yh32, mpf32, band_rows;  // band_rows: only problem 0 and yh_lo .. yh_hi exist
     int yh_lo, yh_hi;
     size_t z_bytes, yh_bytes, yraw_elems, frames_elems;  // d_Z_, d_Yh_, d_yraw_, d_frames_ of BinPipelineImpl
+    // gss: rows per beam behind the per-bin stage (1: gss_kernel / gss_lane_kernel store y_fft = this_yf(0), gss.cpp:120-121; more: their
+    // _all variants store this_yf(0 .. rows - 1) as output streams beam * rows + r, and everything behind them runs over So * rows streams)
+    int rows;
     bool fused() const { return front >= ChainFront::kFusedW64; }
     bool rec_istft() const { return rec == ChainRec::kRecIstft; }
 };
@@ -73,10 +78,11 @@ inline ChainPlan chain_decide(const ChainShape &c) {
     const bool dump = c.dump && !gsc;  // time-domain node: there is no single y_fft, the dump reads as zeros
     const bool mixed = c.precision == BF_PRECISION_MIXED;
     const int NP = ((a == BF_MCRA ? 1 : M) + 1) / 2, D = gsc ? M : c.n_dirs;  // gsc: one aligned output per microphone
+    const int R = (a == BF_GSS && c.gss_rows > 1) ? c.gss_rows : 1;
     const size_t S = (size_t)c.n_streams, So = S * D, F = (size_t)c.n_frames, P = cov ? (size_t)c.past_windows : 0;
     const int mp4 = M <= 4 ? 4 : M <= 8 ? 8 : M <= 16 ? 16 : 32, km = kp1 <= 1 ? 1 : 4;
     ChainPlan p{};
-    p.algo = a; p.layout = c.layout; p.z48 = cov && mixed;
+    p.algo = a; p.layout = c.layout; p.z48 = cov && mixed; p.rows = R;
     // nodes without a frame history, up to 8 microphones, one look direction: STFT and per-bin stage in one launch, spectra never leave the CU
     const bool fused = c.fused_bins != 0 && N <= 2048 && M <= 8 && D == 1 && (pointwise || mpf);
     // the register-resident transforms of the other sizes (stft_small / stft_split = 0: the generic kernels; the fused front has no generic twin)
@@ -113,7 +119,8 @@ inline ChainPlan chain_decide(const ChainShape &c) {
     } else if (cov) {
         p.bins = ChainBins::kMvdrLcmv; p.mp = mp4 < 16 ? mp4 : 16; p.km = km;
     } else {
-        // gss: one lane per problem once the lanes fill the chip (two wavefronts per CU); gss_group = 1 / 0 forces the group / the lane kernel
+        // gss: one lane per problem once the lanes fill the chip (two wavefronts per CU); gss_group = 1 / 0 forces the group / the lane kernel.
+        // Problems are counted per beam: the rows a problem stores do not change who computes it
         const bool lane = c.gss_group >= 0 ? c.gss_group == 0 : (long)So * ((N / 2 + 2 + 63) / 64) >= 2L * c.n_cus;
         p.bins = (M <= 8 && lane) ? ChainBins::kGssLane : ChainBins::kGss; p.mp = mp4; p.km = km;
     }
@@ -139,9 +146,9 @@ inline ChainPlan chain_decide(const ChainShape &c) {
     // Z: the packed spectra of history + batch (+ 512 frames of slack for mvdr_fast_kernel's prefetch past a short last tile); the fused front
     // parks the unpacked spectra of two bins per frame there instead.  Yh: phasempf keeps one double per problem behind the rows
     p.z_bytes = fused ? S * F * 2 * 8 * 16 : (S * (P + F) + (cov ? 512 : 0)) * NP * N * (p.z48 ? 12 : 16);
-    p.yh_bytes = So * F * (N / 2 + 4) * (mpf ? 24 : 16);
+    p.yh_bytes = So * R * F * (N / 2 + 4) * (mpf ? 24 : 16);
     p.yraw_elems = (mpf || gsc) ? So * F * (N / 2) : 0;
-    p.frames_elems = N != 1024 ? So * F * N : 0;
+    p.frames_elems = N != 1024 ? So * R * F * N : 0;
     return p;
 }
 

@@ -1391,7 +1391,7 @@ hipError_t launch_bins_end(const ChainPlan &p, const BinsArgs &a, hipStream_t s)
     if (p.rec == ChainRec::kRecIstft) BF_LAUNCH(mpf_rec_istft_kernel, dim3((unsigned)a.n_streams), dim3(kRiThreads), 0, s, a, aux);
 #endif
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess && p.expand ? launch_expand_spectrum(a.Yh, a.spectrum, (long)a.n_streams * a.n_frames, s) : e;
+    return e == hipSuccess && p.expand ? launch_expand_spectrum(a.Yh, a.spectrum, (long)a.n_streams * p.rows * a.n_frames, s) : e;
 }
 
 // The fused front of this FFT size: frames per round of a block, and the kernel with its block size.  N = 1024 walks single frames.

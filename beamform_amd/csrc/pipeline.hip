@@ -47,7 +47,8 @@ class BinPipelineImpl : public Engine {
         S_ = c.n_streams;                                   // input streams
         D_ = c.n_dirs > 1 ? c.n_dirs : 1;                   // look directions per input stream
         if (time_node_) D_ = M_;                            // gsc: one aligned output per microphone (do_overlap_bymic)
-        So_ = S_ * D_;                                      // output streams
+        So_ = S_ * D_;                                      // beams (output streams of every node but gss with several rows)
+        R_ = (c.algo == BF_GSS && c.gss_out_sources > 1) ? c.gss_out_sources : 1;  // separated sources emitted per beam (gss.cpp:120-121 keeps one)
         const bool multi = (c.algo == BF_LCMV || c.algo == BF_GSS);
         KP1_ = multi ? c.n_interf + 1 : 1;
         Phist_ = cov_node_ ? c.past_windows : 0;
@@ -227,7 +228,7 @@ class BinPipelineImpl : public Engine {
     bool das_one_launch_shape() const { return cfg_.algo == BF_DAS && N_ == 1024 && M_ <= 8 && D_ == 1; }
     size_t steer_elems() const { return (size_t)D_ * N_ * M_ * kMaxCols; }
     size_t hist_elems() const { return (size_t)S_ * M_ * H_; }  // the carried hop of every input stream
-    size_t tail_elems() const { return (size_t)So_ * H_; }      // the overlap-add tail of every output stream
+    size_t tail_elems() const { return (size_t)So_ * R_ * H_; }  // the overlap-add tail of every output stream
     size_t zhist_bytes() const { return Phist_ ? (size_t)S_ * Phist_ * NP_ * N_ * zsz_ : 0; }
     // recursive per-beam state is sized by OUTPUT streams (input streams x look directions)
     size_t gss_bytes() const { return cfg_.algo == BF_GSS ? (size_t)So_ * N_ * kMaxCols * M_ * sizeof(f64x2) : 0; }
@@ -257,7 +258,7 @@ class BinPipelineImpl : public Engine {
     }
 
     bf_config cfg_;
-    int n_cus_, M_, MF_, NP_, S_, D_, So_, KP1_, Phist_;
+    int n_cus_, M_, MF_, NP_, S_, D_, So_, R_, KP1_, Phist_;
     // what kind of node this is
     const bool cov_node_ = cfg_.algo == BF_MVDR || cfg_.algo == BF_LCMV;  // covariance over a frame history; halved (or z48) spectra, band-limited rows
     const bool band_node_ = cov_node_ || cfg_.algo == BF_GSS;             // only the bins inside [freq_min, freq_max] are processed
@@ -347,7 +348,7 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
     const ChainPlan p = chain_decide(ChainShape{cfg_.algo, N_, layout, M_, S_, cfg_.n_dirs > 1 ? cfg_.n_dirs : 1, snap.kp1, cfg_.past_windows,
                                                 cfg_.precision, spectrum != nullptr, F, n_cus_, cfg_.gsc_filter_size, cfg_.smooth_size,
                                                 band_yh_lo_, band_yh_hi_, (reinterpret_cast<size_t>(y) & 15) == 0, sw.fused_bins,
-                                                sw.stft_small, sw.stft_split, sw.mvdr_group, sw.gss_group, sw.gsc_serial});
+                                                sw.stft_small, sw.stft_split, sw.mvdr_group, sw.gss_group, sw.gsc_serial, R_});
     float *const hist = d_hist2_[hist_cur_].get();
     const long FT = Phist_ + F;  // frames in the Z workspace per stream
     ENGINE_HIP(d_Z_.reserve(p.z_bytes));
@@ -386,6 +387,7 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
     ba.z48 = p.z48 ? 1 : 0;
     ba.cfg = cfg_; ba.gssW = d_gssW_.get(); ba.mpf = d_mpf_.get(); ba.gss_reset_mask = snap.gss_reset_mask;
     ba.yh32 = p.yh32 ? 1 : 0; ba.mpf32 = p.mpf32 ? 1 : 0; ba.yh_lo = p.yh_lo; ba.yh_hi = p.yh_hi;
+    ba.gss_rows = p.rows;
     if (p.rec_istft()) {  // mpf_rec_istft_kernel: a block per stream, the y_fft rows stay in LDS
         ba.rec_istft = 1;
         ba.rec_y = d_yraw_.get(); ba.rec_tail_in = d_tail_[tail_cur_].get(); ba.rec_tail_out = d_tail_[tail_cur_ ^ 1].get();
@@ -393,7 +395,8 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
     }
     IstftArgs ia;
     ia.Yh = Yh; ia.y = yraw_target_ ? d_yraw_.get() : y; ia.tail_in = d_tail_[tail_cur_].get();
-    ia.tail_out = d_tail_[tail_cur_ ^ 1].get(); ia.tw = d_tw_.get(); ia.win = d_win_.get(); ia.n_frames = F; ia.n_streams = So_;
+    ia.tail_out = d_tail_[tail_cur_ ^ 1].get(); ia.tw = d_tw_.get(); ia.win = d_win_.get(); ia.n_frames = F;
+    ia.n_streams = So_ * p.rows;  // gss: every row of a beam is an output stream (beam * rows + r) with its own overlap-add tail
     ia.tw32 = d_tw32_.get();
     ia.tw_w64 = d_tw_w64_.get();
     ia.yh32 = ba.yh32; ia.yh_lo = ba.yh_lo; ia.yh_hi = ba.yh_hi;

@@ -67,7 +67,8 @@ struct StftArgs {
 
 struct BinsArgs {
     const f64x2 *Z;      // [stream][frames_ws][NP][N] f64x2 (z48 elements for mvdr / lcmv: reinterpret)
-    f64x2 *Yh;           // [stream][n_frames][kYhStride]: y_fft of problems q = 0..N/2+1 (f32x2 rows when yh32)
+    f64x2 *Yh;           // [stream][n_frames][kYhStride]: y_fft of problems q = 0..N/2+1 (f32x2 rows when yh32); gss with gss_rows > 1:
+                         // [stream][gss_rows][n_frames][kYhStride]
     int yh32;            // mvdr / lcmv in front of the fp32 backward transform: rows are f32x2 and only the problems
                          // 0 and yh_lo..yh_hi are written (the rest is zero by definition: mvdr.cpp:103) -- istft32 knows
     int yh_lo, yh_hi;
@@ -93,6 +94,7 @@ struct BinsArgs {
     const double *rec_win = nullptr;
     int mpf32;           // phasempf in front of the fp32 backward transform: the recursion leaves y_fft as f32x2 rows in the slots of its
                          // |out_int|^2 input (8 bytes each, same [stream][frame][kYhStride] layout, behind the f64x2 rows)
+    int gss_rows = 1;    // gss: separated sources stored per beam (ChainPlan::rows); n_streams, Z, steer, gssW and the reset mask stay per BEAM
 };
 struct IstftArgs {
     const f64x2 *Yh;

@@ -140,6 +140,21 @@ typedef struct bf_config {
     int gsc_use_vad;
     double gsc_vad_threshold, gsc_mu0, gsc_mu_max;
     int gsc_filter_size;           /* 1..256 */
+    /* (new fields are appended: a caller built against an older header that zeroes the struct keeps its meaning) */
+    int gss_out_sources;           /* gss: separated sources emitted per beam, R (0/1 = one, the reference node; up to BF_MAX_INTERF + 1).
+                                      gss.cpp computes this_yf = sep_matrix[j] * in_fft.col(j) every frame and keeps this_yf(0) alone
+                                      ("outputting only the first source of interest", gss.cpp:120-121); with R > 1 each beam (input
+                                      stream x look direction) yields R output streams, index (stream * n_dirs + dir) * R + r, and
+                                      row r is this_yf(r): in band with the gate open (sep_matrix[j] x)(r) for r < 1 + interferers;
+                                      gate closed 0.01 X_0 for r = 0 and 0 above (gss.cpp:139-141); out of band, and for r beyond the
+                                      current source count, 0.  Every row takes row 0's backward transform, window, out_amp and
+                                      overlap-add (gss.cpp:148-155), each with its own tail.  R is fixed at create;
+                                      bf_set_interference may change the source count underneath: a row that stops existing goes
+                                      silent once its tail has been added, a row that starts existing begins from the
+                                      re-initialised sep_matrix = weights^H like every other (gss.cpp:90-93).  Wherever this header
+                                      counts output streams as n_streams * n_dirs (y, spectrum_dev, bf_stream_rms, bf_process_hop,
+                                      the state blob's tails), read n_streams * n_dirs * R.  Row 0 is the R = 1 node's output bit
+                                      for bit; R = 1 runs the very kernels it always ran.  Above 1 with another algo: BF_EINVAL */
 } bf_config;
 #define BF_MAX_DIRS 64
 
@@ -239,7 +254,8 @@ void bf_host_free(void *p);
 /* jack_callback body: do_overlap(in, out, nframes, apply_weights)
  * (das.cpp:72-92, util.h:289-314).  in = n_mics pointers to nframes float32
  * (host memory, as input_from_rosjack returns), out = nframes float32 (host).
- * nframes must equal cfg.hop.  Single-stream handles only; with n_dirs > 1 `out` receives [n_dirs][nframes]. */
+ * nframes must equal cfg.hop.  Single-stream handles only; with n_dirs > 1 `out` receives [n_dirs][nframes], with gss_out_sources = R > 1
+ * [n_dirs][R][nframes]. */
 int bf_process_hop(bf_handle *h, const float *const *in, float *out, uint32_t nframes);
 
 /* n_frames consecutive callbacks per stream in one call, host buffers.
@@ -260,7 +276,8 @@ int bf_process_batch(bf_handle *h, const float *x_host, size_t n_frames, float *
 /* Same, buffers already resident in HBM; enqueued on `hip_stream`
  * (a hipStream_t, NULL = default stream) without host synchronisation.
  * spectrum_dev (nullable): receives y_fft per frame as double2
- * [n_streams][n_frames][2*hop] (see DESIGN.md for the DAS fused variant). */
+ * [n_streams][n_frames][2*hop] (see DESIGN.md for the DAS fused variant).  With look directions / gss_out_sources the leading
+ * axis of y and of spectrum_dev is the output stream, (stream * n_dirs + dir) * R + r. */
 int bf_process_batch_device(bf_handle *h, const float *x_dev, size_t n_frames, float *y_dev,
                             void *spectrum_dev, void *hip_stream);
 
@@ -270,7 +287,8 @@ int bf_get_weights(bf_handle *h, double *w_host);
 
 /* Checkpoint of all per-stream state (ring hop, OLA tail, covariance history,
  * GSS demixing matrices, MCRA/MPF vectors, smoothing tail).  The reference has
- * no counterpart (state lives in process globals). */
+ * no counterpart (state lives in process globals).  A blob is accepted only by a handle of the same shape, gss_out_sources
+ * included (one overlap-add tail per output stream). */
 size_t bf_state_size(const bf_handle *h);
 int bf_get_state(bf_handle *h, void *blob_host, size_t size);
 int bf_set_state(bf_handle *h, const void *blob_host, size_t size);
