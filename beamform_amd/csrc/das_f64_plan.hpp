@@ -1,6 +1,8 @@
-// das_f64_plan.hpp -- the work queue of das_f64_pair_kernel (das_f64_w64.hip), host arithmetic: how a batch is cut into CHUNKS of
-// consecutive frame pairs and where chunk k lies.  Plain C++ (the CPU suite checks it through tests/host_emul: every plan must tile every
-// stream exactly once, start every chunk on an even frame, stay inside the table and inside the 10-bit fields of the kernel's work word).
+// das_f64_plan.hpp -- what one batch of das in double launches (das_f64_w64.hip), host arithmetic: which kernel serves it (das_f64_decide,
+// below) and the work queue of das_f64_pair_kernel: how a batch is cut into CHUNKS of consecutive frame pairs and where chunk k lies.
+// Plain C++ (the CPU suite checks it through tests/host_emul: the decision against every das (double) row of docs/DISPATCH.md, random
+// shapes and both switches; every plan must tile every stream exactly once, start every chunk on an even frame, stay inside the table and
+// inside the 10-bit fields of the kernel's work word).
 //
 // Per stream: nb = blocks per stream (n_cus / n_streams, at least 1).  The first level gives every block one long chunk (81 % of its equal
 // share: consecutive pairs on one CU share their input hop through L1 / L2 and hand over their output hop through LDS flags), the following
@@ -13,6 +15,8 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "../../include/bfcore.h"
+
 #if defined(__HIPCC__)
 #define BF_PLAN_HD __host__ __device__ inline
 #else
@@ -24,6 +28,12 @@ namespace bf {
 constexpr int kChunkEnd = 0xFFFFF;       // chunk field of the kernel's work word: the table is exhausted
 constexpr int kMaxChunkPairs = 1000;     // pairs per chunk (10 bits, and up to 8 draws past the end before the word is replaced)
 constexpr int kSchedMaxChunks = 16384;   // rows of the chunk table
+// the kernel's device workspace: the draw counter on a line of its own, then the table, one row {stream, first frame, frames, 0} per chunk
+constexpr size_t kSchedCounterBytes = 256, kSchedRowBytes = 16;
+constexpr size_t das_f64_sched_ws_bytes() { return kSchedCounterBytes + kSchedMaxChunks * kSchedRowBytes; }
+// what the decision needs of the kernels' shape (das_f64_w64.hip asserts each against its own constant): samples per hop (the kernels are
+// built for N = 1024), wavefronts per block (one step of the microphone-pair kernel's block is 8 frames), hop slots of a block's ring
+constexpr int kDasF64Hop = 512, kDasF64Waves = 8, kDasF64RingSlots = 40;
 
 struct DasSchedPlan {
     int n_levels;
@@ -111,5 +121,61 @@ inline DasSchedPlan das_f64_plan(long n_frames, int n_streams, int n_cus, const 
     return p;
 }
 
+// What one batch launches: das_f64_decide settles it ONCE from the batch's shape, on the host and without touching the device;
+// enqueue_das_f64 (das_f64_w64.hip) carries it out.
+enum class DasF64Path {
+    kChain,      // none of the kernels here: the STFT -> per-bin -> ISTFT chain serves the batch
+    kFramePair,  // das_f64_pair_kernel on planar input
+    kRing,       // das_f64_ring_kernel: [sample][mic] input with 2, 4 or 8 microphones, transposed hop by hop into the blocks' rings
+    kTranspose,  // interleaved_to_planar_kernel (batch, carried hop) + das_f64_pair_kernel: [sample][mic] input otherwise
+    kMicPair,    // das_f64_w64_kernel<1>: [sample][mic] input with one microphone or a non-unit weight row 0
+};
+struct DasF64Launch {
+    DasF64Path path;
+    DasSchedPlan plan;                  // frame-pair kernels: the chunk plan
+    long run_frames, runs_per_stream;   // microphone-pair kernel: its static runs
+    size_t scratch_bytes;               // device scratch of enqueue_das_f64: the blocks' hop rings (kRing), the planar batch + carried hop (kTranspose)
+    bool writes_hist;                   // the kernel stores the carried hop into DasF64Args::hist_out itself (no copy behind it)
+};
+// One batch, as values.  mic0_unit, n_tr: the steering summary (geometry.hpp das_f64_slots); tables: the frame-pair kernels' gains and
+// work-queue workspace exist.  das_il_ring, das_f64_sched: the switches BF_DAS_IL_RING and BF_DAS_F64_SCHED (switches.hpp; null = unset).
+struct DasF64Shape {
+    int layout, n_mics, n_streams, n_cus;
+    long n_frames;
+    bool mic0_unit, tables;
+    int n_tr, das_il_ring;
+    const char *das_f64_sched;
+};
+
+// Which kernel serves a batch (docs/DISPATCH.md).  The frame-pair kernels -- das_f64_pair_kernel on planar input; on [sample][mic] input
+// das_f64_ring_kernel at 2, 4 or 8 microphones (the ring's transposition addresses by shifts; das_il_ring = 0: never) and the
+// transposition in front of das_f64_pair_kernel otherwise -- never transform microphone 0: they need the reference's unit weight row
+// there (das.cpp:33-38, always true for das on a handle that started cold), a second microphone, and a batch their work queue can
+// hold.  [sample][mic] input without the first two: the microphone-pair kernel das_f64_w64_kernel<1>.  Anything else: the chain.
+// (The transposition moves tiles of 256 samples.  A batch is n_frames hops and the carried hop is one, 512 samples each, so the tile
+// always divides both: no frame count is turned away for it.)
+inline DasF64Launch das_f64_decide(const DasF64Shape &c) {
+    DasF64Launch d{};  // the chain
+    if (c.n_mics > 8) return d;  // the gain tables fill the LDS
+    if (!(c.tables && c.mic0_unit && c.n_mics >= 2 && c.n_tr >= 1)) {
+        if (c.layout == BF_PLANAR) return d;
+        // frames per run: a multiple of one step of the block (8 frames), about one run per CU
+        const long runs = c.n_cus > c.n_streams ? c.n_cus / c.n_streams : 1;
+        d.path = DasF64Path::kMicPair;
+        d.run_frames = ((c.n_frames + runs - 1) / runs + kDasF64Waves - 1) / kDasF64Waves * kDasF64Waves;
+        d.runs_per_stream = (c.n_frames + d.run_frames - 1) / d.run_frames;
+        return d;
+    }
+    if ((long)c.n_streams * ((c.n_frames + 1) / 2) >= (1L << 31)) return d;
+    d.plan = das_f64_plan(c.n_frames, c.n_streams, c.n_cus, c.das_f64_sched);
+    if (d.plan.n_chunks < 1 || d.plan.n_chunks > kSchedMaxChunks) return d;  // (more streams than the table has rows)
+    const bool ring = c.das_il_ring != 0 && (c.n_mics == 2 || c.n_mics == 4 || c.n_mics == 8);
+    d.path = c.layout == BF_PLANAR ? DasF64Path::kFramePair : ring ? DasF64Path::kRing : DasF64Path::kTranspose;
+    d.writes_hist = c.layout == BF_PLANAR;
+    // scratch: one ring per CU, whatever the plan's grid; the transposition: the batch and the carried hop, planar
+    const size_t hop_elems = (size_t)c.n_mics * kDasF64Hop;
+    d.scratch_bytes = sizeof(float) * (c.layout == BF_PLANAR ? 0 : ring ? c.n_cus * kDasF64RingSlots * hop_elems : c.n_streams * hop_elems * (c.n_frames + 1));
+    return d;
+}
 
 }  // namespace bf

@@ -1,7 +1,7 @@
 // das_f64_w64.hip -- das at the reference's precision (double arithmetic, das.cpp:47-70 + util.h:217-314), one launch,
 // one full wavefront per transform (fft1024_w64.hpp: 64 lanes x 16 points, 16 x 16 x 4).
 //
-// Two kernels share the transform machinery (das_f64_decide picks per batch, docs/DISPATCH.md):
+// Two kernels share the transform machinery (das_f64_plan.hpp das_f64_decide picks per batch, docs/DISPATCH.md):
 //   das_f64_pair_kernel  planar input (the bench headline), and [sample][mic] input behind interleaved_to_planar_kernel; as
 //   das_f64_ring_kernel  [sample][mic] input with 2, 4 or 8 microphones, transposed hop by hop into the blocks' rings.  A complex
 //                        transform carries frames t and t + 1 of ONE microphone; U = sum_m ce_m Z_m with the per-microphone
@@ -33,7 +33,6 @@
 
 #include "launch_trace.hpp"
 #include "pipeline_kernels.hpp"
-#include "switches.hpp"
 #include "w64_f64_dev.hpp"
 
 namespace bf {
@@ -1097,45 +1096,9 @@ __global__ __launch_bounds__(256) void interleaved_to_planar_kernel(const float 
 
 }  // namespace
 
-// ---- the frame-pair kernel's work queue ------------------------------------------------------------------------------------------
-// Per stream: nb = blocks per stream (n_cus / n_streams, at least 1).  Level 0 gives every block one long chunk (kSchedFirst of its
-// equal share: consecutive pairs on one CU share their input hop through L1 / L2 and hand over their output hop through LDS flags),
-// the following levels halve the chunk until kSchedLast pairs; what is left goes out in chunks of kSchedLast pairs.  A chunk edge costs
-// one input hop read twice and two atomic adds per output sample, so the small chunks are kept to the last ~12 % of the batch.
-// BF_DAS_F64_SCHED=0: one level of equal chunks (the static runs of round 4); BF_DAS_F64_SCHED="88,16,8,4,2": explicit chunk sizes in pairs.
-constexpr size_t kSchedCounterBytes = 256;
-size_t das_f64_sched_ws_bytes() { return kSchedCounterBytes + (size_t)kSchedMaxChunks * sizeof(int4); }
-
-// Which kernel serves a batch (docs/DISPATCH.md).  The frame-pair kernels -- das_f64_pair_kernel on planar input; on [sample][mic] input
-// das_f64_ring_kernel at 2, 4 or 8 microphones (the ring's transposition addresses by shifts; BF_DAS_IL_RING=0: never) and the
-// transposition in front of das_f64_pair_kernel otherwise -- never transform microphone 0: they need the reference's unit weight row
-// there (das.cpp:33-38, always true for das on a handle that started cold), a second microphone, and a batch their work queue can
-// hold.  [sample][mic] input without the first two: the microphone-pair kernel das_f64_w64_kernel<1>.  Anything else: the chain.
-DasF64Launch das_f64_decide(int layout, int n_mics, int n_streams, long n_frames, int n_cus, bool mic0_unit, int n_tr, bool tables) {
-    DasF64Launch d{};  // the chain
-    if (n_mics > 8) return d;  // the gain tables fill the LDS
-    const bool ring = switches().das_il_ring != 0 && (n_mics == 2 || n_mics == 4 || n_mics == 8);
-    bool frame_pair = tables && mic0_unit && n_mics >= 2 && n_tr >= 1;
-    if (layout != BF_PLANAR && !ring && ((n_frames * kHop) & 255) != 0) frame_pair = false;  // the transposition moves tiles of 256 samples
-    if (!frame_pair) {
-        if (layout == BF_PLANAR) return d;
-        // frames per run: a multiple of one step of the block (8 frames), about one run per CU
-        const long runs = n_cus > n_streams ? n_cus / n_streams : 1;
-        d.path = DasF64Path::kMicPair;
-        d.run_frames = ((n_frames + runs - 1) / runs + kWaves - 1) / kWaves * kWaves;
-        d.runs_per_stream = (n_frames + d.run_frames - 1) / d.run_frames;
-        return d;
-    }
-    if ((long)n_streams * ((n_frames + 1) / 2) >= (1L << 31)) return d;
-    d.plan = das_f64_plan(n_frames, n_streams, n_cus, switches().das_f64_sched);
-    if (d.plan.n_chunks < 1 || d.plan.n_chunks > kSchedMaxChunks) return d;  // (more streams than the table has rows)
-    d.path = layout == BF_PLANAR ? DasF64Path::kFramePair : ring ? DasF64Path::kRing : DasF64Path::kTranspose;
-    d.writes_hist = layout == BF_PLANAR;
-    // scratch: one ring per CU, whatever the plan's grid; the transposition: the batch and the carried hop, planar
-    const size_t hop_elems = (size_t)n_mics * kHop;
-    d.scratch_bytes = sizeof(float) * (layout == BF_PLANAR ? 0 : ring ? n_cus * kRingSlots * hop_elems : n_streams * hop_elems * (n_frames + 1));
-    return d;
-}
+// what das_f64_decide (das_f64_plan.hpp, plain C++) assumes of the kernels here
+static_assert(kWaves == kDasF64Waves && kRingSlots == kDasF64RingSlots && kHop == kDasF64Hop, "das_f64_plan.hpp describes other kernels");
+static_assert(sizeof(int4) == kSchedRowBytes, "a row of the chunk table is one int4");
 
 // x = [stream][n][M] -> out = [stream][M][n] (n a multiple of 256 samples, M <= 8, both 16-byte aligned)
 static hipError_t launch_interleaved_to_planar(const float *x, float *out, long n, int n_mics, int n_streams, hipStream_t s) {

@@ -275,4 +275,33 @@ inline std::vector<f64x2> das_mic_gains_w64_f64(const SteeringSet &s, int n_mics
     return T;
 }
 
+// What das_f64_pair_kernel needs to know about a das steering table beyond its gains (pipeline_kernels.hpp DasF64Args of the same names):
+// whether microphone 0's weight row is identically 1 (das.cpp:33-38 writes it once; quirk Q3 can leave it 0) -- only then may the kernel
+// skip that microphone's transform -- and its walk over the others: slot k transforms microphone slot_mic[k], k < n_tr, and extra_mic
+// (-1 = none) shares slot 0's transform.
+struct DasSlots {
+    int n_tr = 0, extra_mic = -1;
+    int slot_mic[8] = {1, 2, 3, 4, 5, 6, 7, 0};
+    bool mic0_unit = false;
+};
+// Microphones 1 .. M - 1 whose weight rows compare equal in every bin (same delay: the reference drops z, util.h:82-92, so e.g. aira16's
+// microphones 1 and 7 -- beamform_config.yaml:21,27 -- coincide for every look direction) share a forward transform: the first such
+// pair (a, b), a < b, goes into slot 0 with extra_mic = b, the other microphones follow in ascending order.  Up to 8 microphones (the
+// one-launch kernels' limit); more: the default, which no kernel reads.
+inline DasSlots das_f64_slots(const SteeringSet &s) {
+    DasSlots sl;
+    const int N = s.n_fft, M = s.n_mics;
+    if (M < 1 || M > 8) return sl;
+    sl.mic0_unit = true;
+    for (int j = 0; j < N && sl.mic0_unit; ++j) sl.mic0_unit = s.at(j, 0, 0) == cplxd(1.0, 0.0);
+    auto same_row = [&](int a, int b) { int j = 0; while (j < N && s.at(j, a, 0) == s.at(j, b, 0)) ++j; return j == N; };
+    int pa = -1;
+    for (int a = 1; a < M && pa < 0; ++a)
+        for (int b = a + 1; b < M && pa < 0; ++b)
+            if (same_row(a, b)) { sl.slot_mic[sl.n_tr++] = pa = a; sl.extra_mic = b; }
+    for (int m = 1; m < M; ++m)
+        if (m != pa && m != sl.extra_mic) sl.slot_mic[sl.n_tr++] = m;
+    return sl;
+}
+
 }  // namespace bf

@@ -105,8 +105,8 @@ class BinPipelineImpl : public Engine {
         }
         for (auto &b : d_steer_) ENGINE_HIP(b.alloc(steer_elems()));
         if (das_one_launch_shape()) {
-            for (auto &b : d_dasg_w64_) ENGINE_HIP(b.alloc((size_t)4 * 1024));
-            for (auto &b : d_dasg_mic_) ENGINE_HIP(b.alloc((size_t)8 * kDasMicGainRows * kDasMicGainRow));
+            for (auto &t : das_) ENGINE_HIP(t.gains_w64.alloc((size_t)4 * 1024));
+            for (auto &t : das_) ENGINE_HIP(t.gains_mic.alloc((size_t)8 * kDasMicGainRows * kDasMicGainRow));
             ENGINE_HIP(d_das_sched_.alloc(das_f64_sched_ws_bytes()));  // das_f64_pair_kernel's work queue (chunk table + counter)
         }
         if (N_ == 1024) ENGINE_HIP(d_tw_w64_.upload(twiddle_table_w64_rot()));
@@ -152,33 +152,13 @@ class BinPipelineImpl : public Engine {
                         t[(((size_t)d * nc + c) * M_ + m) * N_ + j] = f64x2{w.real(), w.imag()};
                     }
         const int nxt = steer_cur_ ^ 1;
-        std::vector<f64x2> dg, dg64, dgm;  // das fp64 in one launch: the pair gains of the (single) look direction, same double buffering
+        std::vector<f64x2> dg64, dgm;  // das in double in one launch: the gains of the (single) look direction and its summary, same double buffering
         if (das_one_launch_shape()) {
-            dg = das_pair_gains_t<f64x2>(dirs[0], 4);
-            dg64 = das_pair_gains_w64_f64(dg, 4);
-            ENGINE_HIP(hipMemcpyAsync(d_dasg_w64_[nxt].get(), dg64.data(), dg64.size() * sizeof(f64x2), hipMemcpyHostToDevice, stream));
+            dg64 = das_pair_gains_w64_f64(das_pair_gains_t<f64x2>(dirs[0], 4), 4);
             dgm = das_mic_gains_w64_f64(dirs[0], 8);
-            ENGINE_HIP(hipMemcpyAsync(d_dasg_mic_[nxt].get(), dgm.data(), dgm.size() * sizeof(f64x2), hipMemcpyHostToDevice, stream));
-            bool unit = true;  // das.cpp:33-38 writes weights(0, j) = 1 once; only then may the pair kernel skip microphone 0's transform
-            for (int j = 0; j < N_ && unit; ++j) unit = dirs[0].at(j, 0, 0) == cplxd(1.0, 0.0);
-            das_mic0_unit_[nxt] = unit;
-            // Microphones 1 .. M - 1 whose weight rows are bitwise identical (same delay: the reference drops z, util.h:82-92, so e.g. aira16's
-            // microphones 1 and 7 -- beamform_config.yaml:21,27 -- coincide for every look direction) share a forward transform in
-            // das_f64_pair_kernel: the first such pair goes into slot 0, the other microphones follow in ascending order.
-            DasSlots sl;
-            int pa = -1, pb = -1;
-            for (int m1 = 1; m1 < M_ && pa < 0; ++m1)
-                for (int m2 = m1 + 1; m2 < M_ && pa < 0; ++m2) {
-                    bool same = true;
-                    for (int j = 0; j < N_ && same; ++j) same = dirs[0].at(j, m1, 0) == dirs[0].at(j, m2, 0);
-                    if (same) { pa = m1; pb = m2; }
-                }
-            sl.n_tr = 0;
-            if (pa >= 0) sl.slot_mic[sl.n_tr++] = pa;
-            for (int m = 1; m < M_; ++m)
-                if (m != pa && m != pb) sl.slot_mic[sl.n_tr++] = m;
-            sl.extra_mic = pb;
-            das_slots_[nxt] = sl;
+            das_[nxt].slots = das_f64_slots(dirs[0]);
+            ENGINE_HIP(hipMemcpyAsync(das_[nxt].gains_w64.get(), dg64.data(), dg64.size() * sizeof(f64x2), hipMemcpyHostToDevice, stream));
+            ENGINE_HIP(hipMemcpyAsync(das_[nxt].gains_mic.get(), dgm.data(), dgm.size() * sizeof(f64x2), hipMemcpyHostToDevice, stream));
         }
         ENGINE_HIP(hipMemcpyAsync(d_steer_[nxt].get(), t.data(), t.size() * sizeof(f64x2), hipMemcpyHostToDevice, stream));
         ENGINE_HIP(hipStreamSynchronize(stream));  // `t` is pageable and about to go out of scope
@@ -199,10 +179,7 @@ class BinPipelineImpl : public Engine {
         sn.gss_reset_mask = gss_reset_mask_;
         sn.steer = d_steer_[steer_cur_].get();
         sn.steer_dir_stride = steer_dir_stride_;
-        sn.das_gains_w64 = d_dasg_w64_[steer_cur_].get();
-        sn.das_gains_mic = d_dasg_mic_[steer_cur_].get();
-        sn.das_mic0_unit = das_mic0_unit_[steer_cur_];
-        sn.das_slots = das_slots_[steer_cur_];
+        sn.das = DasSnapshot{das_[steer_cur_].gains_w64.get(), das_[steer_cur_].gains_mic.get(), das_[steer_cur_].slots};
         gss_reset_mask_ = 0;
         return sn;
     }
@@ -224,7 +201,7 @@ class BinPipelineImpl : public Engine {
     static constexpr int kDeclined = 1;  // (every BF_* code is <= 0)
     int run_das_one_launch(const float *x, long F, float *y, hipStream_t stream, int layout, long mic_stride, const RunSnapshot &snap);
     int run_chain(const float *x, long F, float *y, f64x2 *spectrum, hipStream_t stream, int layout, long mic_stride, const RunSnapshot &snap);
-    // das through this pipeline on the tuned shape: eligible for the one-launch kernels of das_f64_w64.hip (das_f64_decide per batch)
+    // das through this pipeline on the tuned shape: eligible for the one-launch kernels of das_f64_w64.hip (das_f64_plan.hpp das_f64_decide per batch)
     bool das_one_launch_shape() const { return cfg_.algo == BF_DAS && N_ == 1024 && M_ <= 8 && D_ == 1; }
     size_t steer_elems() const { return (size_t)D_ * N_ * M_ * kMaxCols; }
     size_t hist_elems() const { return (size_t)S_ * M_ * H_; }  // the carried hop of every input stream
@@ -278,12 +255,11 @@ class BinPipelineImpl : public Engine {
     DeviceBuffer<f32x2> d_tw32_;
     DeviceBuffer<double> d_win_, d_freq_;
     DeviceBuffer<f64x2> d_steer_[2];     // double-buffered with steer_cur_: a batch in flight keeps the table it was launched with
-    DeviceBuffer<f64x2> d_dasg_w64_[2];  // das_pair_gains_w64_f64 of the same
+    // das in double in one launch, of the same table (geometry.hpp): das_pair_gains_w64_f64 (microphone-pair kernel), das_mic_gains_w64_f64
+    // (frame-pair kernels), das_f64_slots (is row 0 identically 1, which microphones get a forward transform in which order)
+    struct DasTables { DeviceBuffer<f64x2> gains_w64, gains_mic; DasSlots slots; } das_[2];
     DeviceBuffer<f64x2> d_tw_w64_;       // twiddle_table_w64_rot
     DeviceBuffer<char> d_das_sched_;     // das_f64_pair_kernel: chunk table + counter (das_f64_sched_ws_bytes())
-    DeviceBuffer<f64x2> d_dasg_mic_[2];  // das_mic_gains_w64_f64 (frame-pair kernel)
-    bool das_mic0_unit_[2] = {false, false};     // ... and whether microphone 0's weight row in that table is identically 1
-    DasSlots das_slots_[2];                      // ... and which microphones get a forward transform in which order (identical rows merged)
     int steer_cur_ = 0;
     DeviceBuffer<float> d_hist2_[2];  // ring hop in front of the next batch; two buffers: das_f64_pair_kernel writes the carry itself
     int hist_cur_ = 0;
@@ -303,13 +279,16 @@ class BinPipelineImpl : public Engine {
     DeviceBuffer<float> d_frames_;  // N != 1024: windowed frames between the generic ISTFT and its overlap-add
 };
 
-// das at the reference's precision on the tuned shape, no spectrum dump: ONE launch, spectra never leave the CU (das_f64_w64.hip: das_f64_decide
-// picks the kernel -- the frame-pair kernel das_f64_pair_kernel on planar input, the headline -- or declines); BF_FUSED_BINS=0 keeps the chain
-// (cross-checks).  BF_OK: handled; kDeclined: run_chain serves the batch; an error otherwise.
+// das at the reference's precision on the tuned shape, no spectrum dump: ONE launch, spectra never leave the CU.  Decide (das_f64_plan.hpp
+// das_f64_decide: a pure function of the batch's shape, the steering summary and the two switches names the kernel or declines), reserve the
+// scratch, fill the argument block, enqueue (das_f64_w64.hip), flip the double buffers.  BF_FUSED_BINS=0 keeps the chain (cross-checks).
+// BF_OK: handled; kDeclined: run_chain serves the batch; an error otherwise.
 int BinPipelineImpl::run_das_one_launch(const float *x, long F, float *y, hipStream_t stream, int layout, long mic_stride, const RunSnapshot &snap) {
-    if (!das_one_launch_shape() || switches().fused_bins != 1 || snap.das_gains_w64 == nullptr) return kDeclined;
-    const DasF64Launch d = das_f64_decide(layout, M_, S_, F, n_cus_, snap.das_mic0_unit, snap.das_slots.n_tr,
-                                          snap.das_gains_mic != nullptr && d_das_sched_.get() != nullptr);
+    const Switches &sw = switches();
+    if (!das_one_launch_shape() || sw.fused_bins != 1 || snap.das.gains_w64 == nullptr) return kDeclined;
+    const DasSlots &sl = snap.das.slots;
+    const DasF64Launch d = das_f64_decide(DasF64Shape{layout, M_, S_, n_cus_, F, sl.mic0_unit, snap.das.gains_mic && d_das_sched_.get(), sl.n_tr,
+                                                      sw.das_il_ring, sw.das_f64_sched});
     if (d.path == DasF64Path::kChain) return kDeclined;
     ENGINE_HIP(d_planar_.reserve((d.scratch_bytes + sizeof(float) - 1) / sizeof(float)));
     float *const hist = d_hist2_[hist_cur_].get();
@@ -317,12 +296,10 @@ int BinPipelineImpl::run_das_one_launch(const float *x, long F, float *y, hipStr
     da.x = x; da.hist = hist; da.hist_out = d_hist2_[hist_cur_ ^ 1].get(); da.y = y;
     da.tail_in = d_tail_[tail_cur_].get(); da.tail_out = d_tail_[tail_cur_ ^ 1].get();
     da.win = d_win_.get(); da.n_frames = F; da.mic_stride = mic_stride;
-    da.stream_stride_x = (long)M_ * F * H_; da.n_streams = S_; da.n_mics = M_; da.run_len = 1;
-    da.layout = layout;
-    da.gains = snap.das_gains_w64; da.gains_mic = snap.das_gains_mic; da.tw = d_tw_w64_.get();
-    da.mic0_unit = snap.das_mic0_unit ? 1 : 0;
-    da.n_tr = snap.das_slots.n_tr; da.extra_mic = snap.das_slots.extra_mic;
-    for (int k = 0; k < 8; ++k) da.slot_mic[k] = snap.das_slots.slot_mic[k];
+    da.stream_stride_x = (long)M_ * F * H_; da.n_streams = S_; da.n_mics = M_; da.run_len = 1; da.layout = layout;
+    da.gains = snap.das.gains_w64; da.gains_mic = snap.das.gains_mic; da.tw = d_tw_w64_.get();
+    da.mic0_unit = sl.mic0_unit ? 1 : 0; da.n_tr = sl.n_tr; da.extra_mic = sl.extra_mic;
+    for (int k = 0; k < 8; ++k) da.slot_mic[k] = sl.slot_mic[k];
     da.sched_ws = d_das_sched_.get(); da.sched_ws_bytes = d_das_sched_.get() ? das_f64_sched_ws_bytes() : 0;
     ENGINE_HIP(enqueue_das_f64(da, d, d_planar_.get(), stream, kev0, kev1, &kev_recorded));
     if (d.writes_hist)

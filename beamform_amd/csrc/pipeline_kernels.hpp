@@ -125,7 +125,8 @@ struct DasF64Args {
     const double *win;
     long n_frames, mic_stride, stream_stride_x;
     int n_streams, n_mics, run_len;
-    int layout = 0;        // bf_layout of x and hist; 1 (interleaved): das_f64_ring_kernel, das_f64_w64_kernel<1>
+    int layout = 0;        // bf_layout of x and hist as the kernel reads them: [sample][mic] for das_f64_ring_kernel and das_f64_w64_kernel<1>;
+                           // planar for das_f64_pair_kernel, also behind the transposition (enqueue_das_f64 then points x / hist at its scratch)
     float *hist_out = nullptr;         // das_f64_pair_kernel: receives the last hop of the batch (the ring-buffer carry), layout as hist
     const f64x2 *gains_mic = nullptr;  // das_mic_gains_w64_f64: per-microphone Hermitian gains of the frame-pair kernel (planar input)
     // das_f64_pair_kernel: the microphones that get a forward transform, in the order the kernel walks them (slot k -> microphone slot_mic[k],
@@ -140,28 +141,10 @@ struct DasF64Args {
     size_t ring_bytes = 0;
 };
 
-// What one batch of that node launches (das_f64_w64.hip): das_f64_decide settles it ONCE from the batch's shape, on the host and without
-// touching the device; enqueue_das_f64 carries it out.
-enum class DasF64Path {
-    kChain,      // none of the kernels here: the STFT -> per-bin -> ISTFT chain serves the batch
-    kFramePair,  // das_f64_pair_kernel on planar input
-    kRing,       // das_f64_ring_kernel: [sample][mic] input with 2, 4 or 8 microphones, transposed hop by hop into the blocks' rings
-    kTranspose,  // interleaved_to_planar_kernel (batch, carried hop) + das_f64_pair_kernel: [sample][mic] input otherwise
-    kMicPair,    // das_f64_w64_kernel<1>: [sample][mic] input with one microphone or a non-unit weight row 0
-};
-struct DasF64Launch {
-    DasF64Path path;
-    DasSchedPlan plan;                  // frame-pair kernels: the chunk plan
-    long run_frames, runs_per_stream;   // microphone-pair kernel: its static runs
-    size_t scratch_bytes;               // device scratch of enqueue_das_f64: the blocks' hop rings (kRing), the planar batch + carried hop (kTranspose)
-    bool writes_hist;                   // the kernel stores the carried hop into DasF64Args::hist_out itself (no copy behind it)
-};
-// mic0_unit, n_tr: as in DasF64Args; tables: the frame-pair kernels' gains (gains_mic) and work-queue workspace (sched_ws) exist
-DasF64Launch das_f64_decide(int layout, int n_mics, int n_streams, long n_frames, int n_cus, bool mic0_unit, int n_tr, bool tables);
-// `a` as for planar input with hist_out set; `scratch` = d.scratch_bytes of device memory; d.path != kChain.  kev0 / kev1 (nullable)
+// Carries out a DasF64Launch (das_f64_plan.hpp das_f64_decide; das_f64_w64.hip).
+// `a` describes the batch as it came in (x, hist and layout the handle's), hist_out set; `scratch` = d.scratch_bytes of device memory; d.path != kChain.  kev0 / kev1 (nullable)
 // are recorded on `s` right around the kernel, *kev_recorded is raised once the second record has succeeded (pipeline.hpp Engine::kev0)
 hipError_t enqueue_das_f64(DasF64Args a, const DasF64Launch &d, float *scratch, hipStream_t s, hipEvent_t kev0, hipEvent_t kev1, bool *kev_recorded);
-size_t das_f64_sched_ws_bytes();
 
 #ifdef BF_NFFT
 // Every launcher carries out its stage of a ChainPlan (chain_plan.hpp): the plan names the kernel and its template arguments, the launcher

@@ -68,9 +68,11 @@ enum bf_das_impl {
                              look directions that share their forward transforms */
     BF_DAS_F64 = 1        /* default: double arithmetic like das.cpp.  Period 512, <= 8 microphones, one look direction, no spectrum
                              dump: ONE launch of the frame-pair kernel (das_f64_pair_kernel on planar input; on [sample][mic] input
-                             das_f64_ring_kernel for 2, 4 or 8 microphones, a transposition in front of das_f64_pair_kernel otherwise; with one
-                             microphone or a non-unit weight row 0 the microphone-pair kernel das_f64_w64_kernel);
-                             anything else runs STFT -> per-bin kernel -> ISTFT and can dump the full N-bin spectrum */
+                             das_f64_ring_kernel for 2, 4 or 8 microphones, a transposition in front of das_f64_pair_kernel otherwise).
+                             The frame-pair kernel needs a second microphone and the reference's unit weight row 0: without them
+                             [sample][mic] input takes the microphone-pair kernel das_f64_w64_kernel, still one launch, and planar
+                             input the chain.  Anything else runs that chain, STFT -> per-bin kernel -> ISTFT, which can dump the
+                             full N-bin spectrum */
 };
 
 /* Arithmetic of what lies between the transforms (every node computes its per-bin stage in double).

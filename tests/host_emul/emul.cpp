@@ -600,6 +600,46 @@ extern "C" int emul_das_plan(long n_frames, int n_streams, int n_cus, const char
     return p.n_chunks;
 }
 
+// the plan's own members: out[19] = n_levels, cnt[8], size[8], n_chunks, grid
+static void das_plan_out(const bf::DasSchedPlan &p, long *out) {
+    out[0] = p.n_levels;
+    for (int i = 0; i < 8; ++i) { out[1 + i] = p.cnt[i]; out[9 + i] = p.size[i]; }
+    out[17] = p.n_chunks;
+    out[18] = p.grid;
+}
+extern "C" void emul_das_plan_levels(long n_frames, int n_streams, int n_cus, const char *env, long *out) {
+    das_plan_out(bf::das_f64_plan(n_frames, n_streams, n_cus, (env && *env) ? env : nullptr), out);
+}
+
+// ---- which kernel serves a batch of das in double (csrc/das_f64_plan.hpp das_f64_decide) -------------------------------------------------
+// in[9] = layout, n_mics, n_streams, n_frames, n_cus, mic0_unit, n_tr, tables, das_il_ring of a DasF64Shape, sched = its das_f64_sched ("" = unset);
+// out[24] = path (DasF64Path's order), run_frames, runs_per_stream, scratch_bytes, writes_hist, then the plan as emul_das_plan_levels
+extern "C" void emul_das_f64_decide(const long *in, const char *sched, long *out) {
+    bf::DasF64Shape c{};
+    c.layout = (int)in[0]; c.n_mics = (int)in[1]; c.n_streams = (int)in[2]; c.n_frames = in[3]; c.n_cus = (int)in[4];
+    c.mic0_unit = in[5] != 0; c.n_tr = (int)in[6]; c.tables = in[7] != 0; c.das_il_ring = (int)in[8];
+    c.das_f64_sched = (sched && *sched) ? sched : nullptr;
+    const bf::DasF64Launch d = bf::das_f64_decide(c);
+    out[0] = (long)d.path; out[1] = d.run_frames; out[2] = d.runs_per_stream; out[3] = (long)d.scratch_bytes; out[4] = d.writes_hist;
+    das_plan_out(d.plan, out + 5);
+}
+
+// ---- what das_f64_pair_kernel is told about a steering table (csrc/geometry.hpp das_f64_slots) -------------------------------------------
+// The das table of a geometry at N = 1024 as a cold handle builds it; zero_row0: with microphone 0's row cleared (quirk Q3).
+// out[11] = mic0_unit, n_tr, extra_mic, slot_mic[8]
+extern "C" void emul_das_f64_slots(int M, double sr, const double *mx, const double *my, double theta, int zero_row0, long *out) {
+    ArrayGeometry g;
+    g.set(mx, my, M);
+    SteeringSet st;
+    st.allocate(1024, M, 1);
+    st.update_column(g, frequency_vector(1024, sr), 0, theta, true);
+    if (zero_row0)
+        for (int j = 0; j < 1024; ++j) st.at(j, 0, 0) = 0;
+    const DasSlots sl = das_f64_slots(st);
+    out[0] = sl.mic0_unit; out[1] = sl.n_tr; out[2] = sl.extra_mic;
+    for (int k = 0; k < 8; ++k) out[3 + k] = sl.slot_mic[k];
+}
+
 // ---- which fused fp32 das kernel serves a batch and in which runs (csrc/das_fused_plan.hpp) ---------------------------------------------------
 #include "../../beamform_amd/csrc/das_fused_plan.hpp"
 // out[9] = kernel (DasFusedKernel's order), npl, unr, group, frames_per_chunk, chunks_per_stream, blocks, zero_run_heads, group_tables

@@ -54,7 +54,8 @@ static int run_case(int algo, int n_mics, int n_interf, int hops) {
             std::this_thread::sleep_for(std::chrono::microseconds(150));  // a topic, not a spin: std::mutex is not fair
         }
     });
-    for (int t = 0; t < hops; ++t) {
+    // `hops` callbacks at least; on a busy machine the control thread may start late, so go on until ten updates have landed beside them
+    for (int t = 0; t < hops || (updates.load() < 10 && t < 100 * hops); ++t) {
         rc = bf_process_hop(h, in.data(), out.data(), 512);
         if (rc != BF_OK) {
             fprintf(stderr, "bf_process_hop: %d %s\n", rc, bf_last_error(h));
@@ -69,7 +70,7 @@ static int run_case(int algo, int n_mics, int n_interf, int hops) {
     stop.store(true);
     ctl.join();
     bf_destroy(h);
-    printf("algo %d: %d hops, %ld control updates, %ld launches, %ld inconsistent batches\n", algo, hops, updates.load(),
+    printf("algo %d: at least %d hops, %ld control updates, %ld launches, %ld inconsistent batches\n", algo, hops, updates.load(),
            g_launches.load(), g_inconsistent.load());
     return bad || g_inconsistent.load() != 0 || updates.load() < 10;
 }

@@ -47,14 +47,17 @@ const KernelSet *kernel_set_n1024() { return &g_stub_set; }
 const KernelSet *kernel_set_n2048() { return &g_stub_set; }
 const KernelSet *kernel_set_n4096() { return &g_stub_set; }
 const KernelSet *kernel_set_n8192() { return &g_stub_set; }
-// das in double in one launch: a path without scratch whose kernel leaves the carried hop to the pipeline, and an enqueue that succeeds
-DasF64Launch das_f64_decide(int, int, int, long, int, bool, int, bool) {
-    DasF64Launch d{};
-    d.path = DasF64Path::kMicPair;
-    return d;
+// das in double in one launch: the decision (das_f64_plan.hpp) and the steering summary (geometry.hpp) are pure host arithmetic and run
+// for real; only carrying the decision out is stubbed.  The harness's das case is planar with a unit row 0: the frame-pair kernel, and
+// a walk that names every microphone past 0 exactly once, whichever table the batch was launched with.
+hipError_t enqueue_das_f64(DasF64Args a, const DasF64Launch &d, float *, hipStream_t, hipEvent_t, hipEvent_t, bool *) {
+    g_launches++;
+    unsigned seen = a.extra_mic > 0 ? 1u << a.extra_mic : 0;
+    int named = a.extra_mic > 0 ? 1 : 0;
+    for (int k = 0; k < a.n_tr; ++k, ++named) seen |= 1u << a.slot_mic[k];
+    if (d.path != DasF64Path::kFramePair || !a.mic0_unit || named != a.n_mics - 1 || seen != (1u << a.n_mics) - 2) g_inconsistent++;
+    return hipSuccess;
 }
-hipError_t enqueue_das_f64(DasF64Args, const DasF64Launch &, float *, hipStream_t, hipEvent_t, hipEvent_t, bool *) { return hipSuccess; }
-size_t das_f64_sched_ws_bytes() { return 256; }
 
 // the fused fp32 das decision is pure host arithmetic (das_fused_plan.hpp, through kernels.hpp): only carrying it out is stubbed
 hipError_t enqueue_das_fused(const DasFusedArgs &a, const DasFusedLaunch &, int, hipStream_t, hipEvent_t, hipEvent_t, bool *) {

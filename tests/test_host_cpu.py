@@ -555,3 +555,152 @@ def test_chain_switches_route_as_documented(emul_lib):
         assert names("gsc", 512, M, gsc_serial=1)[0][-1] == want, M
     assert names("gsc", 512, 2)[0][-1] == "gsc_nlms_par_kernel<1, 2>" and names("gsc", 512, 8)[0][-1] == "gsc_nlms_mw_kernel<8, 1, 2>"
     assert set(CHAIN_SWITCHES) == {"fused_bins", "stft_small", "stft_split", "mvdr_group", "gss_group", "gsc_serial"}
+
+
+# ---- the launch decision of das in double (csrc/das_f64_plan.hpp das_f64_decide, csrc/geometry.hpp das_f64_slots) ------------------------
+from das_f64_plan_util import (FRAME_PAIR_PATHS, das_f64_decide, das_f64_kernels, das_f64_slots, das_plan_levels, params_decide)   # noqa: E402
+
+DAS_F64_ONE_LAUNCH_ROWS = {("planar", 8): "das_f64_sched_kernel + das_f64_pair_kernel",
+                           ("[sample][mic]", 8): "das_f64_sched_kernel + das_f64_ring_kernel",
+                           ("planar", 3): "das_f64_sched_kernel + das_f64_pair_kernel"}
+
+
+def test_das_f64_decision_names_the_kernels_of_the_dispatch_table(emul_lib):
+    """Every das (double) row of docs/DISPATCH.md (traced on a GPU: 96 frames, one stream, 256 CUs, default switches) that reaches
+    das_f64_decide -- a spectrum dump and several look directions never do: the decision names the row's kernels, or the chain where the
+    row lists chain kernels.  mic0_unit and n_tr come from das_f64_slots on the row's geometry, as on a cold handle."""
+    one_launch, chained = {}, 0
+    for _, period, layout, mics, dirs, dump, kernels in (r for r in dispatch_rows() if r[0] == "das (double)"):
+        if dump == "yes" or int(dirs) > 1:
+            continue
+        M = int(mics)
+        over = {"mics": [(0.2, 0.0)] * M} if M > 16 else {}
+        p = make_params("das", n_mics=M, hop=int(period), **over)
+        d = params_decide(emul_lib, p, 96, 256, layout={"planar": 0, "[sample][mic]": 1}[layout])
+        if kernels.startswith("das_f64_"):
+            assert int(period) == 512 and " + ".join(das_f64_kernels(d)) == kernels, (period, layout, mics, d)
+            one_launch[(layout, M)] = kernels
+        else:
+            assert d["path"] == "chain", (period, layout, mics, d)
+            chained += 1
+    assert one_launch == DAS_F64_ONE_LAUNCH_ROWS, one_launch
+    assert chained >= 8    # the six other periods, 16 and 24 microphones
+
+
+def _das_f64_shapes():
+    """(layout, M, S, F, cus, mic0_unit, n_tr, tables): seeded random shapes and the corners of every branch."""
+    rng = np.random.default_rng(29)
+    fixed_F = [1, 2, 3, 5, 96, 97, 65_536, 1_000_003]
+    shapes = []
+    for i in range(400):
+        M = int(rng.integers(1, 11))
+        F = fixed_F[i % len(fixed_F)] if i % 2 == 0 else int(rng.integers(1, 300_000))
+        S = int(rng.integers(1, 41)) if i % 5 else int(rng.integers(200, 20_000))
+        n_tr = max(0, M - 1 - int(rng.integers(0, 2))) if i % 7 else 0
+        shapes.append((int(rng.integers(0, 2)), M, S, F, int(rng.choice([64, 256, 304])), bool(i % 11), n_tr, bool(i % 13)))
+    for lay in (0, 1):
+        for M in (1, 2, 8, 9):
+            for F in (1, 2, 3, 65_536):
+                shapes.append((lay, M, 1, F, 256, True, M - 1, True))
+        for M in (2, 3, 4, 5, 6, 7, 8):
+            shapes += [(lay, M, 300, 7, 256, True, M - 1, True),            # more streams than CUs
+                       (lay, M, 65_536, 65_536, 256, True, M - 1, True),    # 2^31 pairs exactly
+                       (lay, M, 65_536, 65_534, 256, True, M - 1, True),    # one pair per stream fewer: the plan, then the table's limit
+                       (lay, M, 16_384, 2, 256, True, M - 1, True),         # the table's last row
+                       (lay, M, 16_385, 2, 256, True, M - 1, True),         # one stream past it
+                       (lay, M, 1, 96, 256, True, M - 1, False),            # tables = false
+                       (lay, M, 1, 96, 256, False, M - 1, True),            # mic0_unit = false
+                       (lay, M, 1, 96, 256, True, 0, True)]                 # n_tr = 0
+    return shapes
+
+
+def _das_f64_expected_path(lay, M, S, F, unit, n_tr, tables, ring_switch, n_chunks):
+    """The issue's table of who serves what, written out on its own."""
+    if M > 8:
+        return "chain"
+    if not (tables and unit and M >= 2 and n_tr >= 1):
+        return "chain" if lay == 0 else "mic_pair"
+    if S * ((F + 1) // 2) >= 2 ** 31 or not 1 <= n_chunks <= 16384:
+        return "chain"
+    return "frame_pair" if lay == 0 else "ring" if M in (2, 4, 8) and ring_switch else "transpose"
+
+
+def test_das_f64_decision_is_consistent_on_random_shapes(emul_lib):
+    """A few hundred shapes at the default switches: every path appears exactly where it is built for, the microphone-pair kernel's runs
+    tile a stream within the budget of blocks, the scratch sizes are enqueue_das_f64's, and the frame-pair paths carry das_f64_plan's own
+    value.  The transposition serves every frame count from 1 on: the branch that once turned batches away for its 256-sample tiles could
+    never be taken (a hop is 512 samples)."""
+    seen = set()
+    for lay, M, S, F, cus, unit, n_tr, tables in _das_f64_shapes():
+        d = das_f64_decide(emul_lib, lay, M, S, F, cus, unit, n_tr, tables)
+        ctx = ((lay, M, S, F, cus, unit, n_tr, tables), d)
+        pairs_fit = S * ((F + 1) // 2) < 2 ** 31
+        plan = das_plan_levels(emul_lib, F, S, cus) if pairs_fit else None
+        path = d["path"]
+        seen.add(path)
+        assert path == _das_f64_expected_path(lay, M, S, F, unit, n_tr, tables, 1, plan["n_chunks"] if plan else 0), ctx
+        assert d["writes_hist"] == (path == "frame_pair"), ctx
+        if path == "mic_pair":
+            rf, runs = d["run_frames"], d["runs_per_stream"]
+            assert rf % 8 == 0 and (runs - 1) * rf < F <= runs * rf and runs <= max(1, cus // S), ctx
+        else:
+            assert (d["run_frames"], d["runs_per_stream"]) == (0, 0), ctx
+        want_scratch = {"ring": 4 * cus * 40 * M * 512, "transpose": 4 * S * M * 512 * (F + 1)}.get(path, 0)
+        assert d["scratch_bytes"] == want_scratch, ctx
+        if path in FRAME_PAIR_PATHS:
+            assert d["plan"] == plan and 1 <= plan["n_chunks"] <= 16384, ctx
+        elif not pairs_fit:
+            assert not any(d["plan"].values()), ctx      # 2^31 pairs are turned away before the plan's int arithmetic sees them
+    assert seen == {"chain", "frame_pair", "ring", "transpose", "mic_pair"}
+    for M in (3, 5, 6, 7):       # the transposition takes every frame count
+        for F in list(range(1, 20)) + [255, 256, 257, 65_535]:
+            assert das_f64_decide(emul_lib, 1, M, 1, F, 256)["path"] == "transpose", (M, F)
+
+
+def test_das_f64_switches_change_only_what_they_name(emul_lib):
+    """BF_DAS_IL_RING=0 turns every ring batch into a transposition (with the transposition's scratch) and touches nothing else;
+    BF_DAS_F64_SCHED changes only the chunk plan, and that plan is das_f64_plan's for the same string."""
+    ring_seen = plans_differ = 0
+    for lay, M, S, F, cus, unit, n_tr, tables in _das_f64_shapes():
+        base = das_f64_decide(emul_lib, lay, M, S, F, cus, unit, n_tr, tables)
+        off = das_f64_decide(emul_lib, lay, M, S, F, cus, unit, n_tr, tables, das_il_ring=0)
+        if base["path"] == "ring":
+            ring_seen += 1
+            assert off == {**base, "path": "transpose", "scratch_bytes": 4 * S * M * 512 * (F + 1)}, (lay, M, S, F, off)
+        else:
+            assert off == base, (lay, M, S, F, off)
+        for sched in (b"0", b"5,3,1", b"104,8,4,2", b"1"):
+            d = das_f64_decide(emul_lib, lay, M, S, F, cus, unit, n_tr, tables, sched=sched)
+            assert {**d, "plan": None} == {**base, "plan": None}, (lay, M, S, F, sched, d)
+            if d["path"] in FRAME_PAIR_PATHS:
+                assert d["plan"] == das_plan_levels(emul_lib, F, S, cus, sched), (lay, M, S, F, sched)
+                plans_differ += d["plan"] != base["plan"]
+    assert ring_seen >= 30 and plans_differ >= 100
+
+
+def test_das_f64_slots_merge_identical_rows_and_know_row_0(emul_lib):
+    """geometry.hpp das_f64_slots, what BinPipelineImpl::upload_steering hands the frame-pair kernels: is row 0 identically 1, the first pair
+    of microphones past 0 whose weight rows coincide (slot 0 + extra_mic), the others in ascending order."""
+    def check(mics, theta, **kw):
+        sl = das_f64_slots(emul_lib, mics, theta, **kw)
+        named = sl["slot_mic"][:sl["n_tr"]] + ([sl["extra_mic"]] if sl["extra_mic"] >= 0 else [])
+        assert sorted(named) == list(range(1, len(mics))), (mics, theta, sl)     # every microphone past 0 exactly once
+        return sl
+    bench = make_params("das", n_mics=8)["mics"]      # aira16's first eight: microphones 1 and 7 share (x, y)
+    for theta in (0.0, 20.0, -75.0, 135.0, 180.0, 33.3):
+        sl = check(bench, theta)
+        assert (sl["mic0_unit"], sl["n_tr"], sl["extra_mic"], sl["slot_mic"][:6]) == (True, 6, 7, [1, 2, 3, 4, 5, 6]), (theta, sl)
+        z = check(bench, theta, zero_row0=True)         # quirk Q3: row 0 left at zero -- not a unit row, the walk is the same
+        assert not z["mic0_unit"] and {**z, "mic0_unit": True} == sl, (theta, z)
+    for M in (2, 3, 5, 7):                              # no coinciding (x, y): everyone past 0 in ascending order
+        sl = check(make_params("das", n_mics=M)["mics"], 20.0)
+        assert (sl["mic0_unit"], sl["n_tr"], sl["extra_mic"], sl["slot_mic"][:M - 1]) == (True, M - 1, -1, list(range(1, M))), (M, sl)
+    # A uniform linear array at broadside, every delay equal: the FIRST pair is (1, 2).  The rows must coincide bit for bit, which rounding
+    # denies a horizontal line (cos(90 degrees) is 6e-17 times each distance); a vertical line has it exactly, the reference drops z.
+    line = [(0.05, 0.12)] * 6
+    sl = check(line, 40.0)
+    assert (sl["n_tr"], sl["extra_mic"], sl["slot_mic"][:4]) == (4, 2, [1, 3, 4, 5]), sl
+    one = check([(0.1, 0.2)], 10.0)
+    assert (one["mic0_unit"], one["n_tr"], one["extra_mic"]) == (True, 0, -1), one
+    two = check([(0.1, 0.2), (-0.1, 0.0)], 10.0)
+    assert (two["n_tr"], two["extra_mic"], two["slot_mic"][0]) == (1, -1, 1), two
