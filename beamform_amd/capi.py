@@ -34,8 +34,10 @@ EXPORTS = (
     "bf_resampler_process_device", "bf_resampler_process", "bf_resampler_destroy", "bf_resampler_default_table",
     "bf_resampler_set_mode", "bf_resampler_callback", "bf_resampler_callback_device",
     "bf_doa_create", "bf_doa_set_phat_floor", "bf_doa_process_device", "bf_doa_process", "bf_doa_reset", "bf_doa_destroy",
+    "bf_track_set_angles", "bf_process_batch_device_tracked", "bf_track_from_peaks_device",
 )
 BF_DOA_MAX_ANGLES = 1024
+BF_TRACK_MAX_ANGLES = 1024   # = BF_DOA_MAX_ANGLES: a Doa peak index is a track index
 
 
 class BfConfig(C.Structure):
@@ -199,6 +201,10 @@ def load():
     L.bf_doa_reset.argtypes = [C.c_void_p]
     L.bf_doa_destroy.argtypes = [C.c_void_p]
     L.bf_doa_destroy.restype = None
+    L.bf_track_set_angles.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
+    L.bf_process_batch_device_tracked.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bf_track_from_peaks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_double,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -543,6 +549,19 @@ class Beamformer:
         self._chk(self._L.bf_process_batch_device(self._h, x_ptr, n_frames, y_ptr, spectrum_ptr or None, stream or None),
                   "bf_process_batch_device")
 
+    def set_track_angles(self, angles):
+        """Installs the candidate angles (degrees) of steering tracks: one table per angle, the one set_theta(angle) would build
+        (bf_track_set_angles; host-synchronous).  An empty list drops them.  das in double, phase and phasempf with one look direction."""
+        a = np.ascontiguousarray(angles, np.float64).ravel()
+        ptr = a.ctypes.data_as(C.POINTER(C.c_double)) if a.size else None
+        self._chk(self._L.bf_track_set_angles(self._h, ptr, int(a.size)), "bf_track_set_angles")
+
+    def process_device_tracked(self, x_ptr: int, n_frames: int, y_ptr: int, track_ptr: int, spectrum_ptr: int = 0, stream: int = 0):
+        """process_device with a look angle per frame: track_ptr -> int32 [n_streams][n_frames] on the device, frame t of stream s is
+        weighted with the table of angle track[s][t]; any index outside the installed angles (-1, say) means the handle's own theta."""
+        self._chk(self._L.bf_process_batch_device_tracked(self._h, x_ptr, n_frames, y_ptr, spectrum_ptr or None, track_ptr or None,
+                                                          stream or None), "bf_process_batch_device_tracked")
+
     def process_device_strided(self, x_ptr: int, n_frames: int, y_ptr: int, mic_stride: int, stream: int = 0):
         """process_device on a column range of a longer planar buffer (microphone m at x_ptr + m * mic_stride samples)."""
         self._chk(self._L.bf_process_batch_device_strided(self._h, x_ptr, n_frames, y_ptr, stream or None, mic_stride),
@@ -563,6 +582,20 @@ class Beamformer:
 
     def set_state(self, blob: bytes):
         self._chk(self._L.bf_set_state(self._h, blob, len(blob)), "bf_set_state")
+
+
+def track_from_peaks_device(peak_ptr: int, map_ptr: int, n_angles: int, n_streams: int, n_blocks: int, frames_per_block: int,
+                            latency_blocks: int, min_peak: float, carry_ptr: int, track_ptr: int, stream: int = 0):
+    """Doa peaks [n_streams][n_blocks] (and maps, 0 = none when min_peak <= 0) -> the steering track [n_streams][n_blocks * frames_per_block]
+    of their frames, on the device (bf_track_from_peaks_device): every frame of block b gets the peak of the latest block
+    <= b - latency_blocks whose map value at the peak is not below min_peak, carry[s] where there is none; carry [n_streams] int32 is
+    updated so that the next call continues the stream (start with -1: the handle's theta)."""
+    L = load()
+    rc = L.bf_track_from_peaks_device(peak_ptr or None, map_ptr or None, int(n_angles), int(n_streams), int(n_blocks),
+                                      int(frames_per_block), int(latency_blocks), float(min_peak), carry_ptr or None, track_ptr or None,
+                                      stream or None)
+    if rc:
+        raise BfError(rc, "bf_track_from_peaks_device", (L.bf_last_error(None) or b"").decode() or L.bf_strerror(rc).decode())
 
 
 class Doa:

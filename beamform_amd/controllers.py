@@ -312,3 +312,36 @@ def follow_doa(node, doa, x: np.ndarray, frames_per_block: int, controller):
             node.set_theta(theta)
             published.append((b, theta))
     return np.concatenate(ys), published
+
+
+def follow_doa_device(node, doa, x: np.ndarray, frames_per_block: int, min_peak: float = 0.0):
+    """follow_doa with DoaTheta(doa.angles, min_peak) for a whole recording in three enqueues on one stream and no host synchronisation
+    in between: doa.process_device (maps and peaks of every block), track_from_peaks_device (latency 1, carry -1: block b is steered
+    by what the latest block before it published, block 0 and everything in front of the first publication by the node's own theta)
+    and node.process_device_tracked.  Peaks and maps come back once, at the end, for the list of publications.
+
+    node: beamform_amd.capi.Beamformer (das in double, phase or phasempf, one stream); its track angles are replaced by doa.angles and
+    its theta is left at the last published angle, as follow_doa leaves it.  doa: beamform_amd.capi.Doa on the same geometry, one
+    stream, W = frames_per_block.  x: [M, F*hop] float32 on the host, F a multiple of frames_per_block.
+    Returns (y [F*hop], published: list of (block index, theta))."""
+    import torch
+    from .capi import track_from_peaks_device
+    H, W = node.H, int(frames_per_block)
+    F = x.shape[1] // H
+    nb, A = F // W, int(doa.angles.size)
+    node.set_track_angles(doa.angles)
+    st = torch.cuda.current_stream().cuda_stream
+    xd = torch.from_numpy(np.ascontiguousarray(x, np.float32)).cuda()
+    maps = torch.empty((nb, A), dtype=torch.float64, device="cuda")
+    peaks = torch.empty((nb,), dtype=torch.int32, device="cuda")
+    carry = torch.full((1,), -1, dtype=torch.int32, device="cuda")
+    track = torch.empty((nb * W,), dtype=torch.int32, device="cuda")
+    yd = torch.empty((nb * W * H,), dtype=torch.float32, device="cuda")
+    doa.process_device(xd.data_ptr(), nb * W, maps.data_ptr(), peaks.data_ptr(), st)
+    track_from_peaks_device(peaks.data_ptr(), maps.data_ptr(), A, 1, nb, W, 1, min_peak, carry.data_ptr(), track.data_ptr(), st)
+    node.process_device_tracked(xd.data_ptr(), nb * W, yd.data_ptr(), track.data_ptr(), 0, st)
+    y, pk, mp = yd.cpu().numpy(), peaks.cpu().numpy(), maps.cpu().numpy()
+    published = [(b, float(doa.angles[pk[b]])) for b in range(nb) if not mp[b, pk[b]] < min_peak]
+    if published:
+        node.set_theta(published[-1][1])
+    return y, published

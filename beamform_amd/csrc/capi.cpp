@@ -162,12 +162,17 @@ int timing_collect(bf_handle *h, float *ms_mean, int *n_launches) {
     return BF_OK;
 }
 
+// track (nullable): the batch's steering track, [stream][frame] indices into the tables bf_track_set_angles installed
 int run_batch_device(bf_handle *h, const float *x_dev, size_t n_frames, float *y_dev, void *spectrum_dev, hipStream_t s,
-                     int layout, long mic_stride) {
+                     int layout, long mic_stride, const int32_t *track = nullptr) {
     if (n_frames == 0) return BF_OK;
     RunSnapshot snap;
     int rc = sync_tables(h, s, &snap);
     if (rc != BF_OK) return rc;
+    if (track) {
+        if (snap.track_n == 0) return fail(h, BF_EINVAL, "tracked batch: no track angles installed (bf_track_set_angles)");
+        snap.track = track;
+    }
     // the engine brackets its dominant kernel with this pair when it has one (fused fp32 das, das fp64 in one launch); otherwise the pair
     // stays unrecorded and the session's mean is taken over nothing (callers fall back to the call time)
     hipEvent_t k0 = nullptr, k1 = nullptr;
@@ -428,6 +433,48 @@ int bf_process_batch_device(bf_handle *h, const float *x_dev, size_t n_frames, f
     BF_HIP(h, hipSetDevice(h->device));
     return run_batch_device(h, x_dev, n_frames, y_dev, spectrum_dev, (hipStream_t)hip_stream, h->cfg.layout,
                             (long)n_frames * h->H);
+}
+
+// ---- steering tracks ---------------------------------------------------------------------------------------------------------------
+// One table per candidate angle: the bytes bf_set_theta(h, angle) would leave in look direction 0's table (the same update_weights
+// code; microphone 0's row as it stands: written by the cold start, quirk Q3).  Device layout [angle][mic][N].
+int bf_track_set_angles(bf_handle *h, const double *angles_deg, int n_angles) {
+    if (!h) return BF_EINVAL;
+    if (!h->engine->can_track()) return fail(h, BF_ENOSYS, "steering tracks: das in double, phase and phasempf with one look direction");
+    if (n_angles < 0 || n_angles > BF_TRACK_MAX_ANGLES) return fail(h, BF_EINVAL, "bf_track_set_angles: n_angles must be 0 .. BF_TRACK_MAX_ANGLES");
+    if (n_angles > 0 && !angles_deg) return fail(h, BF_EINVAL, "bf_track_set_angles: angles is NULL");
+    for (int a = 0; a < n_angles; ++a)
+        if (!std::isfinite(angles_deg[a])) return fail(h, BF_EINVAL, "bf_track_set_angles: angle not finite");
+    const size_t per = (size_t)h->M * h->N;
+    if (per * (size_t)n_angles * sizeof(f64x2) > (512ull << 20))
+        return fail(h, BF_EINVAL, "bf_track_set_angles: tables (angles x mics x bins) above 512 MiB");
+    BF_HIP(h, hipSetDevice(h->device));
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::vector<f64x2> t(per * (size_t)n_angles);
+    SteeringSet st;
+    st.allocate(h->N, h->M, 1);
+    for (int j = 0; j < h->N; ++j) st.at(j, 0, 0) = h->steer[0].at(j, 0, 0);
+    for (int a = 0; a < n_angles; ++a) {
+        st.update_column(h->geo, h->freqs, 0, angles_deg[a], false);
+        for (int m = 0; m < h->M; ++m)
+            for (int j = 0; j < h->N; ++j) {
+                const cplxd w = st.at(j, m, 0);
+                t[(size_t)a * per + (size_t)m * h->N + j] = f64x2{w.real(), w.imag()};
+            }
+    }
+    const int rc = h->engine->install_track_tables(t, n_angles);
+    return rc == BF_OK ? BF_OK : fail(h, rc, h->engine->error().c_str());
+}
+
+int bf_process_batch_device_tracked(bf_handle *h, const float *x_dev, size_t n_frames, float *y_dev, void *spectrum_dev,
+                                    const int32_t *track_dev, void *hip_stream) {
+    if (!h || !x_dev || !y_dev) return BF_EINVAL;
+    if (h->n_dirs > 1) return fail(h, BF_EINVAL, "tracked batch: one look direction per handle");
+    if (!h->engine->can_track()) return fail(h, BF_ENOSYS, "steering tracks: das in double, phase and phasempf with one look direction");
+    if (!track_dev) return fail(h, BF_EINVAL, "tracked batch: track is NULL");
+    BF_HIP(h, hipSetDevice(h->device));
+    return run_batch_device(h, x_dev, n_frames, y_dev, spectrum_dev, (hipStream_t)hip_stream, h->cfg.layout, (long)n_frames * h->H,
+                            track_dev);
 }
 
 void *bf_host_alloc(size_t bytes) {

@@ -15,7 +15,8 @@ namespace bf {
 // batch (look direction + interferers; 1 unless lcmv / gss).  band_yh_lo / band_yh_hi: the in-band problems of mvdr / lcmv
 // (BinPipelineImpl::init).  aligned16: the output pointer is 16-byte aligned (device workspaces always are).  The last six: the switches of
 // those names (switches.hpp).  gss_rows (last, so that a shape written without it means one): separated sources gss emits per beam
-// (bf_config.gss_out_sources; 0 = 1, ignored by every other node).
+// (bf_config.gss_out_sources; 0 = 1, ignored by every other node).  track (last again: a shape written without it means false): the batch
+// carries a steering track (bf_process_batch_device_tracked: a table index per (stream, frame); das / phase / phasempf, one look direction).
 struct ChainShape {
     int algo, n_fft, layout, n_mics, n_streams, n_dirs, kp1, past_windows, precision;
     bool dump;
@@ -27,6 +28,7 @@ struct ChainShape {
     int gss_group;
     bool gsc_serial;
     int gss_rows;
+    bool track;
 };
 
 // The kernels of each stage, template arguments behind them as ChainPlan holds them:
@@ -36,6 +38,8 @@ struct ChainShape {
 //          cov2d_kernel<km, wps, !z48>, mvdr_lcmv_kernel<mp, km>, gss_kernel<mp, km>, gss_lane_kernel<mp, km>
 //   rec    phasempf's pass over the frames: mpf_recursion_kernel, or mpf_rec_istft_kernel, which runs the backward transform too
 //   istft  istft_w64_kernel<band_rows>, istft32_kernel, istft_small_kernel, istft_split_kernel, istft_generic_kernel + ola_generic_kernel
+//          with ChainPlan::track their twins that resolve the steering table per frame: stft_bins_w64_track_kernel + fused_tail_track_kernel,
+//          pointwise_track_kernel<mp, algo>, mpf_mask_track_kernel<mp>
 //   tail   smooth4_kernel<t0> or smooth_kernel, then smooth_state_kernel (phasempf); gsc_nlms_kernel / gsc_nlms_par_kernel <t0 = NBM, t1 = KPL>
 //          or gsc_nlms_mw_kernel<t0 = NW, t1 = NBL, t2 = KPL> (gsc)
 enum class ChainFront { kStft, kStftSmall, kStftWave2048, kStftGeneric, kFusedW64, kFusedSmall, kFusedSplit };
@@ -62,6 +66,8 @@ struct ChainPlan {
     // gss: rows per beam behind the per-bin stage (1: gss_kernel / gss_lane_kernel store y_fft = this_yf(0), gss.cpp:120-121; more: their
     // _all variants store this_yf(0 .. rows - 1) as output streams beam * rows + r, and everything behind them runs over So * rows streams)
     int rows;
+    // the front / per-bin kernels are the track twins: the steering pointer of a frame comes from the batch's track (BinsArgs::track)
+    bool track;
     bool fused() const { return front >= ChainFront::kFusedW64; }
     bool rec_istft() const { return rec == ChainRec::kRecIstft; }
 };
@@ -83,8 +89,10 @@ inline ChainPlan chain_decide(const ChainShape &c) {
     const int mp4 = M <= 4 ? 4 : M <= 8 ? 8 : M <= 16 ? 16 : 32, km = kp1 <= 1 ? 1 : 4;
     ChainPlan p{};
     p.algo = a; p.layout = c.layout; p.z48 = cov && mixed; p.rows = R;
-    // nodes without a frame history, up to 8 microphones, one look direction: STFT and per-bin stage in one launch, spectra never leave the CU
-    const bool fused = c.fused_bins != 0 && N <= 2048 && M <= 8 && D == 1 && (pointwise || mpf);
+    p.track = c.track && D == 1 && (pointwise || mpf);
+    // nodes without a frame history, up to 8 microphones, one look direction: STFT and per-bin stage in one launch, spectra never leave the CU.
+    // A tracked batch only at N = 1024: the fused fronts of the other sizes keep a thread's steering entries in registers across frames
+    const bool fused = c.fused_bins != 0 && N <= 2048 && M <= 8 && D == 1 && (pointwise || mpf) && (!p.track || N == 1024);
     // the register-resident transforms of the other sizes (stft_small / stft_split = 0: the generic kernels; the fused front has no generic twin)
     const bool small = N <= 512 && c.stft_small, split = N == 2048 && c.stft_split;
     if (fused) p.front = N == 1024 ? ChainFront::kFusedW64 : N == 2048 ? ChainFront::kFusedSplit : ChainFront::kFusedSmall;

@@ -298,6 +298,29 @@ int bf_doa_process(bf_doa *d, const float *x_host, size_t n_frames, double *map_
     return BF_OK;
 }
 
+// ---- steering tracks: from the peaks of the maps to a table index per frame (no handle) ---------------------------------------------
+int bf_track_from_peaks_device(const int32_t *peak_dev, const double *map_dev, int n_angles, int n_streams, size_t n_blocks,
+                               int frames_per_block, int latency_blocks, double min_peak, int32_t *carry_dev, int32_t *track_dev,
+                               void *hip_stream) {
+    if (n_angles < 1 || n_streams < 1 || frames_per_block < 1 || latency_blocks < 0)
+        return fail(nullptr, BF_EINVAL, "bf_track_from_peaks_device: n_angles, n_streams, frames_per_block >= 1 and latency_blocks >= 0");
+    if (!peak_dev || !carry_dev || !track_dev) return fail(nullptr, BF_EINVAL, "bf_track_from_peaks_device: peak, carry or track is NULL");
+    if (!map_dev && min_peak > 0) return fail(nullptr, BF_EINVAL, "bf_track_from_peaks_device: min_peak > 0 needs the map");
+    if (n_blocks == 0) return BF_OK;  // carry stays: what block 0 of the next call gets
+    TrackFromPeaksArgs a;
+    a.peak = peak_dev;
+    a.map = map_dev;
+    a.carry = carry_dev;
+    a.track = track_dev;
+    a.min_peak = min_peak;
+    a.n_blocks = (long)n_blocks;
+    a.n_angles = n_angles;
+    a.frames_per_block = frames_per_block;
+    a.latency = latency_blocks;
+    DOA_HIP(nullptr, launch_track_from_peaks(a, n_streams, (hipStream_t)hip_stream));
+    return BF_OK;
+}
+
 int bf_doa_reset(bf_doa *d) {
     if (!d) return fail(nullptr, BF_EINVAL, "bf_doa_reset: handle is NULL");
     DOA_HIP(d, hipSetDevice(d->device));

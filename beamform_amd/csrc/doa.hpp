@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <string>
 
 #include "geometry.hpp"
@@ -38,10 +39,22 @@ struct DoaReduceArgs {
     int n_streams, n_angles, n_segments, frames_per_block;
 };
 
+// bf_track_from_peaks_device: peaks (and maps) of the blocks -> the steering track of their frames
+struct TrackFromPeaksArgs {
+    const int32_t *peak;       // [stream][n_blocks]
+    const double *map;         // [stream][n_blocks][n_angles]; null: every block publishes
+    int32_t *carry;            // [stream]: in, the index in force in front of block 0; out, the one a block n_blocks would get
+    int32_t *track;            // [stream][n_blocks * frames_per_block]
+    double min_peak;
+    long n_blocks;
+    int n_angles, frames_per_block, latency;
+};
+
 // per hop of x (hops -1 .. n_frames-1, hop -1 = hist) the microphones with a nonzero sample: layout as the stft kernel reads it
 hipError_t launch_doa_hop_flags(const float *x, const float *hist, unsigned *flags, long n_frames, long mic_stride, long stream_stride_x,
                                 int n_streams, int n_mics, int hop, int layout, hipStream_t s);
 hipError_t launch_doa_map(const DoaMapArgs &a, hipStream_t s);
 hipError_t launch_doa_reduce(const DoaReduceArgs &a, hipStream_t s);
+hipError_t launch_track_from_peaks(const TrackFromPeaksArgs &a, int n_streams, hipStream_t s);
 
 }  // namespace bf

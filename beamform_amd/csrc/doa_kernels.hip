@@ -240,6 +240,46 @@ __global__ __launch_bounds__(kDoaBlock) void doa_reduce_kernel(DoaReduceArgs a) 
     if (tid == 0) a.peak[(long)s * a.map_blocks + a.block0 + b] = bi[0];
 }
 
+// One wavefront per stream walks the blocks, 64 at a time.  V(k) = the index published by the latest block <= k that published (a block
+// publishes its peak when the map value there is not below min_peak), the carry where there is none; the frames of block b get
+// V(b - latency).  Lane l of a round holds k = k0 + l: the published lanes as a ballot, the latest one at or below l through one shuffle.
+__global__ __launch_bounds__(64) void track_from_peaks_kernel(TrackFromPeaksArgs a) {
+    const int lane = threadIdx.x, W = a.frames_per_block, L = a.latency;
+    const long s = blockIdx.x, nb = a.n_blocks;
+    const int *peak = a.peak + s * nb;
+    const double *map = a.map ? a.map + s * nb * a.n_angles : nullptr;
+    int *trk = a.track + s * nb * W;
+    const int c_in = a.carry[s];
+    // blocks 0 .. latency-1: no block of this call is old enough
+    const long n_head = (L < nb ? (long)L : nb) * W;
+    for (long i = lane; i < n_head; i += 64) trk[i] = c_in;
+    const long klast = nb - L < nb - 1 ? nb - L : nb - 1;  // V(klast) is what a block n_blocks would get
+    int cur = c_in;                                        // V(k0 - 1)
+    for (long k0 = 0; k0 <= klast; k0 += 64) {
+        const long k = k0 + lane;
+        int p = 0;
+        bool pub = false;
+        if (k <= klast) {
+            p = peak[k];
+            if (map == nullptr) pub = true;
+            else if (p >= 0 && p < a.n_angles) pub = !(map[k * a.n_angles + p] < a.min_peak);
+        }
+        const unsigned long long m = __ballot(pub);
+        const unsigned long long below = m & (lane == 63 ? ~0ull : ((2ull << lane) - 1));
+        const int src = below ? 63 - __clzll((long long)below) : 0;
+        const int got = __shfl(p, src, 64);
+        const int v = below ? got : cur;
+        for (long i = lane; i < 64L * W; i += 64) {  // the frames of blocks k0 + latency ..., consecutive lanes on consecutive frames
+            const int bl = (int)(i / W);
+            const int vv = __shfl(v, bl, 64);
+            const long kk = k0 + bl;
+            if (kk <= klast && kk + L < nb) trk[(kk + L) * W + (i - (long)bl * W)] = vv;
+        }
+        cur = __shfl(v, 63, 64);  // lanes past klast publish nothing: V(klast) at the end
+    }
+    if (lane == 0) a.carry[s] = cur;
+}
+
 }  // namespace
 
 hipError_t launch_doa_hop_flags(const float *x, const float *hist, unsigned *flags, long n_frames, long mic_stride, long stream_stride_x,
@@ -266,6 +306,11 @@ hipError_t launch_doa_map(const DoaMapArgs &a, hipStream_t s) {
 
 hipError_t launch_doa_reduce(const DoaReduceArgs &a, hipStream_t s) {
     BF_LAUNCH(doa_reduce_kernel, dim3((unsigned)a.n_blocks, (unsigned)a.n_streams), dim3(kDoaBlock), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_track_from_peaks(const TrackFromPeaksArgs &a, int n_streams, hipStream_t s) {
+    BF_LAUNCH(track_from_peaks_kernel, dim3((unsigned)n_streams), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

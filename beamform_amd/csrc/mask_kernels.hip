@@ -92,7 +92,9 @@ __device__ __forceinline__ float pair_phase_mean_f(const float (&ph)[MP], int M)
             }
     return tot / (float)(M * (M - 1) / 2);  // 0/0 = NaN when M == 1: falls through to the double path
 }
-template <int MP>
+// HALVES: the rare redo in double runs its MP arctangents as two groups of MP / 2 (element for element the same operations and results;
+// half the registers at the peak, for the one fused instantiation that would not fit the register file otherwise)
+template <int MP, bool HALVES = false>
 __device__ __forceinline__ bool phase_is_close(const double (&uy)[MP], const double (&ux)[MP], int M, double thr) {
     float fy[MP], fx[MP], ph[MP];
     bool odd = false;  // an argument the float range cannot carry (|u| of [-1,1] audio spectra sits around 1e-3 .. 1e3)
@@ -108,7 +110,23 @@ __device__ __forceinline__ bool phase_is_close(const double (&uy)[MP], const dou
     const bool unsure = odd || !(__builtin_fabsf(mean - thrf) > 1e-4f);
     if (__builtin_amdgcn_ballot_w64(unsure) != 0) {  // rare: the reference's arithmetic for this wavefront
         double pd[MP];
-        atan2_fast_n<MP>(uy, ux, pd);
+        if (HALVES) {
+            constexpr int HP = MP / 2;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                double hy[HP], hx[HP], hp[HP];
+#pragma unroll
+                for (int m = 0; m < HP; ++m) {
+                    hy[m] = uy[h * HP + m];
+                    hx[m] = ux[h * HP + m];
+                }
+                atan2_fast_n<HP>(hy, hx, hp);
+#pragma unroll
+                for (int m = 0; m < HP; ++m) pd[h * HP + m] = hp[m];
+            }
+        } else {
+            atan2_fast_n<MP>(uy, ux, pd);
+        }
         return pair_phase_mean<MP>(pd, M) < thr;
     }
     return mean < thrf;
@@ -184,7 +202,7 @@ __device__ __forceinline__ cd phase_bin(const BinCtx &c, const bf_config &cfg) {
 }
 
 // the binary phase mask of phasempf.cpp:210-248 for bin j >= 1: out_soi and |out_int|^2
-template <int MP>
+template <int MP, bool HALVES = false>
 __device__ __forceinline__ void mpf_mask_core(const cd (&X)[MP], const cd (&w)[MP], int M, const bf_config &cfg, cd &soi_out,
                                               double &int2_out) {
     double uy[MP], ux[MP], ab[MP];
@@ -197,7 +215,7 @@ __device__ __forceinline__ void mpf_mask_core(const cd (&X)[MP], const cd (&w)[M
         ux[m] = u.x;
         if (m < M) mag += ab[m];
     }
-    const bool is_soi = phase_is_close<MP>(uy, ux, M, cfg.min_phase * M_PI / 180);
+    const bool is_soi = phase_is_close<MP, HALVES>(uy, ux, M, cfg.min_phase * M_PI / 180);
     mag = div_rcp(mag, (double)M, 1.0 / (double)M);
     const double lo = mag * cfg.min_mag;
     const double msoi = is_soi ? mag : lo, mint = is_soi ? lo : mag;
@@ -216,8 +234,16 @@ __device__ __forceinline__ void mpf_mask_core(const cd (&X)[MP], const cd (&w)[M
     int2_out = norm2(in);
 }
 
-template <int MP, int ALGO>
-__global__ __launch_bounds__(256) void pointwise_bins_kernel(BinsArgs a) {
+// The steering table of frame t of stream s in a tracked batch (BinsArgs::track): the table the track names, the batch's own /theta table
+// for every index that names none (a bad index is never read through)
+__device__ __forceinline__ const f64x2 *track_steer(const BinsArgs &b, long sf) {
+    const int i = b.track[sf];  // sf = stream * n_frames + frame
+    return (unsigned)i < (unsigned)b.track_n ? b.track_tables + (long)i * b.track_stride : b.steer;
+}
+
+// (two kernels, one body: TRACK takes the steering pointer per frame from the batch's track; tracked batches have one look direction)
+template <int MP, int ALGO, bool TRACK>
+__device__ __forceinline__ void pointwise_body(const BinsArgs &a) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long total = (long)a.n_streams * a.n_frames * kNQ;
     if (idx >= total) return;
@@ -228,7 +254,7 @@ __global__ __launch_bounds__(256) void pointwise_bins_kernel(BinsArgs a) {
     const int NP = (a.n_mics + 1) >> 1;
     BinCtx c;
     c.Zf = a.Z + (((long)(s / a.n_dirs) * a.frames_ws + a.frame_off + t) * NP) * kN;
-    c.steer = a.steer + (long)(s % a.n_dirs) * a.steer_dir_stride;
+    c.steer = TRACK ? track_steer(a, st) : a.steer + (long)(s % a.n_dirs) * a.steer_dir_stride;
     c.M = a.n_mics;
     c.q = q;
     cd y;
@@ -238,6 +264,10 @@ __global__ __launch_bounds__(256) void pointwise_bins_kernel(BinsArgs a) {
         y = phase_bin<MP>(c, a.cfg);
     st_y(a, ((long)s * a.n_frames + t) * kYhStride + q, q, y);
 }
+template <int MP, int ALGO>
+__global__ __launch_bounds__(256) void pointwise_bins_kernel(BinsArgs a) { pointwise_body<MP, ALGO, false>(a); }
+template <int MP, int ALGO>
+__global__ __launch_bounds__(256) void pointwise_track_kernel(BinsArgs a) { pointwise_body<MP, ALGO, true>(a); }
 
 
 // ======================================================================================
@@ -245,8 +275,8 @@ __global__ __launch_bounds__(256) void pointwise_bins_kernel(BinsArgs a) {
 // ======================================================================================
 // Pass 1, one thread per (stream, frame, problem): the binary phase mask of phasempf.cpp:210-248.
 // out_soi goes to Yh (complex), |out_int|^2 to aux.
-template <int MP>
-__global__ __launch_bounds__(256) void mpf_mask_kernel(BinsArgs a, double *aux) {
+template <int MP, bool TRACK>
+__device__ __forceinline__ void mpf_mask_body(const BinsArgs &a, double *aux) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long total = (long)a.n_streams * a.n_frames * kNQ;
     if (idx >= total) return;
@@ -256,7 +286,7 @@ __global__ __launch_bounds__(256) void mpf_mask_kernel(BinsArgs a, double *aux) 
     const int s = (int)(st / a.n_frames);
     const int M = a.n_mics, NP = (M + 1) >> 1;
     const f64x2 *Zf = a.Z + (((long)(s / a.n_dirs) * a.frames_ws + a.frame_off + t) * NP) * kN;
-    const f64x2 *steer = a.steer + (long)(s % a.n_dirs) * a.steer_dir_stride;
+    const f64x2 *steer = TRACK ? track_steer(a, st) : a.steer + (long)(s % a.n_dirs) * a.steer_dir_stride;
     cd X[MP];
     load_X<MP>(Zf, q, M, X);
     const int j = q_bin(q);
@@ -273,6 +303,10 @@ __global__ __launch_bounds__(256) void mpf_mask_kernel(BinsArgs a, double *aux) 
     a.Yh[o] = f64x2{soi.x, soi.y};
     aux[o] = int2;
 }
+template <int MP>
+__global__ __launch_bounds__(256) void mpf_mask_kernel(BinsArgs a, double *aux) { mpf_mask_body<MP, false>(a, aux); }
+template <int MP>
+__global__ __launch_bounds__(256) void mpf_mask_track_kernel(BinsArgs a, double *aux) { mpf_mask_body<MP, true>(a, aux); }
 
 struct MpfState {
     double Sprev, Stmp, Smin, lam, Z, rev0, rev1;
@@ -786,9 +820,12 @@ __device__ __forceinline__ void team_barrier(lds_cnt_t cnt, int target, int lane
     asm volatile("" ::: "memory");
 }
 
-template <int LAYOUT, int MP, int ALGO>
-__global__ __launch_bounds__(512) void stft_bins_w64_kernel(StftArgs a, BinsArgs b, long frames_per_block, long total_frames, double *aux,
-                                                            f64x2 *xtail) {
+// (two kernels, one body, as das_f64_pair_body: the untracked kernel keeps its name in every profile, trace and dispatch table.  TRACK:
+// the frame's steering table comes from the batch's track, resolved once per (team, frame) next to s and t, wavefront-uniform; the
+// per-item steering loads then go through that pointer exactly as they go through b.steer)
+template <int LAYOUT, int MP, int ALGO, bool TRACK>
+__device__ __forceinline__ void stft_bins_w64_body(const StftArgs &a, const BinsArgs &b, long frames_per_block, long total_frames, double *aux,
+                                                   f64x2 *xtail) {
     constexpr int NPc = MP / 2;            // wavefronts per team = pair slots per frame
     constexpr int NT = 8 / NPc;            // teams per block
     constexpr int TT = 64 * NPc;           // threads per team
@@ -871,6 +908,13 @@ __global__ __launch_bounds__(512) void stft_bins_w64_kernel(StftArgs a, BinsArgs
         const long gf = gf0 + lf;
         const int s = (int)(gf / a.n_frames);
         const long t = gf - (long)s * a.n_frames;
+        // the frame's steering table: requested here, so that the index travels during the transform.  gf = s * n_frames + t is the same on
+        // every lane of the team: one index, scalar pointer arithmetic
+        const f64x2 *steer = b.steer;
+        if (TRACK) {
+            const int ti = __builtin_amdgcn_readfirstlane(b.track[gf]);
+            if ((unsigned)ti < (unsigned)b.track_n) steer = b.track_tables + (long)ti * b.track_stride;
+        }
         // ---- pass 1: window + forward FFT of (frame, pair p) into this wavefront's slot -------------------------------------------
         if (has_pair) {
             double re[16], im[16];
@@ -941,7 +985,7 @@ __global__ __launch_bounds__(512) void stft_bins_w64_kernel(StftArgs a, BinsArgs
         for (int n = 0; n < NIT; ++n) {
             const int q = tt + TT * n, j = q_bin(q);
             cd wst[MP];
-            if (ALGO != BF_PHASE) load_steer<MP>(b.steer, j, M, wst);  // from L1 / L2, in flight while the spectra come out of LDS
+            if (ALGO != BF_PHASE) load_steer<MP>(steer, j, M, wst);  // from L1 / L2, in flight while the spectra come out of LDS
             cd X[MP];
             load_X<MP>(zs, q, M, X);
             const long o = ((long)s * b.n_frames + t) * kYhStride + q;
@@ -949,7 +993,7 @@ __global__ __launch_bounds__(512) void stft_bins_w64_kernel(StftArgs a, BinsArgs
                 const cd y = das_core<MP>(X, wst, M);
                 st_y(b, o, q, y);
             } else if (ALGO == BF_PHASE) {
-                const cd y = phase_core_lazy<MP>(X, b.steer, M, j, b.cfg);  // steering only where the magnitude gate is open
+                const cd y = phase_core_lazy<MP>(X, steer, M, j, b.cfg);  // steering only where the magnitude gate is open
                 st_y(b, o, q, y);
             } else {  // phasempf mask
                 if (j == 0) {
@@ -958,7 +1002,8 @@ __global__ __launch_bounds__(512) void stft_bins_w64_kernel(StftArgs a, BinsArgs
                 } else {
                     cd soi;
                     double int2;
-                    mpf_mask_core<MP>(X, wst, M, b.cfg, soi, int2);
+                    // (the tracked [sample][mic] kernel at 8 microphones: the untracked one keeps 9 of the next frame's samples in scratch)
+                    mpf_mask_core<MP, TRACK && LAYOUT == 1 && MP == 8>(X, wst, M, b.cfg, soi, int2);
                     b.Yh[o] = f64x2{soi.x, soi.y};
                     aux[o] = int2;
                 }
@@ -978,12 +1023,22 @@ __global__ __launch_bounds__(512) void stft_bins_w64_kernel(StftArgs a, BinsArgs
         lf_next = lf_next2;
     }
 }
+template <int LAYOUT, int MP, int ALGO>
+__global__ __launch_bounds__(512) void stft_bins_w64_kernel(StftArgs a, BinsArgs b, long frames_per_block, long total_frames, double *aux,
+                                                            f64x2 *xtail) {
+    stft_bins_w64_body<LAYOUT, MP, ALGO, false>(a, b, frames_per_block, total_frames, aux, xtail);
+}
+template <int LAYOUT, int MP, int ALGO>
+__global__ __launch_bounds__(512) void stft_bins_w64_track_kernel(StftArgs a, BinsArgs b, long frames_per_block, long total_frames, double *aux,
+                                                                  f64x2 *xtail) {
+    stft_bins_w64_body<LAYOUT, MP, ALGO, true>(a, b, frames_per_block, total_frames, aux, xtail);
+}
 
 #endif
 
 // the two deferred problems per frame of the fused STFT + per-bin kernels: one thread per (stream, frame, q in {N/2, N/2+1})
-template <int MP, int ALGO>
-__global__ __launch_bounds__(256) void fused_tail_kernel(BinsArgs b, const f64x2 *xtail, double *aux) {
+template <int MP, int ALGO, bool TRACK>
+__device__ __forceinline__ void fused_tail_body(const BinsArgs &b, const f64x2 *xtail, double *aux) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     const long total = (long)b.n_streams * b.n_frames * 2;
     if (idx >= total) return;
@@ -992,7 +1047,7 @@ __global__ __launch_bounds__(256) void fused_tail_kernel(BinsArgs b, const f64x2
     cd X[MP], w[MP];
 #pragma unroll
     for (int m = 0; m < MP; ++m) X[m] = ld(xtail + idx * MP + m);
-    load_steer<MP>(b.steer, j, b.n_mics, w);
+    load_steer<MP>(TRACK ? track_steer(b, sf) : b.steer, j, b.n_mics, w);
     const long o = sf * kYhStride + q;
     if (ALGO == BF_DAS) {
         const cd y = das_core<MP>(X, w, b.n_mics);
@@ -1008,6 +1063,10 @@ __global__ __launch_bounds__(256) void fused_tail_kernel(BinsArgs b, const f64x2
         aux[o] = int2;
     }
 }
+template <int MP, int ALGO>
+__global__ __launch_bounds__(256) void fused_tail_kernel(BinsArgs b, const f64x2 *xtail, double *aux) { fused_tail_body<MP, ALGO, false>(b, xtail, aux); }
+template <int MP, int ALGO>
+__global__ __launch_bounds__(256) void fused_tail_track_kernel(BinsArgs b, const f64x2 *xtail, double *aux) { fused_tail_body<MP, ALGO, true>(b, xtail, aux); }
 
 #if BF_NFFT == 128 || BF_NFFT == 256 || BF_NFFT == 512
 // ---- the same fusion at the JACK periods 64 / 128 / 256: stft_small_kernel's transform in front of the per-bin arithmetic ----------------------
@@ -1398,6 +1457,7 @@ hipError_t launch_bins_end(const ChainPlan &p, const BinsArgs &a, hipStream_t s)
 #if BF_NFFT == 1024
 #define BF_FUSED_FPR 1
 #define BF_FUSED_FRONT(L_, MP_, A_) BF_LAUNCH((stft_bins_w64_kernel<L_, MP_, A_>), grid, dim3(512), 0, s, a, b, rpb, total, aux, xtail)
+#define BF_FUSED_FRONT_TRACK(L_, MP_, A_) BF_LAUNCH((stft_bins_w64_track_kernel<L_, MP_, A_>), grid, dim3(512), 0, s, a, b, rpb, total, aux, xtail)
 #elif BF_NFFT == 2048
 #define BF_FUSED_FPR (p.mp == 4 ? 2 : 1)
 #define BF_FUSED_FRONT(L_, MP_, A_) BF_LAUNCH((stft_bins_split_kernel<L_, MP_, A_>), grid, dim3(256), 0, s, a, b, rps, total, rpb, aux, xtail)
@@ -1420,8 +1480,20 @@ hipError_t launch_stft_bins_fused(const ChainPlan &p, const StftArgs &a, const B
     f64x2 *xtail = a.Z;  // [stream][frame][2][MP]: the plan sizes the Z workspace for it
     const long tail_items = (long)b.n_streams * b.n_frames * 2;
     const unsigned tail_blocks = (unsigned)((tail_items + 255) / 256);
+#ifdef BF_FUSED_FRONT_TRACK  // a tracked batch (ChainPlan::track): the twins that resolve the steering table per frame
+#define BF_FUSED_GO_TRACK(L_, MP_, A_)                                                                                     \
+    if (p.track) {                                                                                                         \
+        BF_FUSED_FRONT_TRACK(L_, MP_, A_);                                                                                 \
+        BF_LAUNCH((fused_tail_track_kernel<MP_, A_>), dim3(tail_blocks), dim3(256), 0, s, b, (const f64x2 *)xtail, aux);   \
+        break;                                                                                                             \
+    }
+#else  // no tracked fused front at this size: the plan never names one
+    if (p.track) return hipErrorInvalidValue;
+#define BF_FUSED_GO_TRACK(L_, MP_, A_)
+#endif
 #define BF_FUSED_GO(L_, MP_, A_)                                                                                     \
     do {                                                                                                             \
+        BF_FUSED_GO_TRACK(L_, MP_, A_)                                                                               \
         BF_FUSED_FRONT(L_, MP_, A_);                                                                                 \
         BF_LAUNCH((fused_tail_kernel<MP_, A_>), dim3(tail_blocks), dim3(256), 0, s, b, (const f64x2 *)xtail, aux);   \
     } while (0)
@@ -1438,6 +1510,7 @@ hipError_t launch_stft_bins_fused(const ChainPlan &p, const StftArgs &a, const B
     }
 #undef BF_FUSED_ALGO
 #undef BF_FUSED_GO
+#undef BF_FUSED_GO_TRACK
     const hipError_t e = hipGetLastError();
     return e != hipSuccess ? e : launch_bins_end(p, b, s);
 #else
@@ -1446,6 +1519,7 @@ hipError_t launch_stft_bins_fused(const ChainPlan &p, const StftArgs &a, const B
 #endif
 }
 #undef BF_FUSED_FRONT
+#undef BF_FUSED_FRONT_TRACK
 #undef BF_FUSED_FPR
 
 // MP_ = 4 / 8 / 16 / 32 of the plan -> the instantiation
@@ -1462,7 +1536,10 @@ hipError_t launch_mpf_mask(const ChainPlan &p, const BinsArgs &a, hipStream_t s)
     const long total = (long)a.n_streams * a.n_frames * kNQ;
     const unsigned blocks = (unsigned)((total + 255) / 256);
 #define BF_MASK(MP_) BF_LAUNCH((mpf_mask_kernel<MP_>), dim3(blocks), dim3(256), 0, s, a, aux)
-    BF_BY_MP(BF_MASK);
+#define BF_MASK_TRACK(MP_) BF_LAUNCH((mpf_mask_track_kernel<MP_>), dim3(blocks), dim3(256), 0, s, a, aux)
+    if (p.track) BF_BY_MP(BF_MASK_TRACK);
+    else BF_BY_MP(BF_MASK);
+#undef BF_MASK_TRACK
 #undef BF_MASK
     return hipGetLastError();
 }
@@ -1472,8 +1549,15 @@ hipError_t launch_pointwise(const ChainPlan &p, const BinsArgs &a, hipStream_t s
     const unsigned blocks = (unsigned)((total + 255) / 256);
 #define BF_PW_DAS(MP_) BF_LAUNCH((pointwise_bins_kernel<MP_, BF_DAS>), dim3(blocks), dim3(256), 0, s, a)
 #define BF_PW_PHASE(MP_) BF_LAUNCH((pointwise_bins_kernel<MP_, BF_PHASE>), dim3(blocks), dim3(256), 0, s, a)
-    if (p.algo == BF_DAS) BF_BY_MP(BF_PW_DAS);
+#define BF_PW_DAS_TRACK(MP_) BF_LAUNCH((pointwise_track_kernel<MP_, BF_DAS>), dim3(blocks), dim3(256), 0, s, a)
+#define BF_PW_PHASE_TRACK(MP_) BF_LAUNCH((pointwise_track_kernel<MP_, BF_PHASE>), dim3(blocks), dim3(256), 0, s, a)
+    if (p.track) {
+        if (p.algo == BF_DAS) BF_BY_MP(BF_PW_DAS_TRACK);
+        else BF_BY_MP(BF_PW_PHASE_TRACK);
+    } else if (p.algo == BF_DAS) BF_BY_MP(BF_PW_DAS);
     else BF_BY_MP(BF_PW_PHASE);
+#undef BF_PW_PHASE_TRACK
+#undef BF_PW_DAS_TRACK
 #undef BF_PW_PHASE
 #undef BF_PW_DAS
     return hipGetLastError();

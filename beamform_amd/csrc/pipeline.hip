@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <utility>
 #include <vector>
 
 #include "device_mem.hpp"
@@ -167,6 +168,22 @@ class BinPipelineImpl : public Engine {
         return BF_OK;
     }
 
+    bool can_track() const override { return (cfg_.algo == BF_DAS || cfg_.algo == BF_PHASE || cfg_.algo == BF_PHASEMPF) && D_ == 1; }
+    int install_track_tables(const std::vector<f64x2> &tables, int n_angles) override {
+        if (!can_track()) return Engine::install_track_tables(tables, n_angles);
+        // The tables in force are RETIRED, not freed: another thread may have taken them in its snapshot and still be enqueueing the kernels
+        // of that batch, which no synchronisation here can wait for.  What the previous call retired goes now: every batch that could
+        // hold it was begun before that call returned, and the device is idle with respect to what has been enqueued
+        ENGINE_HIP(hipDeviceSynchronize());
+        d_track_retired_ = std::move(d_track_);
+        track_n_ = 0;
+        if (n_angles > 0) {
+            ENGINE_HIP(d_track_.upload(tables));
+            track_n_ = n_angles;
+        }
+        return BF_OK;
+    }
+
     void on_theta_changed(int dir) override { gss_reset_mask_ |= dir < 0 ? ~0ull : (1ull << dir); }
     void set_columns(int kp1) override {
         KP1_ = kp1;
@@ -180,6 +197,8 @@ class BinPipelineImpl : public Engine {
         sn.steer = d_steer_[steer_cur_].get();
         sn.steer_dir_stride = steer_dir_stride_;
         sn.das = DasSnapshot{das_[steer_cur_].gains_w64.get(), das_[steer_cur_].gains_mic.get(), das_[steer_cur_].slots};
+        sn.track_tables = d_track_.get();
+        sn.track_n = track_n_;
         gss_reset_mask_ = 0;
         return sn;
     }
@@ -261,6 +280,9 @@ class BinPipelineImpl : public Engine {
     DeviceBuffer<f64x2> d_tw_w64_;       // twiddle_table_w64_rot
     DeviceBuffer<char> d_das_sched_;     // das_f64_pair_kernel: chunk table + counter (das_f64_sched_ws_bytes())
     int steer_cur_ = 0;
+    DeviceBuffer<f64x2> d_track_;        // steering tracks: [angle][mic][N], the [dir][col][mic][N] layout with one column (install_track_tables)
+    DeviceBuffer<f64x2> d_track_retired_;  // the tables the last install replaced: a batch being enqueued may still name them
+    int track_n_ = 0;
     DeviceBuffer<float> d_hist2_[2];  // ring hop in front of the next batch; two buffers: das_f64_pair_kernel writes the carry itself
     int hist_cur_ = 0;
     DeviceBuffer<float> d_tail_[2];
@@ -312,7 +334,8 @@ int BinPipelineImpl::run_das_one_launch(const float *x, long F, float *y, hipStr
 
 int BinPipelineImpl::run(const float *x, long F, float *y, f64x2 *spectrum, hipStream_t stream, int layout, long mic_stride,
                          const RunSnapshot &snap) {
-    const int rc = spectrum ? kDeclined : run_das_one_launch(x, F, y, stream, layout, mic_stride, snap);
+    // (a tracked batch never takes the one-launch kernels: the frame-pair kernel puts two frames, so two tables, into one transform)
+    const int rc = (spectrum || snap.track) ? kDeclined : run_das_one_launch(x, F, y, stream, layout, mic_stride, snap);
     return rc == kDeclined ? run_chain(x, F, y, spectrum, stream, layout, mic_stride, snap) : rc;
 }
 
@@ -325,7 +348,7 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
     const ChainPlan p = chain_decide(ChainShape{cfg_.algo, N_, layout, M_, S_, cfg_.n_dirs > 1 ? cfg_.n_dirs : 1, snap.kp1, cfg_.past_windows,
                                                 cfg_.precision, spectrum != nullptr, F, n_cus_, cfg_.gsc_filter_size, cfg_.smooth_size,
                                                 band_yh_lo_, band_yh_hi_, (reinterpret_cast<size_t>(y) & 15) == 0, sw.fused_bins,
-                                                sw.stft_small, sw.stft_split, sw.mvdr_group, sw.gss_group, sw.gsc_serial, R_});
+                                                sw.stft_small, sw.stft_split, sw.mvdr_group, sw.gss_group, sw.gsc_serial, R_, snap.track != nullptr});
     float *const hist = d_hist2_[hist_cur_].get();
     const long FT = Phist_ + F;  // frames in the Z workspace per stream
     ENGINE_HIP(d_Z_.reserve(p.z_bytes));
@@ -365,6 +388,9 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
     ba.cfg = cfg_; ba.gssW = d_gssW_.get(); ba.mpf = d_mpf_.get(); ba.gss_reset_mask = snap.gss_reset_mask;
     ba.yh32 = p.yh32 ? 1 : 0; ba.mpf32 = p.mpf32 ? 1 : 0; ba.yh_lo = p.yh_lo; ba.yh_hi = p.yh_hi;
     ba.gss_rows = p.rows;
+    if (p.track) {  // the per-frame table: tables + track[stream][frame] * stride where the index names a table, ba.steer otherwise
+        ba.track = snap.track; ba.track_tables = snap.track_tables; ba.track_n = snap.track_n; ba.track_stride = (long)M_ * N_;
+    }
     if (p.rec_istft()) {  // mpf_rec_istft_kernel: a block per stream, the y_fft rows stay in LDS
         ba.rec_istft = 1;
         ba.rec_y = d_yraw_.get(); ba.rec_tail_in = d_tail_[tail_cur_].get(); ba.rec_tail_out = d_tail_[tail_cur_ ^ 1].get();

@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <string>
 #include <vector>
 
@@ -34,6 +35,11 @@ struct RunSnapshot {
     const f64x2 *steer = nullptr;
     long steer_dir_stride = 0;
     DasSnapshot das;
+    // steering tracks (bf_track_set_angles): the installed tables [angle][mic][N] and their count, taken with the rest; `track` is not the
+    // engine's: the caller of run() points it at the batch's [stream][frame] indices (null: an untracked batch)
+    const f64x2 *track_tables = nullptr;
+    int track_n = 0;
+    const int32_t *track = nullptr;
 };
 
 class Engine {
@@ -47,6 +53,15 @@ class Engine {
     virtual int upload_steering(const std::vector<SteeringSet> &dirs, hipStream_t stream) = 0;
     virtual void on_theta_changed(int dir = -1) = 0;  // dir < 0: every look direction
     virtual void set_columns(int kp1) = 0;  // interferer added/removed (lcmv.cpp:266-305)
+    // steering tracks: can this engine weight every frame of a batch with a table of its own (das in double, phase, phasempf on the bin
+    // pipeline, one look direction)?  install_track_tables replaces the tables a tracked run() chooses from: `tables` = [n_angles][mic][N]
+    // on the host, n_angles = 0 drops them.  Host-synchronous (waits for the device); the replaced tables stay allocated until the next
+    // call, so a run() another thread is still enqueueing with them in its snapshot reads live memory.  Caller holds the control-plane mutex
+    virtual bool can_track() const { return false; }
+    virtual int install_track_tables(const std::vector<f64x2> &, int) {
+        err_ = "steering tracks: das in double, phase and phasempf with one look direction";
+        return BF_ENOSYS;
+    }
     // caller holds the control-plane mutex: hands the pending demixing resets to this run and clears them
     virtual RunSnapshot snapshot_for_run() = 0;
     virtual int run(const float *x_dev, long n_frames, float *y_dev, f64x2 *spectrum_dev, hipStream_t stream, int layout,

@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
+
 #include "../../include/bfcore.h"
 #include "chain_plan.hpp"
 #include "das_f64_plan.hpp"
@@ -95,6 +97,12 @@ struct BinsArgs {
     int mpf32;           // phasempf in front of the fp32 backward transform: the recursion leaves y_fft as f32x2 rows in the slots of its
                          // |out_int|^2 input (8 bytes each, same [stream][frame][kYhStride] layout, behind the f64x2 rows)
     int gss_rows = 1;    // gss: separated sources stored per beam (ChainPlan::rows); n_streams, Z, steer, gssW and the reset mask stay per BEAM
+    // steering track of the batch (ChainPlan::track; das / phase / phasempf, one look direction): frame t of stream s is weighted with
+    // track_tables + track[s * n_frames + t] * track_stride when that index lies in 0 .. track_n-1, with `steer` otherwise
+    const int32_t *track = nullptr;        // [stream][n_frames]
+    const f64x2 *track_tables = nullptr;   // [angle][mic][N]
+    int track_n = 0;
+    long track_stride = 0;                 // f64x2 elements per table
 };
 struct IstftArgs {
     const f64x2 *Yh;

@@ -407,6 +407,54 @@ int bf_resampler_process(bf_resampler *r, const float *in, size_t n_in, float *o
 void bf_resampler_destroy(bf_resampler *r);                                           /* src_delete */
 int bf_resampler_default_table(float *dst, int cap, int *index_inc);                  /* copy of the built-in table; returns its length */
 
+/* ---- steering tracks: a look angle per frame inside one batch --------------------------------------------------------------------
+ * In the reference a /theta message lands between two JACK callbacks, so the look angle can change at every frame (das.cpp:94-99,
+ * SURVEY 3.3); bf_set_theta takes effect at the next batch, which freezes a batch on one angle.  A steering track lifts that: the handle
+ * holds one steering table per CANDIDATE angle, and a device array names, for every (stream, frame) of a batch, which of them weights
+ * that frame.
+ *   Semantics: frame t of stream s is weighted exactly as the reference's callback t is with /theta = angles[track[s][t]] in force,
+ *   i.e. as if that angle had been set between callbacks t-1 and t.  theta_roscallback only rewrites the weight rows of these nodes, so
+ *   everything else -- the history hop (frame t is [hop t-1 | hop t] as always), the overlap-add tail, phasempf's recursive state and
+ *   smoother -- carries across frames and across calls exactly as in an untracked batch.
+ *   Index rule: track[s][t] in 0 .. n_angles-1 selects that table; ANY other value (negative, >= n_angles) selects the handle's own
+ *   /theta table, the one an untracked batch uses.  A bad index is never read through; -1 is the way to say "nothing published yet".
+ *   Supported: BF_DAS with BF_DAS_F64, BF_PHASE, BF_PHASEMPF, one look direction (n_dirs <= 1); any n_streams, both layouts, every
+ *   period, both precisions.  Every other handle answers BF_ENOSYS (gss re-initialises its demixing matrices on every /theta,
+ *   gss.cpp:90-93; mvdr / lcmv and the fp32 das kernels are not built for tracks).
+ *   Kernels: period 512 with <= 8 microphones keeps STFT and per-bin stage in one launch (the spectra never leave the CU); every other
+ *   shape runs STFT -> per-bin kernel -> ISTFT.  das in double never takes its one-launch frame-pair kernel for a tracked batch (two
+ *   frames share a transform there), so an untracked batch is the faster way to run a constant angle.
+ * A handle that never installs angles runs the kernels it always ran. */
+#define BF_TRACK_MAX_ANGLES 1024   /* = BF_DOA_MAX_ANGLES: a bf_doa peak index is a track index */
+/* Installs the candidate angles (degrees): table a holds the bytes bf_set_theta with angles_deg[a] would leave in the handle's table (the
+ * same host code, microphone 0's row as it stands).  n_angles = 0 drops the tables.  HOST-SYNCHRONOUS: waits until the device has
+ * finished everything enqueued before it, then installs the new tables for the batches that begin afterwards.  Thread-safe against a
+ * concurrent bf_process_* on the handle, like bf_set_theta: the handle's mutex guards the switch, and a tracked batch that another
+ * thread has begun keeps the tables it began with -- they are retired, not freed, until the NEXT bf_track_set_angles (or bf_destroy),
+ * so up to two sets of tables are resident.  The tables are input, not state: no part of bf_state_size / the state blob.
+ * BF_EINVAL: a non-finite angle, n_angles outside 0 .. BF_TRACK_MAX_ANGLES, tables (n_angles x n_mics x 2 hop complex doubles) above
+ * 512 MiB.  BF_ENOSYS: a handle without tracks (above). */
+int bf_track_set_angles(bf_handle *h, const double *angles_deg, int n_angles);
+/* bf_process_batch_device with a track: track_dev is [n_streams][n_frames] int32 on the device, read by the kernels (it must stay
+ * valid until hip_stream has passed the batch).  Tracked and untracked calls may alternate on one handle; the handle's own theta is
+ * not changed.  BF_EINVAL: no angles installed, track_dev NULL, n_dirs > 1.  BF_ENOSYS: a handle without tracks. */
+int bf_process_batch_device_tracked(bf_handle *h, const float *x_dev, size_t n_frames, float *y_dev, void *spectrum_dev,
+                                    const int32_t *track_dev, void *hip_stream);
+/* From direction-of-arrival peaks to a track, on the device (no handle; one small launch on hip_stream, no host synchronisation).
+ * peak_dev: [n_streams][n_blocks] as bf_doa_process_device writes it; map_dev: [n_streams][n_blocks][n_angles], may be NULL when
+ * min_peak <= 0.  Block b PUBLISHES peak[s][b] when map[s][b][peak[s][b]] >= min_peak (not below it: a NaN publishes, as
+ * controllers.DoaTheta does); with a NULL map every block publishes; with a map, a peak outside 0 .. n_angles-1 is not looked up and
+ * does not publish.  Every frame of block b gets the index published by the latest block b' <= b - latency_blocks that published; if
+ * there is none, carry[s] as it was on entry.  On exit carry[s] is the index a block n_blocks would get, so that consecutive calls
+ * continue one stream (exactly for latency_blocks <= 1: carry is one index, a longer latency forgets what the last
+ * latency_blocks - 1 blocks of the previous call published).  Start with carry = -1: "the handle's theta".  latency_blocks = 1 is an
+ * external localiser's one block of latency (controllers.follow_doa).  track_dev: [n_streams][n_blocks * frames_per_block].
+ * BF_EINVAL, checked before any device work: n_angles < 1, n_streams < 1, frames_per_block < 1, latency_blocks < 0, NULL peak / carry /
+ * track, NULL map with min_peak > 0. */
+int bf_track_from_peaks_device(const int32_t *peak_dev, const double *map_dev, int n_angles, int n_streams, size_t n_blocks,
+                               int frames_per_block, int latency_blocks, double min_peak, int32_t *carry_dev, int32_t *track_dev,
+                               void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
