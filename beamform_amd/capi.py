@@ -33,10 +33,12 @@ EXPORTS = (
     "bf_resampler_create", "bf_resampler_set_table", "bf_resampler_reset", "bf_resampler_out_count", "bf_resampler_latency",
     "bf_resampler_process_device", "bf_resampler_process", "bf_resampler_destroy", "bf_resampler_default_table",
     "bf_resampler_set_mode", "bf_resampler_callback", "bf_resampler_callback_device",
-    "bf_doa_create", "bf_doa_set_phat_floor", "bf_doa_process_device", "bf_doa_process", "bf_doa_reset", "bf_doa_destroy",
+    "bf_doa_create", "bf_doa_set_phat_floor", "bf_doa_set_method", "bf_doa_set_loading", "bf_doa_process_device", "bf_doa_process",
+    "bf_doa_reset", "bf_doa_destroy",
     "bf_track_set_angles", "bf_process_batch_device_tracked", "bf_track_from_peaks_device",
 )
 BF_DOA_MAX_ANGLES = 1024
+BF_DOA_SRP_PHAT, BF_DOA_CAPON = 0, 1   # bf_doa_method
 BF_TRACK_MAX_ANGLES = 1024   # = BF_DOA_MAX_ANGLES: a Doa peak index is a track index
 
 
@@ -196,6 +198,8 @@ def load():
     L.bf_doa_create.argtypes = [C.POINTER(BfConfig), C.POINTER(C.c_double), C.c_int, C.c_double, C.c_double, C.c_int,
                                 C.POINTER(C.c_void_p)]
     L.bf_doa_set_phat_floor.argtypes = [C.c_void_p, C.c_double]
+    L.bf_doa_set_method.argtypes = [C.c_void_p, C.c_int]
+    L.bf_doa_set_loading.argtypes = [C.c_void_p, C.c_double]
     L.bf_doa_process_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bf_doa_process.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.bf_doa_reset.argtypes = [C.c_void_p]
@@ -599,7 +603,7 @@ def track_from_peaks_device(peak_ptr: int, map_ptr: int, n_angles: int, n_stream
 
 
 class Doa:
-    """SRP-PHAT direction-of-arrival maps (bf_doa_*): per block of `frames_per_block` frames, the PHAT-weighted steered response
+    """Direction-of-arrival maps (bf_doa_*; SRP-PHAT by default, Capon through set_method): per block of `frames_per_block` frames, the PHAT-weighted steered response
     power of every angle in `angles` (degrees) over the band [freq_lo, freq_hi] Hz, and the index of the best angle.  `params`
     supplies the geometry, hop and sample rate (a beamform_amd.params dict); the angle of a peak is what das takes in set_theta."""
 
@@ -633,6 +637,18 @@ class Doa:
 
     def set_phat_floor(self, eps: float):
         self._chk(self._L.bf_doa_set_phat_floor(self._h, float(eps)), "bf_doa_set_phat_floor")
+
+    def set_method(self, method):
+        """"srp_phat" (the default) or "capon" (or the BF_DOA_* constant): the map the next process call computes.  The Capon map
+        tells several sources apart where the SRP-PHAT map shows the strongest one's sidelobes (controllers.follow_sources)."""
+        m = {"srp_phat": BF_DOA_SRP_PHAT, "capon": BF_DOA_CAPON}.get(method, method)
+        if isinstance(m, str):
+            raise ValueError(f"unknown Doa method {method!r}")
+        self._chk(self._L.bf_doa_set_method(self._h, int(m)), "bf_doa_set_method")
+
+    def set_loading(self, delta: float):
+        """Capon's diagonal loading, in (0, 1] (default 1e-3)."""
+        self._chk(self._L.bf_doa_set_loading(self._h, float(delta)), "bf_doa_set_loading")
 
     def reset(self):
         self._chk(self._L.bf_doa_reset(self._h), "bf_doa_reset")

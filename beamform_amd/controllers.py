@@ -345,3 +345,71 @@ def follow_doa_device(node, doa, x: np.ndarray, frames_per_block: int, min_peak:
     if published:
         node.set_theta(published[-1][1])
     return y, published
+
+
+def pick_sources(row, angles, k: int, min_sep_deg: float, rel_floor: float = 0.0):
+    """Greedy peak picking on one map row (a Capon map tells several sources apart: capi.Doa.set_method("capon")): repeatedly the
+    largest remaining value, the lowest index on ties; every angle whose circular distance to a picked angle is below `min_sep_deg`
+    is suppressed.  Stops after `k` picks, when nothing remains, or when the value is below `rel_floor` x the row's maximum.
+    Returns the picked indices, strongest first."""
+    row = np.asarray(row, dtype=np.float64).ravel()
+    ang = np.asarray(angles, dtype=np.float64).ravel()
+    if row.size == 0:
+        return []
+    floor = float(rel_floor) * float(np.max(row))
+    free = np.ones(row.size, bool)
+    picks = []
+    while len(picks) < int(k) and free.any():
+        d = int(np.argmax(np.where(free, row, -np.inf)))  # the lowest index on ties
+        if row[d] < floor:
+            break
+        picks.append(d)
+        free &= np.abs((ang - ang[d] + 180.0) % 360.0 - 180.0) >= float(min_sep_deg)
+        free[d] = False
+    return picks
+
+
+class DoaSources:
+    """A publisher of a look direction and its interferers from one map row: on_map(row) returns (theta, [interferer angles]) --
+    pick_sources' strongest pick and the rest in order -- or None when the strongest value is below `min_peak`."""
+
+    def __init__(self, angles, k: int, min_sep_deg: float, rel_floor: float = 0.0, min_peak: float = 0.0):
+        self.angles = np.asarray(angles, dtype=np.float64).ravel()
+        self.k, self.min_sep_deg = int(k), float(min_sep_deg)
+        self.rel_floor, self.min_peak = float(rel_floor), float(min_peak)
+
+    def on_map(self, row):
+        row = np.asarray(row, dtype=np.float64).ravel()
+        picks = pick_sources(row, self.angles, self.k, self.min_sep_deg, self.rel_floor)
+        if not picks or row[picks[0]] < self.min_peak:
+            return None
+        return float(self.angles[picks[0]]), [float(self.angles[d]) for d in picks[1:]]
+
+
+def follow_sources(node, doa, x: np.ndarray, frames_per_block: int, controller):
+    """follow_doa's loop for the nodes that take more than one angle (lcmv, gss), one stream and one block of latency: after block b
+    has been processed, a publication (theta, interferers) of controller.on_map is applied as node.set_theta(theta), then
+    node.set_interference(i + 1, angle_i) for each interferer in order.  The loop never removes an interferer itself:
+    bf_set_interference's own rules (update, append, merge within interf_angle_threshold) do what they do.
+
+    node: process(x [M, n*hop]) -> [n*hop], set_theta(deg), set_interference(id, deg), attribute H.  doa: beamform_amd.capi.Doa on the
+    same geometry, one stream, W = frames_per_block (the Capon method for more than one source).  x: [M, F*hop] float32.
+    Returns (y [F*hop], published: list of (block index, theta, tuple of interferer angles))."""
+    H, W = node.H, int(frames_per_block)
+    F = x.shape[1] // H
+    ys, published = [], []
+    for b in range(F // W):
+        seg = np.ascontiguousarray(x[:, b * W * H:(b + 1) * W * H])
+        m, _ = doa.process(seg)
+        y = node.process(seg)
+        if isinstance(y, tuple):
+            y = y[0]
+        ys.append(np.array(y, copy=True))
+        pub = controller.on_map(m[0])
+        if pub is not None:
+            theta, interf = pub
+            node.set_theta(theta)
+            for i, a in enumerate(interf):
+                node.set_interference(i + 1, a)
+            published.append((b, theta, tuple(interf)))
+    return np.concatenate(ys), published

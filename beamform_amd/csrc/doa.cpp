@@ -1,4 +1,4 @@
-// doa.cpp -- bf_doa_*: SRP-PHAT direction-of-arrival maps over the nodes' frames (include/bfcore.h, DESIGN.md "Direction-of-arrival
+// doa.cpp -- bf_doa_*: SRP-PHAT and Capon direction-of-arrival maps over the nodes' frames (include/bfcore.h, DESIGN.md "Direction-of-arrival
 // maps").  Host side: argument checks, the steering table (SteeringSet, the weights das steers with), scratch sizing and the launch
 // sequence per chunk of frames.  Every per-frame operation runs in the gfx950 kernels (pipeline_kernels.hpp launch_stft,
 // doa_kernels.hip); there is no CPU fallback.
@@ -22,10 +22,14 @@ struct bf_doa {
     int M = 0, H = 0, N = 0, S = 1, NP = 1, layout = 0, device = 0, n_cus = 256;
     int D = 0, W = 1, klo = 0, nK = 0, G = 1;
     double eps = 1e-10;
+    int method = BF_DOA_SRP_PHAT;                 // bf_doa_set_method
+    double delta = 1e-3;                          // bf_doa_set_loading
     std::string err;
     const KernelSet *ks = nullptr;
     hipStream_t stream = nullptr;                 // bf_doa_process (host buffers)
     DeviceBuffer<f64x2> d_steer, d_tw;            // [bin - klo][mic][angle]; forward-transform twiddles
+    DeviceBuffer<f64x2> d_steer_capon;            // [angle][mic][bin - klo]: built when Capon is first selected
+    DeviceBuffer<f64x2> d_ws;                     // Capon above 8 microphones: the covariance triangles of one chunk
     DeviceBuffer<double> d_win;                   // sqrt-Hann
     DeviceBuffer<float> d_hist;                   // [stream][hop before the next frame], layout as the input
     // scratch for one chunk of `cap` frames (allocated on first use, grown up to the budget, kept)
@@ -84,6 +88,104 @@ int ensure_scratch(bf_doa *d, long frames) {
         return fail(d, BF_ENOMEM, "bf_doa scratch");
     }
     d->cap = frames;
+    return BF_OK;
+}
+
+// Capon: the buffers one chunk of the plan needs (the spectra and partial sums share the SRP-PHAT scratch, which only ever grows)
+int ensure_capon_scratch(bf_doa *d, const CaponPlan &p) {
+    const size_t z = p.z_bytes / sizeof(f64x2), part = p.part_bytes / sizeof(double), ws = p.ws_bytes / sizeof(f64x2);
+    if (z <= d->d_Z.size() && part <= d->d_part.size() && ws <= d->d_ws.size()) return BF_OK;
+    DOA_HIP(d, hipDeviceSynchronize());  // a batch still in flight may read the old buffers
+    d->cap = 0;                          // a failed growth leaves a buffer empty
+    if (d->d_Z.reserve(z) != hipSuccess || d->d_part.reserve(part) != hipSuccess || d->d_ws.reserve(ws) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(d, BF_ENOMEM, "bf_doa scratch");
+    }
+    return BF_OK;
+}
+
+// the forward transforms of frames [0, n) at xc into d_Z (rows of frames_ws frames per stream): packed pairs, halved, band rows only
+int enqueue_stft(bf_doa *d, const float *xc, long n, long frames_ws, long mic_stride, long stream_stride, hipStream_t s) {
+    StftArgs sa{};
+    sa.x = xc;
+    sa.hist = d->d_hist.get();
+    sa.Z = d->d_Z.get();
+    sa.tw = d->d_tw.get();
+    sa.win = d->d_win.get();
+    sa.n_frames = n;
+    sa.frames_ws = frames_ws;
+    sa.frame_off = 0;
+    sa.mic_stride = mic_stride;
+    sa.stream_stride_x = stream_stride;
+    sa.n_streams = d->S;
+    sa.n_mics = d->M;
+    sa.layout = d->layout;
+    sa.n_fft_mics = d->M;
+    sa.skip_lo = d->N;  // store everything ...
+    sa.skip_hi = 0;
+    const int khi = d->klo + d->nK - 1;
+    if (khi < d->N / 2 - 2) {  // ... but the bins between the band's top bin and its mirror
+        sa.skip_lo = khi;
+        sa.skip_hi = d->N - khi;
+    }
+    sa.z48 = 0;
+    sa.halve = 1;  // X_a = Z[k] + conj Z[N-k], X_b = -i (Z[k] - conj Z[N-k])
+    sa.run_len = 1;
+    ChainPlan front{};  // only the STFT of the chain runs here
+    front.layout = d->layout;
+    front.front = chain_stft_front(d->N, switches().stft_small, switches().stft_split);
+    DOA_HIP(d, d->ks->stft(front, sa, d->n_cus, s));
+    return BF_OK;
+}
+
+// One batch of the Capon method: per chunk the forward transforms, doa_capon_kernel, the reduction over the band's segments.
+int capon_process_device(bf_doa *d, const float *x_dev, long F, double *map_dev, int32_t *peak_dev, hipStream_t s) {
+    const CaponPlan plan = capon_decide(CaponShape{d->M, d->S, d->N, d->D, d->nK, d->W, F});
+    int rc = ensure_capon_scratch(d, plan);
+    if (rc != BF_OK) return rc;
+    const int M = d->M, H = d->H;
+    const long CF = plan.chunk_frames, CB = plan.chunk_blocks;
+    const long mic_stride = d->layout == BF_PLANAR ? F * H : 1;
+    const long stream_stride = (long)M * F * H;
+    for (long c0 = 0; c0 < F; c0 += CF) {
+        const long n = std::min(CF, F - c0);
+        const float *xc = x_dev + (d->layout == BF_PLANAR ? c0 * H : c0 * (long)H * M);
+        rc = enqueue_stft(d, xc, n, CF, mic_stride, stream_stride, s);
+        if (rc != BF_OK) return rc;
+        CaponArgs ca;
+        ca.Z = d->d_Z.get();
+        ca.steer = d->d_steer_capon.get();
+        ca.part = d->d_part.get();
+        ca.ws = d->d_ws.get();
+        ca.delta = d->delta;
+        ca.frames_ws = CF;
+        ca.blocks_ws = CB;
+        ca.n_blocks = n / d->W;
+        ca.n_streams = d->S;
+        ca.n_mics = M;
+        ca.nfft = d->N;
+        ca.n_angles = d->D;
+        ca.klo = d->klo;
+        ca.n_bins = d->nK;
+        ca.n_segments = plan.segments;
+        ca.frames_per_block = d->W;
+        DOA_HIP(d, launch_capon(ca, plan, s));
+        DoaReduceArgs ra;  // a block's partial sums are laid out as one frame's: the segments in order, the scale, the argmax
+        ra.part = d->d_part.get();
+        ra.map = map_dev;
+        ra.peak = peak_dev;
+        ra.scale = 1.0 / (double)d->nK;
+        ra.frames_ws = CB;
+        ra.map_blocks = F / d->W;
+        ra.block0 = c0 / d->W;
+        ra.n_blocks = n / d->W;
+        ra.n_streams = d->S;
+        ra.n_angles = d->D;
+        ra.n_segments = plan.segments;
+        ra.frames_per_block = 1;
+        DOA_HIP(d, launch_doa_reduce(ra, s));
+        DOA_HIP(d, carry_last_hop(d->d_hist.get(), xc, n, H, M, d->S, d->layout, mic_stride, stream_stride, s));
+    }
     return BF_OK;
 }
 
@@ -187,6 +289,33 @@ int bf_doa_set_phat_floor(bf_doa *d, double eps) {
     return BF_OK;
 }
 
+int bf_doa_set_method(bf_doa *d, int method) {
+    if (!d || (method != BF_DOA_SRP_PHAT && method != BF_DOA_CAPON))
+        return fail(d, BF_EINVAL, "bf_doa_set_method: NULL handle or unknown method");
+    if (method == BF_DOA_CAPON && d->d_steer_capon.size() == 0) {  // the first selection: the table with the bins innermost
+        DOA_HIP(d, hipSetDevice(d->device));
+        if (d->d_steer_capon.alloc(d->d_steer.size()) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(d, BF_ENOMEM, "bf_doa_set_method: steering table");
+        }
+        hipError_t e = launch_capon_table(d->d_steer.get(), d->d_steer_capon.get(), d->nK, d->M, d->D, d->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+        if (e != hipSuccess) {
+            d->d_steer_capon = DeviceBuffer<f64x2>();
+            return fail(d, BF_EIO, "bf_doa_set_method: steering table", e);
+        }
+    }
+    d->method = method;
+    return BF_OK;
+}
+
+int bf_doa_set_loading(bf_doa *d, double delta) {
+    if (!d || !std::isfinite(delta) || !(delta > 0) || !(delta <= 1))
+        return fail(d, BF_EINVAL, "bf_doa_set_loading: delta must be finite and in (0, 1]");
+    d->delta = delta;
+    return BF_OK;
+}
+
 int bf_doa_process_device(bf_doa *d, const float *x_dev, size_t n_frames, double *map_dev, int32_t *peak_dev, void *hip_stream) {
     if (!d) return fail(nullptr, BF_EINVAL, "bf_doa_process_device: handle is NULL");
     if (!map_dev && !peak_dev) return fail(d, BF_EINVAL, "bf_doa_process_device: map and peak are both NULL");
@@ -195,6 +324,7 @@ int bf_doa_process_device(bf_doa *d, const float *x_dev, size_t n_frames, double
     if (!x_dev) return fail(d, BF_EINVAL, "bf_doa_process_device: x is NULL");
     hipStream_t s = (hipStream_t)hip_stream;
     DOA_HIP(d, hipSetDevice(d->device));
+    if (d->method == BF_DOA_CAPON) return capon_process_device(d, x_dev, (long)n_frames, map_dev, peak_dev, s);
     const long F = (long)n_frames, CF = std::min(chunk_budget(d), F);
     int rc = ensure_scratch(d, CF);
     if (rc != BF_OK) return rc;
@@ -206,35 +336,8 @@ int bf_doa_process_device(bf_doa *d, const float *x_dev, size_t n_frames, double
         const long n = std::min(CF, F - c0);
         const float *xc = x_dev + (d->layout == BF_PLANAR ? c0 * H : c0 * (long)H * M);
         DOA_HIP(d, launch_doa_hop_flags(xc, d->d_hist.get(), d->d_flags.get(), n, mic_stride, stream_stride, d->S, M, H, d->layout, s));
-        StftArgs sa{};
-        sa.x = xc;
-        sa.hist = d->d_hist.get();
-        sa.Z = d->d_Z.get();
-        sa.tw = d->d_tw.get();
-        sa.win = d->d_win.get();
-        sa.n_frames = n;
-        sa.frames_ws = CF;
-        sa.frame_off = 0;
-        sa.mic_stride = mic_stride;
-        sa.stream_stride_x = stream_stride;
-        sa.n_streams = d->S;
-        sa.n_mics = M;
-        sa.layout = d->layout;
-        sa.n_fft_mics = M;
-        sa.skip_lo = d->N;  // store everything ...
-        sa.skip_hi = 0;
-        const int khi = d->klo + d->nK - 1;
-        if (khi < d->N / 2 - 2) {  // ... but the bins between the band's top bin and its mirror
-            sa.skip_lo = khi;
-            sa.skip_hi = d->N - khi;
-        }
-        sa.z48 = 0;
-        sa.halve = 1;  // X_a = Z[k] + conj Z[N-k], X_b = -i (Z[k] - conj Z[N-k])
-        sa.run_len = 1;
-        ChainPlan front{};  // only the STFT of the chain runs here
-        front.layout = d->layout;
-        front.front = chain_stft_front(d->N, switches().stft_small, switches().stft_split);
-        DOA_HIP(d, d->ks->stft(front, sa, d->n_cus, s));
+        rc = enqueue_stft(d, xc, n, CF, mic_stride, stream_stride, s);
+        if (rc != BF_OK) return rc;
         DoaMapArgs ma;
         ma.Z = d->d_Z.get();
         ma.flags = d->d_flags.get();

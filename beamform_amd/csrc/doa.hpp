@@ -1,10 +1,73 @@
 // doa.hpp -- SRP-PHAT direction-of-arrival maps (bf_doa_*, include/bfcore.h): argument blocks and launchers of doa_kernels.hip.
 // The spectra come from the bin pipeline's forward transform (pipeline_kernels.hpp launch_stft, packed microphone pairs, halved).
+//
+// The Capon (MVDR) map is the handle's second method (bf_doa_set_method): its launch decisions are the plain C++ of capon_decide below,
+// which the CPU suite compiles on its own (-DBF_DOA_PLAN_ONLY: no HIP header is read in front of the #ifndef).
 #pragma once
 
+#include <cstddef>
+#include <cstdint>
+
+namespace bf {
+
+// ---- Capon map: one pure launch decision per batch -----------------------------------------------------------------------------------
+// One lane per (stream, block, in-band bin) problem, one wavefront per 64 consecutive bins of a block: a band segment.  The segments
+// depend on |K| only, so a block's sum over the band is formed the same way however a stream is cut into calls or chunks.
+constexpr int kCaponSegBins = 64;
+constexpr int kCaponRegMics = 8;                    // up to here the covariance and its factor live in registers
+constexpr size_t kCaponChunkBytes = 256ull << 20;   // spectra + partial sums + work space of one chunk (never less than one block)
+inline int capon_segments(int n_bins) { return (n_bins + kCaponSegBins - 1) / kCaponSegBins; }
+
+enum class CaponPath : int { kRegisters = 0, kWorkspace = 1 };
+
+struct CaponShape {
+    int n_mics, n_streams, nfft, n_angles, n_bins, frames_per_block;
+    long n_frames;  // of the batch: a multiple of frames_per_block
+};
+struct CaponPlan {
+    CaponPath path;         // by microphone count alone
+    int mp;                 // kRegisters: the kernel's compile-time row count, 2 x microphone pairs (2, 4, 6, 8); kWorkspace: 0
+    int segments;           // of the band: by |K| alone
+    int ws_elems;           // kWorkspace: complex doubles per problem, the lower triangle of R with its diagonal + the solve's vector
+    long chunk_blocks;      // blocks of one chunk: what fits the budget, at least one, at most the batch
+    long chunk_frames;      // chunk_blocks x frames_per_block
+    unsigned grid_x, grid_y;  // of a full chunk: (segments x chunk_blocks, streams); 64 lanes per workgroup
+    size_t z_bytes;         // packed pair spectra of one chunk
+    size_t part_bytes;      // partial sums of one chunk: [segment][stream][chunk block][angle] doubles
+    size_t ws_bytes;        // kWorkspace: [element][stream][chunk block][segment][lane] complex doubles; kRegisters: 0
+    size_t table_bytes;     // the steering table in the kernel's layout, [angle][mic][bin - klo] complex doubles
+};
+
+inline CaponPlan capon_decide(const CaponShape &c) {
+    CaponPlan p{};
+    const size_t M = (size_t)c.n_mics, S = (size_t)c.n_streams, NP = (M + 1) / 2, W = (size_t)c.frames_per_block;
+    p.path = c.n_mics <= kCaponRegMics ? CaponPath::kRegisters : CaponPath::kWorkspace;
+    p.mp = p.path == CaponPath::kRegisters ? 2 * (int)NP : 0;
+    p.segments = capon_segments(c.n_bins);
+    p.ws_elems = p.path == CaponPath::kWorkspace ? (int)(M * (M + 1) / 2 + M) : 0;
+    const size_t G = (size_t)p.segments;
+    const size_t z_block = W * S * NP * (size_t)c.nfft * 16, part_block = G * S * (size_t)c.n_angles * 8;
+    const size_t ws_block = (size_t)p.ws_elems * S * G * kCaponSegBins * 16;
+    long nb = (long)(kCaponChunkBytes / (z_block + part_block + ws_block));
+    const long batch = c.n_frames / c.frames_per_block;
+    if (nb < 1) nb = 1;
+    if (nb > batch) nb = batch;
+    p.chunk_blocks = nb;
+    p.chunk_frames = nb * c.frames_per_block;
+    p.grid_x = (unsigned)(G * (size_t)nb);
+    p.grid_y = (unsigned)S;
+    p.z_bytes = z_block * (size_t)nb;
+    p.part_bytes = part_block * (size_t)nb;
+    p.ws_bytes = ws_block * (size_t)nb;
+    p.table_bytes = (size_t)c.n_angles * M * (size_t)c.n_bins * 16;
+    return p;
+}
+
+}  // namespace bf
+
+#ifndef BF_DOA_PLAN_ONLY
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
 #include <string>
 
 #include "geometry.hpp"
@@ -57,4 +120,19 @@ hipError_t launch_doa_map(const DoaMapArgs &a, hipStream_t s);
 hipError_t launch_doa_reduce(const DoaReduceArgs &a, hipStream_t s);
 hipError_t launch_track_from_peaks(const TrackFromPeaksArgs &a, int n_streams, hipStream_t s);
 
+// ---- Capon map (doa_kernels.hip) -----------------------------------------------------------------------------------------------------
+struct CaponArgs {
+    const f64x2 *Z;            // [stream][frames_ws][NP][N] packed pair spectra, stored halved (only ratios of R enter the map)
+    const f64x2 *steer;        // [angle][mic][bin - klo]: consecutive lanes (bins) read consecutive entries
+    double *part;              // [segment][stream][blocks_ws][angle]: sum over the segment's bins of c_d(k), lanes added in one fixed tree
+    f64x2 *ws;                 // kWorkspace only: [element][problem lane of the grid]
+    double delta;              // the diagonal loading
+    long frames_ws, blocks_ws, n_blocks;  // blocks of this chunk
+    int n_streams, n_mics, nfft, n_angles, klo, n_bins, n_segments, frames_per_block;
+};
+// [bin][mic][angle] -> [angle][mic][bin]
+hipError_t launch_capon_table(const f64x2 *src, f64x2 *dst, int n_bins, int n_mics, int n_angles, hipStream_t s);
+hipError_t launch_capon(const CaponArgs &a, const CaponPlan &p, hipStream_t s);
+
 }  // namespace bf
+#endif  // BF_DOA_PLAN_ONLY

@@ -11,6 +11,19 @@
 //   doa_reduce_kernel     per (stream, block): segments in order, then the block's frames in order, the scale, and the argmax
 // Every sum has one fixed order that depends on the band and W only: map and peak bytes do not depend on how a stream is cut into
 // calls or chunks, nor on the launch.  No atomics reach a sum (the hop flags are OR-ed).
+//
+// The Capon (MVDR) map, the handle's second method (bf_doa_set_method):
+//
+//   R_{s,b}(k) = sum_{t in block b} X X^H,  tau = trace R,  R~ = R / tau + (delta / M) I,  c_d(k) = M / ((1 + delta) a_d^H R~^-1 a_d)  (0 at tau <= 0)
+//   P[s][b][d] = 1 / |K| sum_{k in K} c_d(k)
+//
+// Two kernels per chunk behind the same forward transforms (no hop flags: there is no PHAT normalisation):
+//   doa_capon_kernel      one lane per (stream, block, bin), one wavefront per 64 consecutive bins (a band segment): the covariance over the
+//                         block's frames in ascending order, the Cholesky factor R~ = L L^H, and per angle one forward substitution
+//                         u = L^-1 a_d, c = M / ((1 + delta) |u|^2); the wavefront's 64 values are added in one fixed butterfly ->
+//                         one partial sum per (segment, stream, block, angle).  Up to 8 microphones everything stays in registers
+//                         (doa_capon_kernel<MP>); above, the triangle lives in a work space in memory (doa_capon_ws_kernel).
+//   doa_reduce_kernel     as above with one "frame" per block: segments in ascending order, the scale 1 / |K|, the argmax
 #include <climits>
 
 #include "doa.hpp"
@@ -280,7 +293,251 @@ __global__ __launch_bounds__(64) void track_from_peaks_kernel(TrackFromPeaksArgs
     if (lane == 0) a.carry[s] = cur;
 }
 
+// ---- Capon --------------------------------------------------------------------------------------------------------------------------
+// The sum of a wavefront's 64 values: a butterfly, so every lane forms the same six sums in the same order whatever the launch.
+__device__ __forceinline__ double wave_sum64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// microphone m's spectrum out of its pair's packed rows: X_a = Z[k] + conj Z[N-k], X_b = -i (Z[k] - conj Z[N-k])
+__device__ __forceinline__ f64x2 unpack_mic(const f64x2 z, const f64x2 c, bool second) {
+    return second ? f64x2{z.y + c.y, c.x - z.x} : f64x2{z.x + c.x, z.y - c.y};
+}
+
+__global__ __launch_bounds__(kDoaBlock) void capon_table_kernel(const f64x2 *src, f64x2 *dst, int n_bins, int n_mics, int n_angles) {
+    const long n = (long)n_bins * n_mics * n_angles;
+    for (long i = (long)blockIdx.x * kDoaBlock + threadIdx.x; i < n; i += (long)gridDim.x * kDoaBlock) {
+        const int kk = (int)(i % n_bins);
+        const long r = i / n_bins;  // d * M + m
+        const int m = (int)(r % n_mics), d = (int)(r / n_mics);
+        dst[i] = src[((long)kk * n_mics + m) * n_angles + d];
+    }
+}
+
+// MP = 2 x microphone pairs (2, 4, 6, 8).  An odd count's last pair has a zero partner channel: its spectrum (the transform's rounding
+// residue) is never formed -- row MP-1 of R~ is pinned to the identity and its steering entry to 0, so it adds nothing to |u|^2.
+// The strict lower triangle of R (then of L) and the real diagonal (then 1 / L_ii) are registers; every loop below is unrolled.
+template <int MP>
+__global__ __launch_bounds__(64) void doa_capon_kernel(CaponArgs a) {
+    constexpr int NT = MP * (MP - 1) / 2, NP = MP / 2;
+    const int lane = threadIdx.x, G = a.n_segments;
+    const long b = blockIdx.x / G;
+    const int g = (int)(blockIdx.x - b * G), s = blockIdx.y;
+    const int M = a.n_mics, N = a.nfft, D = a.n_angles, W = a.frames_per_block, nK = a.n_bins;
+    int kk = g * kCaponSegBins + lane;
+    const bool live = kk < nK;  // the band's last segment: the lanes past the band work on its last bin and add 0
+    if (!live) kk = nK - 1;
+    const int k = a.klo + kk;
+    const f64x2 *zr = a.Z + ((long)s * a.frames_ws + b * W) * NP * N;
+    double Rr[NT > 0 ? NT : 1], Ri[NT > 0 ? NT : 1], Rd[MP];
+#pragma unroll
+    for (int e = 0; e < NT; ++e) Rr[e] = Ri[e] = 0.0;
+#pragma unroll
+    for (int i = 0; i < MP; ++i) Rd[i] = 0.0;
+    for (int t = 0; t < W; ++t, zr += (long)NP * N) {
+        double xr[MP], xi[MP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const f64x2 z = zr[(long)p * N + k], c = zr[(long)p * N + (N - k)];
+            xr[2 * p] = z.x + c.x;
+            xi[2 * p] = z.y - c.y;
+            const bool has = 2 * p + 1 < M;
+            xr[2 * p + 1] = has ? z.y + c.y : 0.0;
+            xi[2 * p + 1] = has ? c.x - z.x : 0.0;
+        }
+#pragma unroll
+        for (int i = 0; i < MP; ++i) {
+#pragma unroll
+            for (int c = 0; c < i; ++c) {  // R_ic += x_i conj(x_c)
+                const int e = i * (i - 1) / 2 + c;
+                Rr[e] = fma(xi[i], xi[c], fma(xr[i], xr[c], Rr[e]));
+                Ri[e] = fma(-xr[i], xi[c], fma(xi[i], xr[c], Ri[e]));
+            }
+            Rd[i] = fma(xi[i], xi[i], fma(xr[i], xr[i], Rd[i]));
+        }
+    }
+    double tau = 0.0;
+#pragma unroll
+    for (int i = 0; i < MP; ++i) tau += Rd[i];  // (the pinned row's entry is an exact 0)
+    const bool ok = tau > 0.0;
+    const double inv = ok ? 1.0 / tau : 0.0, load = a.delta / (double)M;  // tau = 0: R~ = (delta / M) I, and c is forced to 0 below
+#pragma unroll
+    for (int e = 0; e < NT; ++e) {
+        Rr[e] *= inv;
+        Ri[e] *= inv;
+    }
+#pragma unroll
+    for (int i = 0; i < MP; ++i) Rd[i] = i < M ? fma(Rd[i], inv, load) : 1.0;
+    // R~ = L L^H in place, column by column; Rd[j] becomes 1 / L_jj
+#pragma unroll
+    for (int j = 0; j < MP; ++j) {
+        const double rinv = 1.0 / sqrt(Rd[j]);
+        Rd[j] = rinv;
+#pragma unroll
+        for (int i = j + 1; i < MP; ++i) {
+            Rr[i * (i - 1) / 2 + j] *= rinv;
+            Ri[i * (i - 1) / 2 + j] *= rinv;
+        }
+#pragma unroll
+        for (int c = j + 1; c < MP; ++c) {
+            const double lr = Rr[c * (c - 1) / 2 + j], li = Ri[c * (c - 1) / 2 + j];
+            Rd[c] = fma(-li, li, fma(-lr, lr, Rd[c]));
+#pragma unroll
+            for (int i = c + 1; i < MP; ++i) {  // A_ic -= L_ij conj(L_cj)
+                const double pr = Rr[i * (i - 1) / 2 + j], pi = Ri[i * (i - 1) / 2 + j];
+                Rr[i * (i - 1) / 2 + c] = fma(-pi, li, fma(-pr, lr, Rr[i * (i - 1) / 2 + c]));
+                Ri[i * (i - 1) / 2 + c] = fma(pr, li, fma(-pi, lr, Ri[i * (i - 1) / 2 + c]));
+            }
+        }
+    }
+    const double cnum = (double)M / (1.0 + a.delta);
+    const f64x2 *st = a.steer + kk;
+    double *row = a.part + (((long)g * a.n_streams + s) * a.blocks_ws + b) * D;
+    f64x2 an[MP];  // the next angle's steering column: requested in front of this angle's substitution
+#pragma unroll
+    for (int m = 0; m < MP; ++m) an[m] = m < M ? st[(long)m * nK] : f64x2{0.0, 0.0};
+    double keep = 0.0;
+    for (int d = 0; d < D; ++d) {
+        double ur[MP], ui[MP];
+#pragma unroll
+        for (int m = 0; m < MP; ++m) {
+            ur[m] = an[m].x;
+            ui[m] = an[m].y;
+        }
+        const int dn = d + 1 < D ? d + 1 : d;
+#pragma unroll
+        for (int m = 0; m < MP; ++m)
+            if (m < M) an[m] = st[((long)dn * M + m) * nK];
+        double q = 0.0;
+#pragma unroll
+        for (int i = 0; i < MP; ++i) {  // u_i = (a_i - sum_{c < i} L_ic u_c) / L_ii
+#pragma unroll
+            for (int c = 0; c < i; ++c) {
+                const int e = i * (i - 1) / 2 + c;
+                ur[i] = fma(Ri[e], ui[c], fma(-Rr[e], ur[c], ur[i]));
+                ui[i] = fma(-Ri[e], ur[c], fma(-Rr[e], ui[c], ui[i]));
+            }
+            ur[i] *= Rd[i];
+            ui[i] *= Rd[i];
+            q = fma(ui[i], ui[i], fma(ur[i], ur[i], q));
+        }
+        const double sum = wave_sum64(live && ok ? cnum / q : 0.0);
+        if (lane == (d & 63)) keep = sum;  // 64 angles' sums leave in one row of stores
+        if ((d & 63) == 63 || d == D - 1) {
+            const int dd = (d & ~63) + lane;
+            if (dd <= d) row[dd] = keep;
+        }
+    }
+}
+
+// More than 8 microphones: the same per-lane algorithm with the lower triangle (diagonal included, idx(i, c) = i (i + 1) / 2 + c) and the
+// frame's spectra / the solve's vector (NT + i) in memory, [element][lane of the grid]: consecutive lanes, consecutive addresses.
+__global__ __launch_bounds__(64) void doa_capon_ws_kernel(CaponArgs a) {
+    const int lane = threadIdx.x, G = a.n_segments;
+    const long b = blockIdx.x / G;
+    const int g = (int)(blockIdx.x - b * G), s = blockIdx.y;
+    const int M = a.n_mics, NP = (M + 1) / 2, N = a.nfft, D = a.n_angles, W = a.frames_per_block, nK = a.n_bins, NT = M * (M + 1) / 2;
+    int kk = g * kCaponSegBins + lane;
+    const bool live = kk < nK;
+    if (!live) kk = nK - 1;
+    const int k = a.klo + kk;
+    const long stride = (long)gridDim.y * gridDim.x * 64;
+    f64x2 *A = a.ws + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 64 + lane;
+    auto at = [&](int e) -> f64x2 & { return A[(long)e * stride]; };
+    const f64x2 *zr = a.Z + ((long)s * a.frames_ws + b * W) * NP * N;
+    for (int e = 0; e < NT; ++e) at(e) = f64x2{0.0, 0.0};
+    for (int t = 0; t < W; ++t, zr += (long)NP * N) {
+        for (int m = 0; m < M; ++m) {  // never the zero partner of an odd count: m < M
+            const f64x2 *pr = zr + (long)(m >> 1) * N;
+            at(NT + m) = unpack_mic(pr[k], pr[N - k], m & 1);
+        }
+        for (int i = 0; i < M; ++i) {
+            const f64x2 x = at(NT + i);
+            for (int c = 0; c < i; ++c) {
+                const f64x2 y = at(NT + c);
+                f64x2 &r = at(i * (i + 1) / 2 + c);
+                r = f64x2{fma(x.y, y.y, fma(x.x, y.x, r.x)), fma(-x.x, y.y, fma(x.y, y.x, r.y))};
+            }
+            f64x2 &r = at(i * (i + 1) / 2 + i);
+            r.x = fma(x.y, x.y, fma(x.x, x.x, r.x));
+        }
+    }
+    double tau = 0.0;
+    for (int i = 0; i < M; ++i) tau += at(i * (i + 1) / 2 + i).x;
+    const bool ok = tau > 0.0;
+    const double inv = ok ? 1.0 / tau : 0.0, load = a.delta / (double)M;
+    for (int i = 0; i < M; ++i) {
+        for (int c = 0; c < i; ++c) {
+            f64x2 &r = at(i * (i + 1) / 2 + c);
+            r = f64x2{r.x * inv, r.y * inv};
+        }
+        f64x2 &r = at(i * (i + 1) / 2 + i);
+        r.x = fma(r.x, inv, load);
+    }
+    for (int j = 0; j < M; ++j) {
+        const double rinv = 1.0 / sqrt(at(j * (j + 1) / 2 + j).x);
+        at(j * (j + 1) / 2 + j).x = rinv;
+        for (int i = j + 1; i < M; ++i) {
+            f64x2 &r = at(i * (i + 1) / 2 + j);
+            r = f64x2{r.x * rinv, r.y * rinv};
+        }
+        for (int c = j + 1; c < M; ++c) {
+            const f64x2 l = at(c * (c + 1) / 2 + j);
+            f64x2 &dg = at(c * (c + 1) / 2 + c);
+            dg.x = fma(-l.y, l.y, fma(-l.x, l.x, dg.x));
+            for (int i = c + 1; i < M; ++i) {
+                const f64x2 p = at(i * (i + 1) / 2 + j);
+                f64x2 &r = at(i * (i + 1) / 2 + c);
+                r = f64x2{fma(-p.y, l.y, fma(-p.x, l.x, r.x)), fma(p.x, l.y, fma(-p.y, l.x, r.y))};
+            }
+        }
+    }
+    const double cnum = (double)M / (1.0 + a.delta);
+    const f64x2 *st = a.steer + kk;
+    double *row = a.part + (((long)g * a.n_streams + s) * a.blocks_ws + b) * D;
+    for (int d = 0; d < D; ++d) {
+        double q = 0.0;
+        for (int i = 0; i < M; ++i) {
+            f64x2 u = st[((long)d * M + i) * nK];
+            for (int c = 0; c < i; ++c) {
+                const f64x2 l = at(i * (i + 1) / 2 + c), v = at(NT + c);
+                u = f64x2{fma(l.y, v.y, fma(-l.x, v.x, u.x)), fma(-l.y, v.x, fma(-l.x, v.y, u.y))};
+            }
+            const double rinv = at(i * (i + 1) / 2 + i).x;
+            u = f64x2{u.x * rinv, u.y * rinv};
+            at(NT + i) = u;
+            q = fma(u.y, u.y, fma(u.x, u.x, q));
+        }
+        const double sum = wave_sum64(live && ok ? cnum / q : 0.0);
+        if (lane == 0) row[d] = sum;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_capon_table(const f64x2 *src, f64x2 *dst, int n_bins, int n_mics, int n_angles, hipStream_t s) {
+    const long n = (long)n_bins * n_mics * n_angles;
+    const long blocks = (n + kDoaBlock - 1) / kDoaBlock;
+    BF_LAUNCH(capon_table_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(kDoaBlock), 0, s, src, dst, n_bins, n_mics, n_angles);
+    return hipGetLastError();
+}
+
+hipError_t launch_capon(const CaponArgs &a, const CaponPlan &p, hipStream_t s) {
+    if (a.n_blocks < 1 || a.n_blocks > p.chunk_blocks || a.n_segments != p.segments) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(a.n_blocks * p.segments), p.grid_y);
+    switch (p.mp) {
+        case 2: BF_LAUNCH(doa_capon_kernel<2>, grid, dim3(64), 0, s, a); break;
+        case 4: BF_LAUNCH(doa_capon_kernel<4>, grid, dim3(64), 0, s, a); break;
+        case 6: BF_LAUNCH(doa_capon_kernel<6>, grid, dim3(64), 0, s, a); break;
+        case 8: BF_LAUNCH(doa_capon_kernel<8>, grid, dim3(64), 0, s, a); break;
+        default:
+            if (p.path != CaponPath::kWorkspace || !a.ws) return hipErrorInvalidValue;
+            BF_LAUNCH(doa_capon_ws_kernel, grid, dim3(64), 0, s, a);
+    }
+    return hipGetLastError();
+}
 
 hipError_t launch_doa_hop_flags(const float *x, const float *hist, unsigned *flags, long n_frames, long mic_stride, long stream_stride_x,
                                 int n_streams, int n_mics, int hop, int layout, hipStream_t s) {

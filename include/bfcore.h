@@ -228,6 +228,28 @@ typedef struct bf_doa bf_doa;
 int bf_doa_create(const bf_config *cfg, const double *angles_deg, int n_angles, double freq_lo, double freq_hi,
                   int frames_per_block, bf_doa **out);
 int bf_doa_set_phat_floor(bf_doa *d, double eps);            /* >= 0; default 1e-10 */
+/* ---- the Capon (MVDR) map: the handle's second method --------------------------------------------------------------------------------
+ * SRP-PHAT localises one source: with 8 or fewer microphones the strongest source's sidelobes outrank the weaker sources.  The Capon
+ * spectrum (Capon 1969) keeps them apart; its peaks feed bf_set_theta and bf_set_interference (controllers.follow_sources).
+ *   Frames, X_m(k), the band K and the weights w_m(theta, k) are exactly those above (microphone 0's row is 1).  There is no PHAT
+ *   normalisation and the PHAT floor is ignored.
+ *   Covariance: R_{s,b}(k) = sum_{t in block b, ascending} X_{s,t}(k) X_{s,t}(k)^H (M x M), tau = trace R.
+ *   Response: tau > 0:  R~ = R / tau + (delta / M) I,  c_d(k) = M / ((1 + delta) a_d^H R~^-1 a_d),  a_d = w(theta_d, k);  else c_d(k) = 0.
+ *           delta: the diagonal loading (bf_doa_set_loading, default 1e-3).
+ *   Map:   P[s][b][d] = 1 / |K| * sum_{k in K} c_d(k), in [0, 1]: c <= (1 + delta / M) / (1 + delta), reached by one frame X = a_d.
+ *   Peak:  peak[s][b] = argmax_d P[s][b][d], the lowest d on ties.
+ * Arithmetic is in double.  Map and peak bytes do not depend on how a stream is cut into calls (at block boundaries), on the internal
+ * chunking, or on the launch: every sum has one fixed order.  Any frames_per_block >= 1 is valid: with W < M the covariance is
+ * rank-deficient and the loading makes it definite.  A silent microphone needs no special case: its row of R is zero (or the packed
+ * transform's 1e-16 residue of its pair partner).  No guarantee for non-finite input or for a subnormal tau.  All of 2 .. BF_MAX_MICS
+ * microphones work; up to 8 the covariance and its factor stay in registers, above 8 they live in device memory (correct, not tuned;
+ * its work space is part of the 256 MiB scratch).  A second steering table (the same size, bins innermost) is built when the method is
+ * first selected.
+ * Both setters take effect at the next bf_doa_process* call (one batch at a time per handle, as ever).  The history hop belongs to the
+ * stream, not to the method: switching mid-stream continues the stream.  A handle that never calls them is the SRP-PHAT handle above. */
+enum bf_doa_method { BF_DOA_SRP_PHAT = 0, BF_DOA_CAPON = 1 };
+int bf_doa_set_method(bf_doa *d, int method);                /* default BF_DOA_SRP_PHAT; BF_EINVAL: NULL handle, unknown method */
+int bf_doa_set_loading(bf_doa *d, double delta);             /* Capon's diagonal loading; default 1e-3; BF_EINVAL unless finite and 0 < delta <= 1 */
 /* n_frames: a multiple of frames_per_block (else BF_EINVAL), 0 is a no-op.  x: as bf_process_batch_device reads it (cfg.layout).
  * map: [n_streams][n_frames/W][n_angles] double, peak: [n_streams][n_frames/W] int32; either may be NULL, not both.
  * Enqueued on hip_stream, no host sync.  HIP errors: BF_EIO, text in bf_last_error(NULL). */

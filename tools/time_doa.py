@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """bf_doa: median ms per 65 536-frame batch (8 microphones, hop 512, band 100-16 000 Hz, W = 16) at 72 and 360 angles, HIP events
-around each bf_doa_process_device call on one stream, >= 20 timed runs after warm-up.  Prints one JSON line per shape."""
+around each bf_doa_process_device call on one stream, >= 20 timed runs after warm-up.  Prints one JSON line per shape.
+  time_doa.py [runs] [--method srp_phat|capon|both] [--mics M]"""
+import argparse
 import json
 import os
 import sys
@@ -10,15 +12,21 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from beamform_amd.capi import Doa  # noqa: E402
-from beamform_amd.params import make_params  # noqa: E402
+from beamform_amd.params import AIRA16_XY, make_params  # noqa: E402
 
-F, M, HOP, W = 65536, 8, 512, 16
-runs = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+ap = argparse.ArgumentParser()
+ap.add_argument("runs", nargs="?", type=int, default=20)
+ap.add_argument("--method", choices=("srp_phat", "capon", "both"), default="srp_phat")
+ap.add_argument("--mics", type=int, default=8)
+args = ap.parse_args()
+F, M, HOP, W = 65536, args.mics, 512, 16
+runs = args.runs
 x = torch.rand((M, F * HOP), device="cuda") - 0.5
 s = torch.cuda.current_stream()
-for D in (72, 360):
+for D, method in ((D, m) for D in (72, 360) for m in (("srp_phat", "capon") if args.method == "both" else (args.method,))):
     angles = np.linspace(-180.0, 180.0, D, endpoint=False)
-    doa = Doa(make_params("das", n_mics=M, hop=HOP), angles, 100.0, 16000.0, W)
+    doa = Doa(make_params("das", n_mics=M, hop=HOP, mics=AIRA16_XY[:M]), angles, 100.0, 16000.0, W)
+    doa.set_method(method)
     m = torch.empty((F // W, D), dtype=torch.float64, device="cuda")
     k = torch.empty((F // W,), dtype=torch.int32, device="cuda")
     for _ in range(3):
@@ -33,5 +41,5 @@ for D in (72, 360):
         e1.synchronize()
         ts.append(e0.elapsed_time(e1))
     doa.close()
-    print(json.dumps({"op": "bf_doa", "frames": F, "mics": M, "hop": HOP, "W": W, "angles": D, "runs": runs,
+    print(json.dumps({"op": "bf_doa", "method": method, "frames": F, "mics": M, "hop": HOP, "W": W, "angles": D, "runs": runs,
                       "median_ms": round(float(np.median(ts)), 4), "min_ms": round(float(np.min(ts)), 4)}), flush=True)
