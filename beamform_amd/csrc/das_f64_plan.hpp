@@ -35,6 +35,26 @@ constexpr size_t das_f64_sched_ws_bytes() { return kSchedCounterBytes + kSchedMa
 // built for N = 1024), wavefronts per block (one step of the microphone-pair kernel's block is 8 frames), hop slots of a block's ring
 constexpr int kDasF64Hop = 512, kDasF64Waves = 8, kDasF64RingSlots = 40;
 
+// The pairing rule of the frame-pair kernels (das_f64_w64.hip das_f64_pair_body; tests/host_emul restates it).  m0, m1, m2: the bit
+// patterns of the largest |sample| (float) of hops t - 1, t, t + 1 over the microphones that are transformed; frame t is hops t - 1, t and
+// frame t + 1 hops t, t + 1.  The two frames share their transforms only if all three maxima are finite (biased exponent below 0xFF) and
+// their exponents are at most kDasPairExpSpan apart; hops of exact zeros pair with other such hops only.
+// Why the hops and not the frames, and why 4 and not the 20 of istft_w64_kernel (stft_istft.hip): a shared transform leaves about 1e-16 of
+// its LOUDEST hop in every sample of both frames, and which neighbour a frame is paired with -- or whether it goes alone, as under
+// bf_process_hop -- depends on how a stream is cut into batches.  The float store of a sample s flips where that error reaches the
+// distance to a rounding boundary, on average with probability error / ulp(s) ~ 1e-16 R / 6e-8 for a hop a factor R below the loudest:
+// 1e-6 R per hop of 512 samples.  R = 2^20 flips samples in every such hop (seen: tests/test_dynamics_gpu.py, the 2^-20 stretch cut at an
+// odd frame -- also in the faint half of a frame that straddles the transition and is itself as loud as its partner, which is why frame
+// maxima do not do); R <= 2^5 keeps it at 3e-5 per hop at most, 1e-6 per hop on level audio.  So two cuts of one stream give the same
+// bytes only STATISTICALLY: about one differing last bit in 10^5 ... 10^6 hops.  No span makes that zero while frames are paired at all;
+// the span bounds the rate.  (A frame that goes alone in both cuts is the same bytes in both.)
+constexpr int kDasPairExpSpan = 4;
+BF_PLAN_HD bool das_f64_may_pair(unsigned m0, unsigned m1, unsigned m2) {
+    const int e0 = (int)(m0 >> 23), e1 = (int)(m1 >> 23), e2 = (int)(m2 >> 23);
+    const int hi = e0 > e1 ? (e0 > e2 ? e0 : e2) : (e1 > e2 ? e1 : e2), lo = e0 < e1 ? (e0 < e2 ? e0 : e2) : (e1 < e2 ? e1 : e2);
+    return hi < 0xFF && hi - lo <= kDasPairExpSpan;
+}
+
 struct DasSchedPlan {
     int n_levels;
     int cnt[8], size[8];   // chunks per stream / pairs per chunk of each level

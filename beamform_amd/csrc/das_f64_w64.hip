@@ -508,6 +508,26 @@ __device__ __forceinline__ void il_tile_through_plane(const il_f4 (&v)[4], float
 // of a slot starts at 4 g; a writer waits for 4 g (every reader of the previous content is done), a reader for 4 g + 2.  The first pair of
 // a chunk puts the hop in front of it (or the carried hop) into its wavefront's private slot.  The memory side of the transposition
 // overlaps the other wavefronts' transforms: measured with a plain 32 KB + 32 KB copy per pair inside the planar kernel: + 0.19 ms.
+// max(m, |x|, |y|) in one instruction; m >= 0.  A NaN operand is dropped (the pairing rule below finds NaNs in the spectrum instead).
+__device__ __forceinline__ float max3abs(float m, float x, float y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    float r;
+    asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(r) : "v"(m), "v"(x), "v"(y));
+    return r;
+#else
+    return fmaxf(m, fmaxf(fabsf(x), fabsf(y)));
+#endif
+}
+
+// The pairing rule (das_f64_plan.hpp das_f64_may_pair; istft_w64_kernel has its like, stft_istft.hip).  A transform's rounding error is
+// 1e-16 of the LOUDER of its two frames and lands in both, and so does a NaN.  Frames tA and tA + 1 therefore share their transforms only if
+// neither holds a non-finite sample and the largest magnitudes of their three hops -- each over every microphone that is transformed -- are
+// within 2^kDasPairExpSpan of each other (by the biased exponents of the float maxima; hops of exact zeros pair with other such hops only).
+// Whether that holds is known once the last microphone's samples are in registers: the hop maxima ride along the forward transforms
+// (3 registers, 12 v_max3_f32 per microphone), a NaN shows in the accumulated spectrum.  Where it does not hold -- rare, and allowed to be
+// slow -- the pair is done again as two frames on their own, the same body twice with the partner's half of the transform SET to zero
+// (not multiplied: NaN x 0): `mode` 1 = frame tA alone, its second half parked in hop tA + 1 (which only this pair writes); `mode` 2 =
+// frame tA + 1 alone, in the imaginary part where it is.  Microphone 0 with the unit row never enters a transform (below) and is left out of the maxima.
 template <int LAYOUT>
 __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const DasSched &sc) {
     __shared__ __attribute__((aligned(16))) double lds[kLdsP];
@@ -730,9 +750,16 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
             request_extra(XM >= 0, cur.d.x, cur.d.y + 2L * cur.pos);
         }
     }
+    // the pairing rule (above): 0 = what `pair` says; 1 / 2 = this pair again, frame tA / tA + 1 on its own (`cur` stays, the next pair is drawn already)
+    int mode = 0;
+    PairWork nxt;
+    nxt.have = false;
+    nxt.d = int4{0, 0, 0, 0};
+    nxt.pos = nxt.len = 0;
+    nxt.u = 0;
     while (cur.have) {  // wavefront-uniform; no block barrier below
         if constexpr (LAYOUT == 1) {  // this pair's hops into the ring (ONE inlined copy of the transposition: here), its first microphone out of it
-            curR = prepare_pair(cur);
+            if (mode == 0) curR = prepare_pair(cur);  // (a pair done again -- the pairing rule -- has its hops in the ring already)
             request_ring_mic(curR, a.slot_mic[0]);
             request_ring_extra(XM >= 0, curR);
         }
@@ -744,8 +771,7 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
         const unsigned u = cur.u;
         const bool has_t = cur.pos + 1 < cur.len, has_h = cur.pos > 0;  // boundaries u (behind this pair) and u - 1 (in front of it) inside the chunk
         float *ys = a.y + (long)stream * a.n_frames * kHop;
-        PairWork nxt;
-        nxt.have = false;
+        if (mode == 0) nxt.have = false;
         // hop tA of the microphone whose loads are in flight (request_pair_mic asked for microphone 1 of this pair); the carried hop
         // stands in for hop -1, the last frame of a stream has no hop behind it
         const float *hp0 = a.x + (long)stream * a.stream_stride_x + tA * kHop;  // microphone 0's
@@ -754,6 +780,7 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
         (void)hp0; (void)hist0; (void)first_hop; (void)last_hop;
 
         double Sr[16], Si[16];
+        float hm0 = 0.f, hm1 = 0.f, hm2 = 0.f;  // largest |sample| of hops tA - 1, tA, tA + 1 this lane has seen, over the microphones transformed
         // one microphone: forward transform of (frame tA, frame tA + 1) and S += ce_m Z_m.  Instantiated twice (FIRST: the microphone
         // that starts the sum with a multiplication): a run-time test per accumulator cost 32 scalar branches per microphone
         auto one_mic = [&](const int k, auto first_tag) {  // slot k of the pair
@@ -767,6 +794,12 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
             // buf[j]*hann_win[i] (util.h:235) and the first butterfly stage in one (see the kernel above); hop tA is the second half of
             // frame tA and the first half of frame tA + 1
             if (FIRST && XM >= 0) {  // slot 0 carries two microphones with the same weight row: their samples are added in double (exact) in front of the window
+#pragma unroll
+                for (int j = 0; j < 8; j += 2) {
+                    hm0 = max3abs(hm0, e0[j], e0[j + 1]);
+                    hm1 = max3abs(hm1, e1[j], e1[j + 1]);
+                    hm2 = max3abs(hm2, e2[j], e2[j + 1]);
+                }
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const double w0 = wrow[j], w1 = wrow[j + 8];
@@ -791,22 +824,35 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
                     im[j + 8] = fma(-u2, w1, t2);
                 }
             }
-            if (__builtin_expect(!pair, 0)) {  // a wavefront-uniform BRANCH (the asm keeps hipcc from turning it into 32 v_cndmask per microphone)
+#pragma unroll
+            for (int j = 0; j < 8; j += 2) {
+                hm0 = max3abs(hm0, n0[j], n0[j + 1]);
+                hm1 = max3abs(hm1, n1[j], n1[j + 1]);
+                hm2 = max3abs(hm2, n2[j], n2[j + 1]);
+            }
+            if (__builtin_expect(!pair || mode != 0, 0)) {  // a wavefront-uniform BRANCH (the asm keeps hipcc from turning it into 32 v_cndmask per microphone)
 #ifndef BF_PAIR_CNDMASK
                 asm volatile("" ::: "memory");
 #endif
+                if (mode == 2) {  // frame tA + 1 on its own, where it is: in the imaginary part
 #pragma unroll
-                for (int j = 0; j < 16; ++j) im[j] = 0.0;
+                    for (int j = 0; j < 16; ++j) re[j] = 0.0;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) im[j] = 0.0;
+                }
             }
             // the next microphone, or the first one of this wavefront's next pair (none left: this pair's first again, unused)
             if (k + 1 < NT) {
                 if constexpr (LAYOUT == 1) request_ring_mic(curR, a.slot_mic[k + 1]);
                 else request_pair_mic(stream, tA, a.slot_mic[k + 1]);
             } else {
-                nxt = draw_pair(s_work, sc, lane, cur.d);
+                if (mode == 0) nxt = draw_pair(s_work, sc, lane, cur.d);  // (drawn once per pair: the passes of a pair done again keep it)
                 if constexpr (LAYOUT == 0) {
-                    if (nxt.have) request_pair_mic(nxt.d.x, nxt.d.y + 2L * nxt.pos, a.slot_mic[0]);
-                    else request_pair_mic(stream, tA, a.slot_mic[0]);
+                    if (mode != 1) {
+                        if (nxt.have) request_pair_mic(nxt.d.x, nxt.d.y + 2L * nxt.pos, a.slot_mic[0]);
+                        else request_pair_mic(stream, tA, a.slot_mic[0]);
+                    }
                 }  // (LAYOUT 1: the next pair's hops are transposed, and then requested, behind this pair's epilogue)
             }
             cx<double> tw[15];
@@ -860,8 +906,25 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
                 }
             }
         };
+        // this pair's first microphone again (the passes of a pair that may not share its transforms)
+        auto request_own = [&]() {
+            if constexpr (LAYOUT == 0) {  // (LAYOUT 1: at the top of the loop)
+                request_pair_mic(stream, tA, a.slot_mic[0]);
+                request_extra(XM >= 0, stream, tA);
+            }
+        };
         one_mic(0, std::true_type{});
         for (int k = 1; k < NT; ++k) one_mic(k, std::false_type{});
+        if (mode == 0 && pair) {
+            const unsigned b0 = wave_max_u32(__float_as_uint(hm0)), b1 = wave_max_u32(__float_as_uint(hm1)), b2 = wave_max_u32(__float_as_uint(hm2));
+            const bool nan = __builtin_amdgcn_ballot_w64(hi_abs(Sr[0]) >= 0x7FF00000u || hi_abs(Si[0]) >= 0x7FF00000u) != 0;  // a non-finite sample anywhere: every bin
+            if (__builtin_expect(nan || !das_f64_may_pair(b0, b1, b2), 0)) {
+                mode = 1;
+                request_own();
+                continue;
+            }
+        }
+        const bool lone = !pair || mode == 1;           // frame tA in the real part, nothing in the imaginary part (mode 2: the other way round)
         float *yo = ys + tA * kHop;
         cx<double> tw[15];
         BF_STAGE();
@@ -901,6 +964,15 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
         // good.  Nobody waits for anybody's arithmetic -- at most for a store acknowledgement when both arrive within a microsecond.
         // microphone 0: h[n] x_0[n] / M joins Re / N in double (frame tA in the real, frame tA + 1 in the imaginary part; a lone frame's
         // imaginary part is not used)
+        // a non-finite sample of microphone 0 makes its whole frame non-finite, as it does through the reference's transform (x * 0 is
+        // zero for finite x only)
+        float z0 = 0.f, z1 = 0.f, z2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            z0 = fmaf(q0[j], 0.f, z0);
+            z1 = fmaf(q1[j], 0.f, z1);
+            z2 = fmaf(q2[j], 0.f, z2);
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const double w0 = wrow[j], w1 = wrow[j + 8];
@@ -910,8 +982,18 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
             Si[j] = fma(c * w0, inv_m, Si[j]);
             Si[j + 8] = fma((double)q2[j] * w1, inv_m, Si[j + 8]);
         }
+        const bool nf_re = __builtin_amdgcn_ballot_w64(!(z0 + z1 == 0.f)) != 0;
+        if (__builtin_expect(nf_re, 0)) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) Sr[j] = __builtin_nan("");
+        }
+        const bool nf_im = __builtin_amdgcn_ballot_w64(!(z1 + z2 == 0.f)) != 0;
+        if (__builtin_expect(nf_im, 0)) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) Si[j] = __builtin_nan("");
+        }
         float oA[16], tl[8];
-        if (pair) {
+        if (!lone) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float f1 = (float)Si[j + 8];
@@ -924,9 +1006,12 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
                 tl[j] = (float)((double)f1 * wrow[j + 8]);
             }
         }
-        float *yn = ys + (tL + 1) * kHop;
+        float *yn = ys + ((lone ? tA : tL) + 1) * kHop;
         int oT = -1, oH = -1;                            // what the claim found: 0 = nobody yet
-        if (has_t) {
+        if (__builtin_expect(mode == 1, 0)) {            // frame tA on its own: its second half waits in hop tA + 1 for frame tA + 1's first (same lanes)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) yn[(unsigned)(64 * j + lane)] = tl[j];
+        } else if (has_t) {
             oT = claim_boundary(s_state, u, lane);
             if (oT == 0) {
 #pragma unroll
@@ -940,8 +1025,12 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
             const float f = (float)Sr[j];               // (float)(Re / N): 1/N is inside the gains
             oA[j] = (float)((double)f * wrow[j]);       // o *= hann_win[n]
         }
-        if (pair) {
+        if (!lone) {
             float *y1 = ys + (tA + 1) * kHop;
+            if (__builtin_expect(mode == 2, 0)) {  // frame tA's second half was computed on its own and waits in the hop
+#pragma unroll
+                for (int j = 0; j < 8; ++j) oA[j + 8] = y1[(unsigned)(64 * j + lane)];
+            }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float f0 = (float)Si[j];
@@ -949,7 +1038,8 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
                 y1[(unsigned)(64 * j + lane)] = oA[j + 8] + b0;  // out_buff[0][j] + out_buff[1][j] as floats (util.h:302), both halves in this lane
             }
         }
-        if (has_h) {
+        if (__builtin_expect(mode == 2, 0)) {  // (frame tA's first half went out in the pass before)
+        } else if (has_h) {
             oH = claim_boundary(s_state, u - 1, lane);
             if (oH == 0) {
 #pragma unroll
@@ -996,6 +1086,11 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
         } else {
             BF_STAT(1);
         }
+        if (__builtin_expect(mode == 1, 0)) {  // now frame tA + 1
+            mode = 2;
+            request_own();
+            continue;
+        }
         if (!has_t) {  // the chunk's last frame: its second half belongs to the next chunk's first hop -- or to the next call
             if (T1 < a.n_frames) {
                 float *ynx = ys + T1 * kHop;
@@ -1024,6 +1119,7 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
             asm volatile("" ::: "memory");
             release_pair(cur, has_t);
         }
+        mode = 0;
         cur = nxt;
         ++it;
     }

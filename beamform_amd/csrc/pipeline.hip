@@ -410,6 +410,9 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
     ia.frames = d_frames_.get();
     ia.post_amp = post_amp_ ? cfg_.out_amp : 1.0;
     ia.use_post_amp = post_amp_ ? 1 : 0;
+    // das in double promises the same bytes for every cut of a stream.  The backward transform sees spectra, not hops: it cannot tell a frame
+    // that straddles a change of level (das_f64_plan.hpp das_f64_may_pair), so behind das every frame goes alone
+    if (cfg_.algo == BF_DAS) ia.pair_span = -1;
 
     if (p.fused())
         ENGINE_HIP(ks_->stft_bins(p, sa, ba, n_cus_, stream));

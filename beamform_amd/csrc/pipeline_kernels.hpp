@@ -120,6 +120,7 @@ struct IstftArgs {
     int n_streams;
     double post_amp;
     int use_post_amp;
+    int pair_span = 20;    // istft_w64_kernel: two frames share a transform only if their largest magnitudes are within 2^pair_span (negative: never; das)
 };
 // das at the reference's precision in ONE launch (N = 1024, <= 8 microphones, one look direction, no spectrum dump): das_f64_w64.hip
 struct DasF64Args {

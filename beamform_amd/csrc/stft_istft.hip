@@ -260,7 +260,8 @@ __global__ __launch_bounds__(kIw64Block, 2) void istft_w64_kernel(IstftArgs a, i
             cd v[16];
             load_row(rb, v);
             // Two frames share a transform only if neither holds a non-finite value and their largest magnitudes are within 2^20 of each
-            // other: the transform's rounding error (1e-16 of the LOUDER frame) lands in both outputs.  A frame of 1e300s beside an
+            // other (a.pair_span; negative behind das: never, so that the float output is the same bytes whichever way a stream is cut --
+            // das_f64_plan.hpp das_f64_may_pair): the transform's rounding error (1e-16 of the LOUDER frame) lands in both outputs.  A frame of 1e300s beside an
             // ordinary one (gss / lcmv on a rank-deficient covariance), or any frame beside an all-zero one, goes alone.
             unsigned ha = 0, hb = 0;
 #pragma unroll
@@ -271,7 +272,7 @@ __global__ __launch_bounds__(kIw64Block, 2) void istft_w64_kernel(IstftArgs a, i
             ha = wave_max_u32(ha);
             hb = wave_max_u32(hb);
             const int ea = (int)(ha >> 20), eb = (int)(hb >> 20);  // biased exponents; 0x7FF: NaN / Inf
-            pair = ea < 0x7FF && eb < 0x7FF && ea - eb <= 20 && eb - ea <= 20;
+            pair = ea < 0x7FF && eb < 0x7FF && ea - eb <= a.pair_span && eb - ea <= a.pair_span;
             if (pair) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {  // Ya + i Yb

@@ -63,8 +63,9 @@ enum bf_layout {
 /* Arithmetic of the das node.  The reference computes in std::complex<double> end to end (das.cpp:16-24,47-70): BF_DAS_F64 is the
  * default (bf_config_init) and what the bench headline measures.  Other algorithms always compute in double. */
 enum bf_das_impl {
-    BF_DAS_FUSED_F32 = 0, /* opt-in: one fused kernel in fp32 arithmetic (narrower than the reference's; 1.5e-7 from it, inside the 1e-5
-                             bar); also the only das path with register-resident kernels at JACK periods other than 512 and with
+    BF_DAS_FUSED_F32 = 0, /* opt-in: one fused kernel in fp32 arithmetic (narrower than the reference's; 1.5e-7 from it on signals of
+                             even level, inside the 1e-5 bar; beside silence, faint stretches or NaN: the G-frame contract at
+                             bf_process_batch); also the only das path with register-resident kernels at JACK periods other than 512 and with
                              look directions that share their forward transforms */
     BF_DAS_F64 = 1        /* default: double arithmetic like das.cpp.  Period 512, <= 8 microphones, one look direction, no spectrum
                              dump: ONE launch of the frame-pair kernel (das_f64_pair_kernel on planar input; on [sample][mic] input
@@ -285,13 +286,33 @@ int bf_process_hop(bf_handle *h, const float *const *in, float *out, uint32_t nf
 /* n_frames consecutive callbacks per stream in one call, host buffers.
  * x: layout per cfg.layout with n_frames*hop samples per mic;
  * y: [n_streams][n_frames*hop].  State carries over to the next call exactly
- * as consecutive callbacks would.  Rounding: the das kernels that pack several frames of a batch into one transform (das in double on
- * planar input: two; fp32 das at periods below 512 frames: 1024 / (2 hop)) choose the frames by their position in the batch, so the same
- * stream cut differently agrees to the last bits of the float output (<= 1e-6 of its scale), not bit for bit; every cut is within the
- * stated tolerance of the reference arithmetic.  Frames that share a transform also share its rounding error, 1e-16 of the LOUDER
- * one: beside an ordinary frame a frame of exact zeros comes out as 1e-17s where the reference writes zeros, and a frame 2^-40 below
- * its neighbour loses its own last 40 bits (das in double only: the other nodes' kernels pair microphones in the forward transform
- * and, in the backward one, only frames of comparable scale).  gss: from 57 streams on a batch runs one lane per (stream, bin) problem
+ * as consecutive callbacks would.
+ * What is promised about silence, faint stretches and non-finite samples (tests/dynamics_cases.py states both contracts):
+ *   The default precision -- das in double and every fp64 node -- per OUTPUT HOP, not per signal: no sample is non-zero where the
+ *   reference writes an exact zero; every other finite hop is within 1e-5 of the reference on its own norm; the non-finite hops are
+ *   the reference's (in the memoryless nodes, das and phase, a NaN or Inf sample in input hop h reaches hops h, h + 1, h + 2 and no
+ *   others; the recursive nodes stay non-finite from there on, as the reference does).
+ *   Rounding across cuts: the das kernels that take several frames of a batch through one transform (das in double: two; fp32 das at
+ *   periods below 512: 1024 / (2 hop)) choose the frames by their position in the batch, so the same stream cut differently agrees to
+ *   the last bits of the float output, not bit for bit.  For das in double the pairing rule below bounds how often a last bit
+ *   differs: about 1e-6 per output hop on audio of even level, 3e-5 per hop at most next to a change of level -- one sample in 10^5 to
+ *   10^6 hops; statistically, not a guarantee.  The frame-pair kernels (das in double, planar or [sample][mic] input)
+ *   take frames t and t + 1 through one transform only if neither holds a non-finite sample and the largest magnitudes of their three
+ *   hops are within 2^4 of each other (das_f64_plan.hpp das_f64_may_pair); otherwise each frame goes alone, at three times the cost for
+ *   that pair.  The backward transform pairs two frames only if both are finite and within 2^20 of each other, and never behind das.
+ *   Not covered: a faint but non-zero MICROPHONE beside loud ones.  Two microphones share a forward transform and the packed
+ *   spectrum's storage, so a microphone more than about 2^20 below its partner loses its own low bits.
+ *   BF_DAS_FUSED_F32 (fp32 opt-in): G frames may share a transform, G = 1024 / (2 hop) at periods below 512 and 2 otherwise, and the
+ *   rounding error is 1e-7 of the LOUDEST of them.  So: |y - reference| <= 1e-5 of the largest reference magnitude within G + 1 hops
+ *   on either side; exact zeros where the reference has them and every input hop within G + 1 hops is zero; the non-finite hops
+ *   contain the reference's and lie within that set widened by G hops each way.  Its frames are chosen by their position in the
+ *   batch, so the same stream cut differently agrees to the last bits of the float output, not bit for bit.
+ *   An all-zero microphone: das and gsc keep the strict contract; mcra reads channel 0 only.  phase and phasempf take arg(+-0 +- 0i)
+ *   of the dead channel -- the reference's own answer hangs on the signs of its FFT library's zeros -- and mvdr, lcmv and gss invert a
+ *   singular covariance: no parity claim there.  phase, phasempf and gss run and stay finite where the reference does; for mvdr and lcmv
+ *   the reference is NaN from frame 0 on, so nothing is promised, or tested, beyond that the node runs.  The same holds for phasempf
+ *   on frames that are all zeros in every microphone (its output there is 1e-6 of the signal, not zero).
+ * gss: from 57 streams on a batch runs one lane per (stream, bin) problem
  * (sums over the microphones as one FMA chain), below that a group of lanes per problem (pairwise sums): the demixing recursion of a
  * stream rounds differently in a small and in a large batch, 1e-16 per step on a state with long memory -- the same stream alone and
  * inside a 64-stream batch agrees to ~1e-12 on the spectrum (float output: equal but for rare last-bit flips), not bit for bit. */

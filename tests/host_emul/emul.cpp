@@ -10,6 +10,7 @@
 #include "../../beamform_amd/csrc/fft1024_w64.hpp"
 #include "../../beamform_amd/csrc/fft_small.hpp"
 #include "../../beamform_amd/csrc/geometry.hpp"
+#include "../../beamform_amd/csrc/das_f64_plan.hpp"
 
 using namespace bf;
 
@@ -487,15 +488,16 @@ void emul_das_pair_f64(int M, double sr, const double *mx, const double *my, dou
     const std::vector<f64x2> T = das_mic_gains_w64_f64(st, 8);
     const std::vector<double> h = sqrt_hann(N);
     std::vector<float> tail(H, 0.f);
-    std::vector<double> z(2 * N), Z(2 * N), U(2 * N), u(2 * N);
+    std::vector<double> z(2 * N), Z(2 * N), U(2 * N), u(2 * N), v(2 * N);
     auto sample = [&](int m, long s) -> double { return s < 0 ? 0.0 : (double)x[(size_t)m * F * H + s]; };
-    for (long t = 0; t < F; t += 2) {
-        const bool two = t + 1 < F;
+    // one transform chain: frame tr in the real part, frame ti in the imaginary part (ti < 0: none -- the part is SET to zero, not
+    // multiplied: a NaN sample of the frame left out does not get in)
+    auto chain = [&](long tr, long ti, std::vector<double> &out) {
         std::fill(U.begin(), U.end(), 0.0);
         for (int m = 0; m < M; ++m) {
             for (int n = 0; n < N; ++n) {
-                z[2 * n] = h[n] * sample(m, (t - 1) * (long)H + n);
-                z[2 * n + 1] = two ? h[n] * sample(m, t * (long)H + n) : 0.0;
+                z[2 * n] = h[n] * sample(m, (tr - 1) * (long)H + n);
+                z[2 * n + 1] = ti >= 0 ? h[n] * sample(m, (ti - 1) * (long)H + n) : 0.0;
             }
             fft1024_emul<double>(z.data(), Z.data(), -1);
             for (int lane = 0; lane < 64; ++lane)
@@ -512,7 +514,39 @@ void emul_das_pair_f64(int M, double sr, const double *mx, const double *my, dou
                     U[2 * k + 1] += G.x * Z[2 * k + 1] + G.y * Z[2 * k];
                 }
         }
-        fft1024_emul<double>(U.data(), u.data(), +1);  // unnormalised: 1/N is inside the gains
+        fft1024_emul<double>(U.data(), out.data(), +1);  // unnormalised: 1/N is inside the gains
+    };
+    // The kernel's pairing rule (das_f64_plan.hpp das_f64_may_pair): frames t and t + 1 share a transform only if neither holds a
+    // non-finite sample and the largest magnitudes of their three hops -- each over every microphone -- are within 2^kDasPairExpSpan of each other.
+    // A transform's rounding error is 1e-16 of the LOUDER frame and lands in both, and so does a NaN.  (The kernel leaves microphone 0 out
+    // of the maxima where its row is the unit row: it is added in the time domain.  A NaN counts as the largest value here; the kernel's
+    // maxima drop it and find it in the spectrum.)
+    auto hop_max = [&](long hp) {  // bits of max |x| over the microphones' hop hp, a NaN counting as the largest
+        unsigned mx = 0;
+        for (int m = 0; m < M; ++m)
+            for (int n = 0; n < H; ++n) {
+                const float f = (float)sample(m, hp * (long)H + n);
+                unsigned b;
+                memcpy(&b, &f, 4);
+                b &= 0x7fffffffu;
+                if (b > mx) mx = b;
+            }
+        return mx;
+    };
+    for (long t = 0; t < F; t += 2) {
+        const bool two = t + 1 < F;
+        bool paired = two;
+        if (two) {
+            const unsigned m0 = hop_max(t - 1), m1 = hop_max(t), m2 = hop_max(t + 1);
+            paired = bf::das_f64_may_pair(m0, m1, m2);
+        }
+        if (paired || !two) {
+            chain(t, two ? t + 1 : -1, u);
+        } else {  // each frame alone: the same chain twice, frame t + 1 in the real part of its own
+            chain(t, -1, u);
+            chain(t + 1, -1, v);
+            for (int n = 0; n < N; ++n) u[2 * n + 1] = v[2 * n];
+        }
         for (int f = 0; f < (two ? 2 : 1); ++f)
             for (int n = 0; n < H; ++n) {
                 const float o1 = (float)((double)(float)u[2 * n + f] * h[n]);
@@ -526,7 +560,7 @@ void emul_das_pair_f64(int M, double sr, const double *mx, const double *my, dou
 // das_fused_small_kernel's formulation (periods below 512 frames): R = 1024 / N consecutive frames interleaved sample by sample into one
 // 1024-point sequence, the N-point pair gains repeated R times (das_pair_gains_interleaved, fp32 table in the 32 x 32 order), one
 // 1024-point transform pair per microphone pair and GROUP of frames.  Arithmetic in double (the kernel: float).  x planar [M][F*H].
-void emul_das_small(int M, int H, double sr, const double *mx, const double *my, double theta, const float *x, long F, float *y) {
+static void das_small_impl(int M, int H, double sr, const double *mx, const double *my, double theta, const float *x, long F, float *y, bool rule) {
     const int N = 2 * H, R = 1024 / N;
     ArrayGeometry g;
     g.set(mx, my, M);
@@ -539,17 +573,17 @@ void emul_das_small(int M, int H, double sr, const double *mx, const double *my,
     const std::vector<double> hd = sqrt_hann(N);
     std::vector<float> h(N);
     for (int i = 0; i < N; ++i) h[i] = (float)hd[i];
-    std::vector<std::vector<float>> tails(1, std::vector<float>(H, 0.f));
     std::vector<float> tail(H, 0.f);
-    std::vector<double> z(2 * 1024), Z(2 * 1024), S(2 * 1024), u(2 * 1024);
+    std::vector<double> z(2 * 1024), Z(2 * 1024), S(2 * 1024), u(2 * 1024), v(2 * 1024);
     auto sample = [&](int m, long s) -> double { return (m >= M || s < 0 || s >= F * (long)H) ? 0.0 : (double)x[(size_t)m * F * H + s]; };
-    for (long tg = 0; tg < F; tg += R) {
+    // the group that starts with frame tg through one transform chain; only >= 0: that frame of the group alone, the others' slots SET to zero
+    auto chain = [&](long tg, int only, std::vector<double> &out) {
         std::fill(S.begin(), S.end(), 0.0);
         for (int p = 0; p < NP; ++p) {
             for (int n = 0; n < 1024; ++n) {  // interleaved index n = R m + i: sample m of frame tg + i
                 const int i = n % R, m = n / R;
                 const long s0 = (tg + i - 1) * (long)H + m;
-                const bool ok = tg + i < F;
+                const bool ok = tg + i < F && (only < 0 || only == i);
                 z[2 * n] = ok ? (double)h[m] * sample(2 * p, s0) : 0.0;
                 z[2 * n + 1] = ok ? (double)h[m] * sample(2 * p + 1, s0) : 0.0;
             }
@@ -562,7 +596,39 @@ void emul_das_small(int M, int H, double sr, const double *mx, const double *my,
                     S[2 * k + 1] += (double)d.x * Z[2 * k + 1] + (double)d.y * Z[2 * k];
                 }
         }
-        fft1024_emul<double>(S.data(), u.data(), +1);
+        fft1024_emul<double>(S.data(), out.data(), +1);
+    };
+    auto frame_max = [&](long t) {  // bits of max |x| over the microphones' frame t, a NaN counting as the largest
+        unsigned mxb = 0;
+        for (int m = 0; m < M; ++m)
+            for (int n = 0; n < N; ++n) {
+                const float f = (float)sample(m, (t - 1) * (long)H + n);
+                unsigned b;
+                memcpy(&b, &f, 4);
+                b &= 0x7fffffffu;
+                if (b > mxb) mxb = b;
+            }
+        return mxb;
+    };
+    for (long tg = 0; tg < F; tg += R) {
+        bool together = true;
+        if (rule) {  // das_f64_may_pair's rule on a group: every frame finite, the exponents of the frame maxima at most kDasPairExpSpan apart
+            int lo = 0x7FFFFFFF, hi = 0;
+            for (int i = 0; i < R && tg + i < F; ++i) {
+                const int e = (int)(frame_max(tg + i) >> 23);
+                lo = e < lo ? e : lo;
+                hi = e > hi ? e : hi;
+            }
+            together = hi < 0xFF && hi - lo <= kDasPairExpSpan;
+        }
+        if (together) {
+            chain(tg, -1, u);
+        } else {
+            for (int i = 0; i < R && tg + i < F; ++i) {
+                chain(tg, i, v);
+                for (int m = 0; m < N; ++m) u[2 * (R * m + i)] = v[2 * (R * m + i)];
+            }
+        }
         for (int i = 0; i < R && tg + i < F; ++i)
             for (int m = 0; m < H; ++m) {
                 const float o1 = (float)u[2 * (R * m + i)] * h[m];
@@ -572,7 +638,16 @@ void emul_das_small(int M, int H, double sr, const double *mx, const double *my,
             }
     }
 }
-
+void emul_das_small(int M, int H, double sr, const double *mx, const double *my, double theta, const float *x, long F, float *y) {
+    das_small_impl(M, H, sr, mx, my, theta, x, F, y, false);
+}
+// The same formulation with the frame-pair kernels' rule applied to the group (das_f64_plan.hpp das_f64_may_pair): a group shares its
+// transforms only if every frame is finite and the frame maxima are within 2^kDasPairExpSpan of each other, otherwise every frame goes
+// alone.  das_fused_kernel's group mode does NOT carry this rule -- the fp32 opt-in promises the grouped contract of include/bfcore.h --
+// this is what the formulation would need to meet the strict one.
+void emul_das_small_ruled(int M, int H, double sr, const double *mx, const double *my, double theta, const float *x, long F, float *y) {
+    das_small_impl(M, H, sr, mx, my, theta, x, F, y, true);
+}
 // Host geometry accessors for known-answer tests.
 void emul_freqs(int N, double sr, double *f) {
     std::vector<double> v = frequency_vector(N, sr);
@@ -590,7 +665,6 @@ void emul_hann(int N, double *h) {
 }
 
 // ---- das_f64_pair_kernel's chunk plan (csrc/das_f64_plan.hpp): the table as das_f64_sched_kernel writes it --------------------------------
-#include "../../beamform_amd/csrc/das_f64_plan.hpp"
 // fills stream / t0 / n (capacity `cap` rows) and returns the number of chunks (negative: more than `cap`); *grid = persistent blocks
 extern "C" int emul_das_plan(long n_frames, int n_streams, int n_cus, const char *env, int cap, int *stream, long *t0, long *n, int *grid) {
     const bf::DasSchedPlan p = bf::das_f64_plan(n_frames, n_streams, n_cus, (env && *env) ? env : nullptr);
@@ -599,6 +673,9 @@ extern "C" int emul_das_plan(long n_frames, int n_streams, int n_cus, const char
     for (int k = 0; k < p.n_chunks; ++k) bf::das_f64_chunk(p, n_frames, n_streams, k, &stream[k], &t0[k], &n[k]);
     return p.n_chunks;
 }
+
+// the frame-pair kernels' pairing rule on the bit patterns of three hop maxima (csrc/das_f64_plan.hpp)
+extern "C" int emul_das_may_pair(unsigned m0, unsigned m1, unsigned m2) { return bf::das_f64_may_pair(m0, m1, m2) ? 1 : 0; }
 
 // the plan's own members: out[19] = n_levels, cnt[8], size[8], n_chunks, grid
 static void das_plan_out(const bf::DasSchedPlan &p, long *out) {
