@@ -36,6 +36,7 @@ EXPORTS = (
     "bf_doa_create", "bf_doa_set_phat_floor", "bf_doa_set_method", "bf_doa_set_loading", "bf_doa_process_device", "bf_doa_process",
     "bf_doa_reset", "bf_doa_destroy",
     "bf_track_set_angles", "bf_process_batch_device_tracked", "bf_track_from_peaks_device",
+    "bf_ctrack_set_angles", "bf_process_batch_device_ctracked",
 )
 BF_DOA_MAX_ANGLES = 1024
 BF_DOA_SRP_PHAT, BF_DOA_CAPON = 0, 1   # bf_doa_method
@@ -207,6 +208,8 @@ def load():
     L.bf_doa_destroy.restype = None
     L.bf_track_set_angles.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
     L.bf_process_batch_device_tracked.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bf_ctrack_set_angles.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
+    L.bf_process_batch_device_ctracked.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.bf_track_from_peaks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_double,
                                              C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
@@ -565,6 +568,20 @@ class Beamformer:
         weighted with the table of angle track[s][t]; any index outside the installed angles (-1, say) means the handle's own theta."""
         self._chk(self._L.bf_process_batch_device_tracked(self._h, x_ptr, n_frames, y_ptr, spectrum_ptr or None, track_ptr or None,
                                                           stream or None), "bf_process_batch_device_tracked")
+
+    def set_ctrack_angles(self, angles):
+        """set_track_angles for mvdr / lcmv (bf_ctrack_set_angles; host-synchronous): one table per candidate angle, shared by the look
+        direction and every interferer column.  An empty list drops them."""
+        a = np.ascontiguousarray(angles, np.float64).ravel()
+        ptr = a.ctypes.data_as(C.POINTER(C.c_double)) if a.size else None
+        self._chk(self._L.bf_ctrack_set_angles(self._h, ptr, int(a.size)), "bf_ctrack_set_angles")
+
+    def process_device_ctracked(self, x_ptr: int, n_frames: int, y_ptr: int, track_ptr: int, n_cols: int, spectrum_ptr: int = 0, stream: int = 0):
+        """process_device with an angle per frame and constraint column (mvdr / lcmv): track_ptr -> int32 [n_streams][n_frames][n_cols] on
+        the device, column 0 = look direction, column c = interferer c; an index outside the installed angles (-1, say) means the
+        handle's own column, and so does every column from n_cols on."""
+        self._chk(self._L.bf_process_batch_device_ctracked(self._h, x_ptr, n_frames, y_ptr, spectrum_ptr or None, track_ptr or None,
+                                                           int(n_cols), stream or None), "bf_process_batch_device_ctracked")
 
     def process_device_strided(self, x_ptr: int, n_frames: int, y_ptr: int, mic_stride: int, stream: int = 0):
         """process_device on a column range of a longer planar buffer (microphone m at x_ptr + m * mic_stride samples)."""

@@ -413,3 +413,82 @@ def follow_sources(node, doa, x: np.ndarray, frames_per_block: int, controller):
                 node.set_interference(i + 1, a)
             published.append((b, theta, tuple(interf)))
     return np.concatenate(ys), published
+
+
+def sources_track(maps, controller, frames_per_block: int, n_cols: int, latency_blocks: int = 1):
+    """follow_sources' schedule as a column track (bf_process_batch_device_ctracked), pure numpy.  maps: [nb, n_angles], one row per
+    block.  Row by row, controller.on_map(row) may publish (theta, interferers); a publication of block b sets column 0 to theta and
+    columns 1 ... to the interferers in order for the frames of block b + latency_blocks and later (latency_blocks = 1: "from the next
+    block on", as follow_sources applies it).  A column the publication does not mention keeps its last index, interferers beyond
+    n_cols - 1 are dropped, and before the first publication every column is -1 (the node's own angles).  Angles are mapped to their
+    indices in controller.angles.
+    Returns (track [nb * frames_per_block, n_cols] int32, published: list of (block index, theta, tuple of interferer angles))."""
+    maps = np.asarray(maps, dtype=np.float64)
+    if maps.ndim != 2:
+        raise ValueError("maps must be [n_blocks, n_angles]")
+    nb, W, n_cols, lat = maps.shape[0], int(frames_per_block), int(n_cols), int(latency_blocks)
+    if W < 1 or n_cols < 1 or lat < 0:
+        raise ValueError("frames_per_block >= 1, n_cols >= 1, latency_blocks >= 0")
+    grid = np.asarray(controller.angles, dtype=np.float64).ravel()
+
+    def index_of(angle):
+        hit = np.flatnonzero(grid == float(angle))
+        if hit.size == 0:
+            raise ValueError(f"published angle {angle!r} is not one of controller.angles")
+        return int(hit[0])
+
+    state = np.full((nb + 1, n_cols), -1, np.int32)  # state[b]: the indices in force once blocks 0 .. b-1 have published
+    published = []
+    for b in range(nb):
+        state[b + 1] = state[b]
+        pub = controller.on_map(maps[b])
+        if pub is None:
+            continue
+        theta, interf = pub
+        state[b + 1, 0] = index_of(theta)
+        for i, a in enumerate(list(interf)[:n_cols - 1]):
+            state[b + 1, i + 1] = index_of(a)
+        published.append((b, float(theta), tuple(float(a) for a in interf)))
+    track = np.empty((nb * W, n_cols), np.int32)
+    for b in range(nb):
+        track[b * W:(b + 1) * W] = state[max(0, b - lat + 1)]
+    return track, published
+
+
+def follow_sources_tracked(node, doa, x: np.ndarray, frames_per_block: int, controller):
+    """follow_sources for a whole recording in one pass: node.set_ctrack_angles(doa.angles), ONE doa.process_device over the recording,
+    the maps to the host once, sources_track (one block of latency), ONE column-tracked batch -- instead of a doa.process, a
+    node.process and up to K + 1 table rebuilds per block.
+
+    The one difference from follow_sources: the interferer count is the node's, fixed for the batch.  A publication with more
+    interferers than the node has appends none (the extra ones are dropped), and bf_set_interference's merge rule never runs inside
+    the batch.
+
+    node: beamform_amd.capi.Beamformer (mvdr or lcmv, one stream); its track angles are replaced by doa.angles, and its theta and
+    interferers are left at the last publication, as follow_sources leaves them.  doa: beamform_amd.capi.Doa on the same geometry,
+    one stream, W = frames_per_block, angles = controller.angles.  x: [M, F*hop] float32 on the host, F a multiple of frames_per_block.
+    Returns (y [F*hop], published: list of (block index, theta, tuple of interferer angles))."""
+    import torch
+    H, W = node.H, int(frames_per_block)
+    F = x.shape[1] // H
+    nb, A, n_cols = F // W, int(doa.angles.size), int(node.S)
+    node.set_ctrack_angles(doa.angles)
+    st = torch.cuda.current_stream().cuda_stream
+    xd = torch.from_numpy(np.ascontiguousarray(x, np.float32)).cuda()
+    maps = torch.empty((nb, A), dtype=torch.float64, device="cuda")
+    yd = torch.empty((nb * W * H,), dtype=torch.float32, device="cuda")
+    doa.process_device(xd.data_ptr(), nb * W, maps.data_ptr(), 0, st)
+    track, published = sources_track(maps.cpu().numpy(), controller, W, n_cols, 1)
+    td = torch.from_numpy(track).cuda()
+    node.process_device_ctracked(xd.data_ptr(), nb * W, yd.data_ptr(), td.data_ptr(), n_cols, 0, st)
+    y = yd.cpu().numpy()
+    last = {}  # column -> the angle it was last published with
+    for _, theta, interf in published:
+        last[0] = theta
+        for i, a in enumerate(interf[:n_cols - 1]):
+            last[i + 1] = a
+    if 0 in last:
+        node.set_theta(last[0])
+    for c in sorted(k for k in last if k > 0):
+        node.set_interference(c, last[c])
+    return y, published

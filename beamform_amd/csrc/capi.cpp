@@ -162,16 +162,21 @@ int timing_collect(bf_handle *h, float *ms_mean, int *n_launches) {
     return BF_OK;
 }
 
-// track (nullable): the batch's steering track, [stream][frame] indices into the tables bf_track_set_angles installed
+// track (nullable): the batch's steering track, [stream][frame] indices into the tables bf_track_set_angles installed; with track_cols > 0
+// a column track, [stream][frame][track_cols] indices into the tables bf_ctrack_set_angles installed
 int run_batch_device(bf_handle *h, const float *x_dev, size_t n_frames, float *y_dev, void *spectrum_dev, hipStream_t s,
-                     int layout, long mic_stride, const int32_t *track = nullptr) {
+                     int layout, long mic_stride, const int32_t *track = nullptr, int track_cols = 0) {
     if (n_frames == 0) return BF_OK;
     RunSnapshot snap;
     int rc = sync_tables(h, s, &snap);
     if (rc != BF_OK) return rc;
     if (track) {
-        if (snap.track_n == 0) return fail(h, BF_EINVAL, "tracked batch: no track angles installed (bf_track_set_angles)");
+        if (snap.track_n == 0)
+            return fail(h, BF_EINVAL, track_cols > 0 ? "column-tracked batch: no track angles installed (bf_ctrack_set_angles)"
+                                                     : "tracked batch: no track angles installed (bf_track_set_angles)");
+        if (track_cols > snap.kp1) return fail(h, BF_EINVAL, "column-tracked batch: n_cols above the handle's column count");
         snap.track = track;
+        snap.track_cols = track_cols;
     }
     // the engine brackets its dominant kernel with this pair when it has one (fused fp32 das, das fp64 in one launch); otherwise the pair
     // stays unrecorded and the session's mean is taken over nothing (callers fall back to the call time)
@@ -438,16 +443,15 @@ int bf_process_batch_device(bf_handle *h, const float *x_dev, size_t n_frames, f
 // ---- steering tracks ---------------------------------------------------------------------------------------------------------------
 // One table per candidate angle: the bytes bf_set_theta(h, angle) would leave in look direction 0's table (the same update_weights
 // code; microphone 0's row as it stands: written by the cold start, quirk Q3).  Device layout [angle][mic][N].
-int bf_track_set_angles(bf_handle *h, const double *angles_deg, int n_angles) {
-    if (!h) return BF_EINVAL;
-    if (!h->engine->can_track()) return fail(h, BF_ENOSYS, "steering tracks: das in double, phase and phasempf with one look direction");
-    if (n_angles < 0 || n_angles > BF_TRACK_MAX_ANGLES) return fail(h, BF_EINVAL, "bf_track_set_angles: n_angles must be 0 .. BF_TRACK_MAX_ANGLES");
-    if (n_angles > 0 && !angles_deg) return fail(h, BF_EINVAL, "bf_track_set_angles: angles is NULL");
+namespace {
+int install_angle_tables(bf_handle *h, const double *angles_deg, int n_angles) {
+    if (n_angles < 0 || n_angles > BF_TRACK_MAX_ANGLES) return fail(h, BF_EINVAL, "track angles: n_angles must be 0 .. BF_TRACK_MAX_ANGLES");
+    if (n_angles > 0 && !angles_deg) return fail(h, BF_EINVAL, "track angles: angles is NULL");
     for (int a = 0; a < n_angles; ++a)
-        if (!std::isfinite(angles_deg[a])) return fail(h, BF_EINVAL, "bf_track_set_angles: angle not finite");
+        if (!std::isfinite(angles_deg[a])) return fail(h, BF_EINVAL, "track angles: angle not finite");
     const size_t per = (size_t)h->M * h->N;
     if (per * (size_t)n_angles * sizeof(f64x2) > (512ull << 20))
-        return fail(h, BF_EINVAL, "bf_track_set_angles: tables (angles x mics x bins) above 512 MiB");
+        return fail(h, BF_EINVAL, "track angles: tables (angles x mics x bins) above 512 MiB");
     BF_HIP(h, hipSetDevice(h->device));
     std::lock_guard<std::mutex> lk(h->mu);
     std::vector<f64x2> t(per * (size_t)n_angles);
@@ -464,6 +468,38 @@ int bf_track_set_angles(bf_handle *h, const double *angles_deg, int n_angles) {
     }
     const int rc = h->engine->install_track_tables(t, n_angles);
     return rc == BF_OK ? BF_OK : fail(h, rc, h->engine->error().c_str());
+}
+}  // namespace
+
+int bf_track_set_angles(bf_handle *h, const double *angles_deg, int n_angles) {
+    if (!h) return BF_EINVAL;
+    if (!h->engine->can_track()) return fail(h, BF_ENOSYS, "steering tracks: das in double, phase and phasempf with one look direction");
+    return install_angle_tables(h, angles_deg, n_angles);
+}
+
+// Column tracks (mvdr / lcmv): the same tables -- calculate_interf_delays is calculate_delays with another angle (util.h:136-188), so one
+// table per candidate angle serves every constraint column.  The kernels never read a table's microphone-0 row: that entry is the handle's
+// own column's (quirk Q3), so a structural bf_set_interference after this call leaves nothing stale behind.
+int bf_ctrack_set_angles(bf_handle *h, const double *angles_deg, int n_angles) {
+    if (!h) return BF_EINVAL;
+    if (h->cfg.algo != BF_MVDR && h->cfg.algo != BF_LCMV) return fail(h, BF_ENOSYS, "column tracks: mvdr and lcmv with one look direction");
+    if (h->n_dirs > 1 || !h->engine->can_ctrack()) return fail(h, BF_EINVAL, "column tracks: one look direction per handle");
+    return install_angle_tables(h, angles_deg, n_angles);
+}
+
+int bf_process_batch_device_ctracked(bf_handle *h, const float *x_dev, size_t n_frames, float *y_dev, void *spectrum_dev,
+                                     const int32_t *track_dev, int n_cols, void *hip_stream) {
+    if (!h || !x_dev || !y_dev) return BF_EINVAL;
+    if (h->cfg.algo != BF_MVDR && h->cfg.algo != BF_LCMV) return fail(h, BF_ENOSYS, "column tracks: mvdr and lcmv with one look direction");
+    if (h->n_dirs > 1) return fail(h, BF_EINVAL, "column-tracked batch: one look direction per handle");
+    if (!track_dev) return fail(h, BF_EINVAL, "column-tracked batch: track is NULL");
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (n_cols < 1 || n_cols > h->S) return fail(h, BF_EINVAL, "column-tracked batch: n_cols must be 1 .. 1 + the handle's interferers");
+    }
+    BF_HIP(h, hipSetDevice(h->device));
+    return run_batch_device(h, x_dev, n_frames, y_dev, spectrum_dev, (hipStream_t)hip_stream, h->cfg.layout, (long)n_frames * h->H,
+                            track_dev, n_cols);
 }
 
 int bf_process_batch_device_tracked(bf_handle *h, const float *x_dev, size_t n_frames, float *y_dev, void *spectrum_dev,

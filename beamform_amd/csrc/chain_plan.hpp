@@ -17,6 +17,8 @@ namespace bf {
 // those names (switches.hpp).  gss_rows (last, so that a shape written without it means one): separated sources gss emits per beam
 // (bf_config.gss_out_sources; 0 = 1, ignored by every other node).  track (last again: a shape written without it means false): the batch
 // carries a steering track (bf_process_batch_device_tracked: a table index per (stream, frame); das / phase / phasempf, one look direction).
+// ctrack_cols (last once more: a shape written without it means 0 = none): the batch carries a column track
+// (bf_process_batch_device_ctracked: a table index per (stream, frame, constraint column); mvdr / lcmv, one look direction).
 struct ChainShape {
     int algo, n_fft, layout, n_mics, n_streams, n_dirs, kp1, past_windows, precision;
     bool dump;
@@ -29,6 +31,7 @@ struct ChainShape {
     bool gsc_serial;
     int gss_rows;
     bool track;
+    int ctrack_cols;
 };
 
 // The kernels of each stage, template arguments behind them as ChainPlan holds them:
@@ -39,7 +42,8 @@ struct ChainShape {
 //   rec    phasempf's pass over the frames: mpf_recursion_kernel, or mpf_rec_istft_kernel, which runs the backward transform too
 //   istft  istft_w64_kernel<band_rows>, istft32_kernel, istft_small_kernel, istft_split_kernel, istft_generic_kernel + ola_generic_kernel
 //          with ChainPlan::track their twins that resolve the steering table per frame: stft_bins_w64_track_kernel + fused_tail_track_kernel,
-//          pointwise_track_kernel<mp, algo>, mpf_mask_track_kernel<mp>
+//          pointwise_track_kernel<mp, algo>, mpf_mask_track_kernel<mp>; with ChainPlan::ctrack mvdr_fast_track_kernel<mp, km, !z48> and
+//          mvdr_lcmv_track_kernel<mp, km> (cov2d_kernel has no twin: 9 .. 16 microphones run the group kernel's)
 //   tail   smooth4_kernel<t0> or smooth_kernel, then smooth_state_kernel (phasempf); gsc_nlms_kernel / gsc_nlms_par_kernel <t0 = NBM, t1 = KPL>
 //          or gsc_nlms_mw_kernel<t0 = NW, t1 = NBL, t2 = KPL> (gsc)
 enum class ChainFront { kStft, kStftSmall, kStftWave2048, kStftGeneric, kFusedW64, kFusedSmall, kFusedSplit };
@@ -68,6 +72,9 @@ struct ChainPlan {
     int rows;
     // the front / per-bin kernels are the track twins: the steering pointer of a frame comes from the batch's track (BinsArgs::track)
     bool track;
+    // the per-bin kernel is the column-track twin of mvdr_fast_kernel / mvdr_lcmv_kernel: the constraint columns of a frame come from the
+    // batch's track (BinsArgs::track with track_cols entries per frame); mvdr / lcmv with one look direction only
+    bool ctrack;
     bool fused() const { return front >= ChainFront::kFusedW64; }
     bool rec_istft() const { return rec == ChainRec::kRecIstft; }
 };
@@ -90,6 +97,7 @@ inline ChainPlan chain_decide(const ChainShape &c) {
     ChainPlan p{};
     p.algo = a; p.layout = c.layout; p.z48 = cov && mixed; p.rows = R;
     p.track = c.track && D == 1 && (pointwise || mpf);
+    p.ctrack = c.ctrack_cols > 0 && D == 1 && cov;
     // nodes without a frame history, up to 8 microphones, one look direction: STFT and per-bin stage in one launch, spectra never leave the CU.
     // A tracked batch only at N = 1024: the fused fronts of the other sizes keep a thread's steering entries in registers across frames
     const bool fused = c.fused_bins != 0 && N <= 2048 && M <= 8 && D == 1 && (pointwise || mpf) && (!p.track || N == 1024);
@@ -117,9 +125,9 @@ inline ChainPlan chain_decide(const ChainShape &c) {
         p.bins = cov ? ChainBins::kMvdrLcmv : ChainBins::kGss;
         p.km = kp1 <= 1 ? 1 : kp1 <= 4 ? 4 : kp1 <= 8 ? 8 : 16;
         p.mp = kp1 <= 4 ? 32 : kp1 <= 8 ? (M <= 8 ? 8 : mp4) : (M <= 16 ? 16 : 32);
-    } else if (cov && !c.mvdr_group && M > 8) {
+    } else if (cov && !c.mvdr_group && M > 8 && !p.ctrack) {
         p.bins = ChainBins::kCov2d; p.km = km; p.wps = km == 1 ? 3 : 2;  // 2-D cyclic 4 x 4 lanes per problem; wavefronts per SIMD
-    } else if (cov && !c.mvdr_group && (M > 2 || kp1 <= 2)) {
+    } else if (cov && !c.mvdr_group && M <= 8 && (M > 2 || kp1 <= 2)) {  // (a column-tracked batch of 9 .. 16 microphones: the group kernel below)
         // one lane per (tile, problem); lcmv's columns ride along while they fit the register file (K = 3 only at 7-8 microphones).
         // Two microphones hold at most two columns: more go to the group kernel
         p.bins = ChainBins::kMvdrFast; p.mp = M <= 2 ? 2 : M <= 4 ? 4 : M <= 6 ? 6 : 8;

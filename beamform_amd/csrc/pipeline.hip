@@ -169,8 +169,9 @@ class BinPipelineImpl : public Engine {
     }
 
     bool can_track() const override { return (cfg_.algo == BF_DAS || cfg_.algo == BF_PHASE || cfg_.algo == BF_PHASEMPF) && D_ == 1; }
+    bool can_ctrack() const override { return cov_node_ && D_ == 1; }
     int install_track_tables(const std::vector<f64x2> &tables, int n_angles) override {
-        if (!can_track()) return Engine::install_track_tables(tables, n_angles);
+        if (!can_track() && !can_ctrack()) return Engine::install_track_tables(tables, n_angles);
         // The tables in force are RETIRED, not freed: another thread may have taken them in its snapshot and still be enqueueing the kernels
         // of that batch, which no synchronisation here can wait for.  What the previous call retired goes now: every batch that could
         // hold it was begun before that call returned, and the device is idle with respect to what has been enqueued
@@ -348,7 +349,8 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
     const ChainPlan p = chain_decide(ChainShape{cfg_.algo, N_, layout, M_, S_, cfg_.n_dirs > 1 ? cfg_.n_dirs : 1, snap.kp1, cfg_.past_windows,
                                                 cfg_.precision, spectrum != nullptr, F, n_cus_, cfg_.gsc_filter_size, cfg_.smooth_size,
                                                 band_yh_lo_, band_yh_hi_, (reinterpret_cast<size_t>(y) & 15) == 0, sw.fused_bins,
-                                                sw.stft_small, sw.stft_split, sw.mvdr_group, sw.gss_group, sw.gsc_serial, R_, snap.track != nullptr});
+                                                sw.stft_small, sw.stft_split, sw.mvdr_group, sw.gss_group, sw.gsc_serial, R_, snap.track != nullptr && snap.track_cols == 0,
+                                                snap.track != nullptr ? snap.track_cols : 0});
     float *const hist = d_hist2_[hist_cur_].get();
     const long FT = Phist_ + F;  // frames in the Z workspace per stream
     ENGINE_HIP(d_Z_.reserve(p.z_bytes));
@@ -388,8 +390,9 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
     ba.cfg = cfg_; ba.gssW = d_gssW_.get(); ba.mpf = d_mpf_.get(); ba.gss_reset_mask = snap.gss_reset_mask;
     ba.yh32 = p.yh32 ? 1 : 0; ba.mpf32 = p.mpf32 ? 1 : 0; ba.yh_lo = p.yh_lo; ba.yh_hi = p.yh_hi;
     ba.gss_rows = p.rows;
-    if (p.track) {  // the per-frame table: tables + track[stream][frame] * stride where the index names a table, ba.steer otherwise
+    if (p.track || p.ctrack) {  // the per-frame table: tables + track[stream][frame] * stride where the index names a table, ba.steer otherwise
         ba.track = snap.track; ba.track_tables = snap.track_tables; ba.track_n = snap.track_n; ba.track_stride = (long)M_ * N_;
+        ba.track_cols = p.ctrack ? snap.track_cols : 0;  // mvdr / lcmv: an index per frame and constraint column
     }
     if (p.rec_istft()) {  // mpf_rec_istft_kernel: a block per stream, the y_fft rows stay in LDS
         ba.rec_istft = 1;

@@ -40,6 +40,8 @@ struct RunSnapshot {
     const f64x2 *track_tables = nullptr;
     int track_n = 0;
     const int32_t *track = nullptr;
+    // > 0: `track` is a column track, [stream][frame][track_cols] (bf_process_batch_device_ctracked; mvdr / lcmv)
+    int track_cols = 0;
 };
 
 class Engine {
@@ -58,6 +60,9 @@ class Engine {
     // on the host, n_angles = 0 drops them.  Host-synchronous (waits for the device); the replaced tables stay allocated until the next
     // call, so a run() another thread is still enqueueing with them in its snapshot reads live memory.  Caller holds the control-plane mutex
     virtual bool can_track() const { return false; }
+    // column tracks (mvdr / lcmv with one look direction: a table index per frame and constraint column); the tables are installed by
+    // the same install_track_tables
+    virtual bool can_ctrack() const { return false; }
     virtual int install_track_tables(const std::vector<f64x2> &, int) {
         err_ = "steering tracks: das in double, phase and phasempf with one look direction";
         return BF_ENOSYS;

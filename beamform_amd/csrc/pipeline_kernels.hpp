@@ -102,6 +102,11 @@ struct BinsArgs {
     const int32_t *track = nullptr;        // [stream][n_frames]
     const f64x2 *track_tables = nullptr;   // [angle][mic][N]
     int track_n = 0;
+    // column track (ChainPlan::ctrack; mvdr / lcmv): track is [stream][n_frames][track_cols] and entry c of a frame picks constraint column
+    // c (0 = look direction, c >= 1 = interferer c) by the same rule -- a table, or the column c of `steer`; columns >= track_cols are
+    // `steer`'s, and microphone 0's entry of every column always is (quirk Q3).  (In the four bytes of padding behind track_n: the
+    // argument block of every per-bin kernel keeps its size and its offsets)
+    int track_cols = 0;
     long track_stride = 0;                 // f64x2 elements per table
 };
 struct IstftArgs {

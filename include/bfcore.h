@@ -463,7 +463,7 @@ int bf_resampler_default_table(float *dst, int cap, int *index_inc);            
  *   /theta table, the one an untracked batch uses.  A bad index is never read through; -1 is the way to say "nothing published yet".
  *   Supported: BF_DAS with BF_DAS_F64, BF_PHASE, BF_PHASEMPF, one look direction (n_dirs <= 1); any n_streams, both layouts, every
  *   period, both precisions.  Every other handle answers BF_ENOSYS (gss re-initialises its demixing matrices on every /theta,
- *   gss.cpp:90-93; mvdr / lcmv and the fp32 das kernels are not built for tracks).
+ *   gss.cpp:90-93; the fp32 das kernels are not built for tracks; mvdr / lcmv have entry points of their own, bf_ctrack_* below).
  *   Kernels: period 512 with <= 8 microphones keeps STFT and per-bin stage in one launch (the spectra never leave the CU); every other
  *   shape runs STFT -> per-bin kernel -> ISTFT.  das in double never takes its one-launch frame-pair kernel for a tracked batch (two
  *   frames share a transform there), so an untracked batch is the faster way to run a constant angle.
@@ -497,6 +497,43 @@ int bf_process_batch_device_tracked(bf_handle *h, const float *x_dev, size_t n_f
 int bf_track_from_peaks_device(const int32_t *peak_dev, const double *map_dev, int n_angles, int n_streams, size_t n_blocks,
                                int frames_per_block, int latency_blocks, double min_peak, int32_t *carry_dev, int32_t *track_dev,
                                void *hip_stream);
+
+/* ---- column tracks: mvdr and lcmv, an angle per frame AND per constraint column ----------------------------------------------------
+ * mvdr's theta_roscallback only rewrites its steering vector (mvdr.cpp:41-60, 139-143) and lcmv's update_weights() rebuilds every
+ * constraint column from `angle` and `interference_angles` (lcmv.cpp:44-86); neither touches past_ffts.  So a steering vector per frame
+ * is the reference's semantics for these nodes too.  They get entry points of their own (bf_track_* keeps answering BF_ENOSYS on them)
+ * because an lcmv track carries one index per constraint column, not one per frame.
+ *   Track layout: track_dev is [n_streams][n_frames][n_cols] int32 on the device, n_cols from 1 to 1 + bf_n_interferers(h) at the time
+ *   of the call (mvdr: 1 only).  Column 0 is the look direction, column c >= 1 is interferer c (the 1-based id of bf_set_interference).
+ *   Semantics: frame t of stream s is processed exactly as the reference's callback t is with angle = angles[track[s][t][0]] and
+ *   interference_angles[c-1] = angles[track[s][t][c]] in force and update_weights() (without `ini`) run after the assignment.  The
+ *   interferer COUNT does not change inside a batch, and the callback's proximity rule (lcmv.cpp:264-279: an interferer that comes within
+ *   interf_angle_threshold of another is removed) is NOT applied: where two columns of one frame lie that close the reference would
+ *   have dropped one, and no parity is claimed there.
+ *   Index rule, per column: 0 .. n_angles-1 selects that angle's table; ANY other value selects the handle's own column c (what an
+ *   untracked batch uses).  Columns >= n_cols are always the handle's own.  A bad index is never read through.
+ *   Microphone 0: whatever the index, the entry of microphone 0 in column c is the handle's own column c's entry -- 1 after create, 0
+ *   after a structural interferer change (quirk Q3, lcmv.cpp:50-56, 243-252).  The kernels read it from the handle's table at every
+ *   frame, so a structural bf_set_interference after bf_ctrack_set_angles leaves nothing stale behind.
+ *   State: the history hop, the covariance history of the previous past_windows frames, the overlap-add tail and out_amp carry across
+ *   frames and calls exactly as in an untracked batch; tracked and untracked calls may alternate on one handle.
+ *   Supported: BF_MVDR and BF_LCMV, n_dirs <= 1, any n_streams, both layouts, both precisions, every period, up to 32 microphones and
+ *   the handle's current column count, with or without spectrum_dev.
+ *   Kernels: up to 8 microphones (and the columns mvdr_fast_kernel takes) run mvdr_fast_track_kernel -- for mvdr without the
+ *   register-resident steering vector of the untracked kernel, the columns are re-read per frame as lcmv's always were.  Everything
+ *   else, 9 .. 16 microphones included, runs mvdr_lcmv_track_kernel, the group kernel's twin: cov2d_kernel has no twin, so those shapes
+ *   are correct but not tuned.  BF_MVDR_TILE and BF_MVDR_GROUP act as on untracked batches.  An untracked batch is the faster way to
+ *   run constant angles. */
+/* bf_track_set_angles for these handles, with its rules: host-synchronous, thread-safe beside a batch being enqueued, the replaced tables
+ * retired until the next install, the tables no part of the state blob.  One table per candidate angle serves every column
+ * (calculate_interf_delays is calculate_delays with another angle, util.h:136-188).  BF_ENOSYS: any algorithm but mvdr / lcmv.
+ * BF_EINVAL: NULL handle, n_dirs > 1, a non-finite angle, n_angles outside 0 .. BF_TRACK_MAX_ANGLES, tables above 512 MiB. */
+int bf_ctrack_set_angles(bf_handle *h, const double *angles_deg, int n_angles);
+/* One batch with a column track (it must stay valid until hip_stream has passed the batch).  Checked before any device work:
+ * BF_ENOSYS: any algorithm but mvdr / lcmv.  BF_EINVAL: NULL handle, x, y or track; no angles installed; n_cols < 1 or above the
+ * current column count; n_dirs > 1. */
+int bf_process_batch_device_ctracked(bf_handle *h, const float *x_dev, size_t n_frames, float *y_dev, void *spectrum_dev,
+                                     const int32_t *track_dev, int n_cols, void *hip_stream);
 
 #ifdef __cplusplus
 }
