@@ -15,7 +15,7 @@ OBJS := $(patsubst $(SRC)/%.hip,$(OBJ)/%.o,$(HIP_SRCS)) $(patsubst $(SRC)/%.cpp,
         $(foreach n,$(NFFTS),$(foreach b,$(BIN_SRCS),$(OBJ)/$(b)_n$(n).o))
 HDRS := $(wildcard $(SRC)/*.hpp) include/bfcore.h
 
-all: $(LIB) oracle examples/file_node examples/theta_scan examples/shard_node examples/separate_node
+all: $(LIB) oracle examples/file_node examples/theta_scan examples/shard_node examples/separate_node examples/follow_sources_node
 
 examples/shard_node: examples/shard_node.cpp include/bfcore.h $(LIB)
 	$(HIPCC) -O2 -std=c++17 -x hip --offload-arch=$(ARCH) examples/shard_node.cpp -o $@ -Lbeamform_amd/lib -lbfcore -L/opt/rocm/lib -lrccl -Wl,-rpath,'$$ORIGIN/../beamform_amd/lib'
@@ -25,6 +25,9 @@ examples/theta_scan: examples/theta_scan.cpp include/bfcore.h $(LIB)
 
 examples/separate_node: examples/separate_node.cpp include/bfcore.h $(LIB)
 	$(HIPCC) -O2 -std=c++17 -x hip --offload-arch=$(ARCH) examples/separate_node.cpp -o $@ -Lbeamform_amd/lib -lbfcore -Wl,-rpath,'$$ORIGIN/../beamform_amd/lib'
+
+examples/follow_sources_node: examples/follow_sources_node.cpp include/bfcore.h $(LIB)
+	$(HIPCC) -O2 -std=c++17 -x hip --offload-arch=$(ARCH) examples/follow_sources_node.cpp -o $@ -Lbeamform_amd/lib -lbfcore -Wl,-rpath,'$$ORIGIN/../beamform_amd/lib'
 
 examples/file_node: examples/file_node.cpp include/bf_node_shim.hpp include/bfcore.h $(LIB)
 	$(HIPCC) -O2 -std=c++17 -x hip --offload-arch=$(ARCH) examples/file_node.cpp -o $@ -Lbeamform_amd/lib -lbfcore -Wl,-rpath,'$$ORIGIN/../beamform_amd/lib'
@@ -62,7 +65,7 @@ emul:
 	g++ -O2 -std=c++17 -fPIC -shared -o tests/host_emul/libemul.so tests/host_emul/emul.cpp
 
 clean:
-	rm -rf build $(LIB) tests/host_emul/libemul.so examples/file_node examples/theta_scan examples/shard_node examples/separate_node
+	rm -rf build $(LIB) tests/host_emul/libemul.so examples/file_node examples/theta_scan examples/shard_node examples/separate_node examples/follow_sources_node
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle emul ubench clean dispatch-table

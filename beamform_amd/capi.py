@@ -37,10 +37,12 @@ EXPORTS = (
     "bf_doa_reset", "bf_doa_destroy",
     "bf_track_set_angles", "bf_process_batch_device_tracked", "bf_track_from_peaks_device",
     "bf_ctrack_set_angles", "bf_process_batch_device_ctracked",
+    "bf_doa_pick_device", "bf_ctrack_from_picks_device",
 )
 BF_DOA_MAX_ANGLES = 1024
 BF_DOA_SRP_PHAT, BF_DOA_CAPON = 0, 1   # bf_doa_method
 BF_TRACK_MAX_ANGLES = 1024   # = BF_DOA_MAX_ANGLES: a Doa peak index is a track index
+BF_DOA_MAX_PICKS = 16        # = BF_MAX_INTERF + 1: a look direction and every interferer
 
 
 class BfConfig(C.Structure):
@@ -212,6 +214,10 @@ def load():
     L.bf_process_batch_device_ctracked.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.bf_track_from_peaks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_double,
                                              C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bf_doa_pick_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_void_p,
+                                     C.c_void_p]
+    L.bf_ctrack_from_picks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_double,
+                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -617,6 +623,33 @@ def track_from_peaks_device(peak_ptr: int, map_ptr: int, n_angles: int, n_stream
                                       stream or None)
     if rc:
         raise BfError(rc, "bf_track_from_peaks_device", (L.bf_last_error(None) or b"").decode() or L.bf_strerror(rc).decode())
+
+
+def doa_pick_device(map_ptr: int, angles_ptr: int, n_angles: int, n_streams: int, n_blocks: int, k: int, min_sep_deg: float,
+                    rel_floor: float, picks_ptr: int, stream: int = 0):
+    """Doa maps [n_streams][n_blocks][n_angles] and the grid [n_angles] float64 (degrees, on the device) -> picks
+    [n_streams][n_blocks][k] int32, on the device (bf_doa_pick_device): per row controllers.pick_sources' indices, strongest first, -1 in
+    the unused places."""
+    L = load()
+    rc = L.bf_doa_pick_device(map_ptr or None, angles_ptr or None, int(n_angles), int(n_streams), int(n_blocks), int(k),
+                              float(min_sep_deg), float(rel_floor), picks_ptr or None, stream or None)
+    if rc:
+        raise BfError(rc, "bf_doa_pick_device", (L.bf_last_error(None) or b"").decode() or L.bf_strerror(rc).decode())
+
+
+def ctrack_from_picks_device(picks_ptr: int, map_ptr: int, n_angles: int, k: int, n_streams: int, n_blocks: int, frames_per_block: int,
+                             latency_blocks: int, min_peak: float, n_cols: int, carry_ptr: int, track_ptr: int, stream: int = 0):
+    """Picks [n_streams][n_blocks][k] (and maps, 0 = none when min_peak <= 0) -> the column track
+    [n_streams][n_blocks * frames_per_block][n_cols] of their frames, on the device (bf_ctrack_from_picks_device): controllers.sources_track
+    with a DoaSources controller.  A block publishes when its first pick's map value is not below min_peak; column c of every frame of
+    block b is pick c of the latest block <= b - latency_blocks that published one, carry[s][c] where there is none; carry
+    [n_streams][n_cols] int32 is updated so that the next call continues the stream (start with -1: the handle's own columns)."""
+    L = load()
+    rc = L.bf_ctrack_from_picks_device(picks_ptr or None, map_ptr or None, int(n_angles), int(k), int(n_streams), int(n_blocks),
+                                       int(frames_per_block), int(latency_blocks), float(min_peak), int(n_cols), carry_ptr or None,
+                                       track_ptr or None, stream or None)
+    if rc:
+        raise BfError(rc, "bf_ctrack_from_picks_device", (L.bf_last_error(None) or b"").decode() or L.bf_strerror(rc).decode())
 
 
 class Doa:

@@ -492,3 +492,50 @@ def follow_sources_tracked(node, doa, x: np.ndarray, frames_per_block: int, cont
     for c in sorted(k for k in last if k > 0):
         node.set_interference(c, last[c])
     return y, published
+
+
+def follow_sources_device(node, doa, x: np.ndarray, frames_per_block: int, k: int, min_sep_deg: float, rel_floor: float = 0.0,
+                          min_peak: float = 0.0):
+    """follow_sources_tracked with DoaSources(doa.angles, k, min_sep_deg, rel_floor, min_peak) as four enqueues on one stream, with
+    nothing copied or synchronised in between: doa.process_device (the map of every block), doa_pick_device (pick_sources on the
+    device), ctrack_from_picks_device (sources_track: latency 1, carry -1, n_cols = node.S) and node.process_device_ctracked.  Picks and
+    maps come back once, at the end, for the list of publications.
+
+    The track holds the picks themselves, so doa.angles should not list an angle twice (sources_track names the first of equal
+    angles; with min_sep_deg > 0 a duplicate is never picked anyway).
+
+    node, doa, x: as follow_sources_tracked takes them; the node is left at the last publication in the same way.
+    Returns (y [F*hop], published: list of (block index, theta, tuple of interferer angles))."""
+    import torch
+    from .capi import ctrack_from_picks_device, doa_pick_device
+    H, W, k = node.H, int(frames_per_block), int(k)
+    F = x.shape[1] // H
+    nb, A, n_cols = F // W, int(doa.angles.size), int(node.S)
+    node.set_ctrack_angles(doa.angles)
+    st = torch.cuda.current_stream().cuda_stream
+    xd = torch.from_numpy(np.ascontiguousarray(x, np.float32)).cuda()
+    ad = torch.from_numpy(np.ascontiguousarray(doa.angles, np.float64)).cuda()
+    maps = torch.empty((nb, A), dtype=torch.float64, device="cuda")
+    picks = torch.empty((nb, k), dtype=torch.int32, device="cuda")
+    carry = torch.full((n_cols,), -1, dtype=torch.int32, device="cuda")
+    track = torch.empty((nb * W, n_cols), dtype=torch.int32, device="cuda")
+    yd = torch.empty((nb * W * H,), dtype=torch.float32, device="cuda")
+    doa.process_device(xd.data_ptr(), nb * W, maps.data_ptr(), 0, st)
+    doa_pick_device(maps.data_ptr(), ad.data_ptr(), A, 1, nb, k, min_sep_deg, rel_floor, picks.data_ptr(), st)
+    ctrack_from_picks_device(picks.data_ptr(), maps.data_ptr(), A, k, 1, nb, W, 1, min_peak, n_cols, carry.data_ptr(), track.data_ptr(), st)
+    node.process_device_ctracked(xd.data_ptr(), nb * W, yd.data_ptr(), track.data_ptr(), n_cols, 0, st)
+    y, pk, mp = yd.cpu().numpy(), picks.cpu().numpy(), maps.cpu().numpy()
+    published, last = [], {}  # last: column -> the angle it was last published with
+    for b in range(nb):
+        p0 = int(pk[b, 0])
+        if not 0 <= p0 < A or mp[b, p0] < min_peak:
+            continue
+        rest = [int(d) for d in pk[b, 1:] if 0 <= d < A]
+        published.append((b, float(doa.angles[p0]), tuple(float(doa.angles[d]) for d in rest)))
+        for c, d in enumerate([p0] + rest[:n_cols - 1]):
+            last[c] = float(doa.angles[d])
+    if 0 in last:
+        node.set_theta(last[0])
+    for c in sorted(c for c in last if c > 0):
+        node.set_interference(c, last[c])
+    return y, published

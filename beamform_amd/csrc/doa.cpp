@@ -424,6 +424,59 @@ int bf_track_from_peaks_device(const int32_t *peak_dev, const double *map_dev, i
     return BF_OK;
 }
 
+// ---- multi-source picks and the column track they publish (no handle) ------------------------------------------------------------------
+static_assert(BF_DOA_MAX_PICKS == kPickMax && BF_DOA_MAX_PICKS == BF_MAX_INTERF + 1, "a look direction and every interferer");
+static_assert(BF_DOA_MAX_ANGLES == 64 * kPickSlots, "doa_pick_kernel keeps a whole row in one wavefront's registers");
+
+int bf_doa_pick_device(const double *map_dev, const double *angles_dev, int n_angles, int n_streams, size_t n_blocks, int k,
+                       double min_sep_deg, double rel_floor, int32_t *picks_dev, void *hip_stream) {
+    if (n_angles < 1 || n_angles > BF_DOA_MAX_ANGLES || n_streams < 1)
+        return fail(nullptr, BF_EINVAL, "bf_doa_pick_device: n_angles must be in 1 .. BF_DOA_MAX_ANGLES and n_streams >= 1");
+    if (k < 1 || k > BF_DOA_MAX_PICKS) return fail(nullptr, BF_EINVAL, "bf_doa_pick_device: k must be in 1 .. BF_DOA_MAX_PICKS");
+    if (!std::isfinite(min_sep_deg) || min_sep_deg < 0 || !std::isfinite(rel_floor))
+        return fail(nullptr, BF_EINVAL, "bf_doa_pick_device: min_sep_deg must be finite and >= 0, rel_floor finite");
+    if (!map_dev || !angles_dev || !picks_dev) return fail(nullptr, BF_EINVAL, "bf_doa_pick_device: map, angles or picks is NULL");
+    if (n_blocks == 0) return BF_OK;
+    DoaPickArgs a;
+    a.map = map_dev;
+    a.angles = angles_dev;
+    a.picks = picks_dev;
+    a.min_sep = min_sep_deg;
+    a.rel_floor = rel_floor;
+    a.n_rows = (long)n_streams * (long)n_blocks;
+    a.n_angles = n_angles;
+    a.k = k;
+    DOA_HIP(nullptr, launch_doa_pick(a, (hipStream_t)hip_stream));
+    return BF_OK;
+}
+
+int bf_ctrack_from_picks_device(const int32_t *picks_dev, const double *map_dev, int n_angles, int k, int n_streams, size_t n_blocks,
+                                int frames_per_block, int latency_blocks, double min_peak, int n_cols, int32_t *carry_dev,
+                                int32_t *track_dev, void *hip_stream) {
+    if (n_angles < 1 || n_streams < 1 || frames_per_block < 1 || latency_blocks < 0)
+        return fail(nullptr, BF_EINVAL, "bf_ctrack_from_picks_device: n_angles, n_streams, frames_per_block >= 1 and latency_blocks >= 0");
+    if (k < 1 || k > BF_DOA_MAX_PICKS) return fail(nullptr, BF_EINVAL, "bf_ctrack_from_picks_device: k must be in 1 .. BF_DOA_MAX_PICKS");
+    if (n_cols < 1 || n_cols > BF_MAX_INTERF + 1)
+        return fail(nullptr, BF_EINVAL, "bf_ctrack_from_picks_device: n_cols must be in 1 .. BF_MAX_INTERF + 1");
+    if (!picks_dev || !carry_dev || !track_dev) return fail(nullptr, BF_EINVAL, "bf_ctrack_from_picks_device: picks, carry or track is NULL");
+    if (!map_dev && min_peak > 0) return fail(nullptr, BF_EINVAL, "bf_ctrack_from_picks_device: min_peak > 0 needs the map");
+    if (n_blocks == 0) return BF_OK;  // carry stays: what block 0 of the next call gets
+    CtrackFromPicksArgs a;
+    a.picks = picks_dev;
+    a.map = map_dev;
+    a.carry = carry_dev;
+    a.track = track_dev;
+    a.min_peak = min_peak;
+    a.n_blocks = (long)n_blocks;
+    a.n_angles = n_angles;
+    a.k = k;
+    a.n_cols = n_cols;
+    a.frames_per_block = frames_per_block;
+    a.latency = latency_blocks;
+    DOA_HIP(nullptr, launch_ctrack_from_picks(a, n_streams, (hipStream_t)hip_stream));
+    return BF_OK;
+}
+
 int bf_doa_reset(bf_doa *d) {
     if (!d) return fail(nullptr, BF_EINVAL, "bf_doa_reset: handle is NULL");
     DOA_HIP(d, hipSetDevice(d->device));

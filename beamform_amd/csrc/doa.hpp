@@ -113,12 +113,37 @@ struct TrackFromPeaksArgs {
     int n_angles, frames_per_block, latency;
 };
 
+// bf_doa_pick_device: the k strongest separated peaks of every map row (the rule: doa_pick.hpp and include/bfcore.h)
+constexpr int kPickSlots = 16;  // angles per lane: lane l keeps angles l, l + 64, ... (64 x 16 = BF_DOA_MAX_ANGLES)
+constexpr int kPickMax = 16;    // BF_DOA_MAX_PICKS, and the most columns of a column track (BF_MAX_INTERF + 1)
+struct DoaPickArgs {
+    const double *map;         // [row][n_angles], row = stream x block
+    const double *angles;      // [n_angles] degrees
+    int32_t *picks;            // [row][k], strongest first, -1 where nothing was picked
+    double min_sep, rel_floor;
+    long n_rows;
+    int n_angles, k;
+};
+
+// bf_ctrack_from_picks_device: picks (and maps) of the blocks -> the column track of their frames
+struct CtrackFromPicksArgs {
+    const int32_t *picks;      // [stream][n_blocks][k]
+    const double *map;         // [stream][n_blocks][n_angles]; null: every block with a valid first pick publishes
+    int32_t *carry;            // [stream][n_cols]: in, the indices in force in front of block 0; out, those a block n_blocks would get
+    int32_t *track;            // [stream][n_blocks * frames_per_block][n_cols]
+    double min_peak;
+    long n_blocks;
+    int n_angles, k, n_cols, frames_per_block, latency;
+};
+
 // per hop of x (hops -1 .. n_frames-1, hop -1 = hist) the microphones with a nonzero sample: layout as the stft kernel reads it
 hipError_t launch_doa_hop_flags(const float *x, const float *hist, unsigned *flags, long n_frames, long mic_stride, long stream_stride_x,
                                 int n_streams, int n_mics, int hop, int layout, hipStream_t s);
 hipError_t launch_doa_map(const DoaMapArgs &a, hipStream_t s);
 hipError_t launch_doa_reduce(const DoaReduceArgs &a, hipStream_t s);
 hipError_t launch_track_from_peaks(const TrackFromPeaksArgs &a, int n_streams, hipStream_t s);
+hipError_t launch_doa_pick(const DoaPickArgs &a, hipStream_t s);
+hipError_t launch_ctrack_from_picks(const CtrackFromPicksArgs &a, int n_streams, hipStream_t s);
 
 // ---- Capon map (doa_kernels.hip) -----------------------------------------------------------------------------------------------------
 struct CaponArgs {

@@ -24,9 +24,13 @@
 //                         one partial sum per (segment, stream, block, angle).  Up to 8 microphones everything stays in registers
 //                         (doa_capon_kernel<MP>); above, the triangle lives in a work space in memory (doa_capon_ws_kernel).
 //   doa_reduce_kernel     as above with one "frame" per block: segments in ascending order, the scale 1 / |K|, the argmax
+//
+// Behind the maps, without a handle: doa_pick_kernel (bf_doa_pick_device: the k strongest separated peaks of every row) and the two
+// track builders, track_from_peaks_kernel and ctrack_from_picks_kernel (one look angle, or one angle per constraint column, per frame).
 #include <climits>
 
 #include "doa.hpp"
+#include "doa_pick.hpp"
 #include "launch_trace.hpp"
 
 namespace bf {
@@ -291,6 +295,142 @@ __global__ __launch_bounds__(64) void track_from_peaks_kernel(TrackFromPeaksArgs
         cur = __shfl(v, 63, 64);  // lanes past klast publish nothing: V(klast) at the end
     }
     if (lane == 0) a.carry[s] = cur;
+}
+
+// One wavefront per map row (a stream's block).  Lane l keeps the values and the angles l, l + 64, ... in registers (kPickSlots of each)
+// and one bit per slot: "still free".  A pick: the lane's best free value (ascending slots, so the lane's lowest index wins its ties),
+// a butterfly over (value, index) that prefers the lower index on equal values, the winner's angle through one shuffle, then every
+// lane takes its angles within min_sep of it out of the running (doa_pick.hpp).  Lane j remembers pick j: one row of stores at the end.
+// No LDS, no atomics; rows do not see each other, so the bytes cannot depend on the launch.  A NaN never compares as larger, so it can
+// only be picked where nothing else is free: the loop still ends after k rounds and writes indices of the row or -1.
+__global__ __launch_bounds__(64) void doa_pick_kernel(DoaPickArgs a) {
+    const int lane = threadIdx.x, D = a.n_angles, K = a.k;
+    for (long r = blockIdx.x; r < a.n_rows; r += gridDim.x) {
+        const double *row = a.map + r * D;
+        double v[kPickSlots], ang[kPickSlots];
+        unsigned free_mask = 0u;
+        double top = -INFINITY;  // the row's maximum
+#pragma unroll
+        for (int j = 0; j < kPickSlots; ++j) {
+            const int i = lane + 64 * j;
+            const bool in = i < D;
+            v[j] = in ? row[i] : 0.0;
+            ang[j] = in ? a.angles[i] : 0.0;
+            if (in) {
+                free_mask |= 1u << j;
+                if (v[j] > top) top = v[j];
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double t = __shfl_xor(top, o, 64);
+            if (t > top) top = t;
+        }
+        const double floor_v = a.rel_floor * top;
+        int mine = -1;
+        for (int n = 0; n < K; ++n) {
+            double bv = 0.0, ba = 0.0;
+            int bi = INT_MAX;  // nothing free in this lane
+#pragma unroll
+            for (int j = 0; j < kPickSlots; ++j)
+                if (((free_mask >> j) & 1u) && (bi == INT_MAX || v[j] > bv)) {
+                    bv = v[j];
+                    ba = ang[j];
+                    bi = lane + 64 * j;
+                }
+            double wv = bv;
+            int wi = bi;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double ov = __shfl_xor(wv, o, 64);
+                const int oi = __shfl_xor(wi, o, 64);
+                if (oi != INT_MAX && (wi == INT_MAX || ov > wv || (ov == wv && oi < wi))) {
+                    wv = ov;
+                    wi = oi;
+                }
+            }
+            // every lane follows lane 0 (without a NaN all lanes hold the same winner anyway)
+            const int d = __shfl(wi, 0, 64);
+            const double dv = __shfl(wv, 0, 64);
+            if (d == INT_MAX || dv < floor_v) break;
+            const double da = __shfl(ba, d & 63, 64);  // the owner's best is the winner
+            if (lane == n) mine = d;
+#pragma unroll
+            for (int j = 0; j < kPickSlots; ++j)
+                if (((free_mask >> j) & 1u) && (lane + 64 * j == d || !pick_stays_free(ang[j], da, a.min_sep))) free_mask &= ~(1u << j);
+        }
+        if (lane < K) a.picks[r * K + lane] = mine;
+    }
+}
+
+// track_from_peaks_kernel with a column dimension.  One wavefront per stream walks the blocks, 64 at a time; lane l of a round holds
+// block k = k0 + l.  A block publishes when its first pick is an index of the map whose value is not below min_peak; a publishing block
+// updates column c < min(n_cols, k) when pick c is an index of the map.  V_c(k) = column c's latest update by a block <= k, the carry
+// where there is none: per column a ballot of the updating lanes, the latest one at or below l through one shuffle.  The round's
+// [block][column] values go through LDS so that the frames of blocks k0 + latency ... leave as [frame][column] rows, consecutive lanes
+// on consecutive int32s.  Lane c keeps V_c(k0 - 1) between the rounds.  A pick or a carry is copied, never used as an index, but for
+// the look-up of a first pick that has been checked against the map.
+__global__ __launch_bounds__(64) void ctrack_from_picks_kernel(CtrackFromPicksArgs a) {
+    __shared__ int vs[64 * kPickMax];  // [block of the round][column]
+    const int lane = threadIdx.x, W = a.frames_per_block, L = a.latency, C = a.n_cols, K = a.k, A = a.n_angles;
+    const long s = blockIdx.x, nb = a.n_blocks, WC = (long)W * C;
+    const int *picks = a.picks + s * nb * K;
+    const double *map = a.map ? a.map + s * nb * A : nullptr;
+    int *trk = a.track + s * nb * WC;
+    int *carry = a.carry + s * C;
+    int cur = lane < C ? carry[lane] : -1;  // lane c: V_c(k0 - 1)
+    // blocks 0 .. latency-1: no block of this call is old enough
+    const long n_head = (L < nb ? (long)L : nb) * WC;
+    for (long i0 = 0; i0 < n_head; i0 += 64) {  // every lane takes part in the shuffle, also in a short last round
+        const long i = i0 + lane;
+        const int c_in = __shfl(cur, (int)(i % C), 64);
+        if (i < n_head) trk[i] = c_in;
+    }
+    const long klast = nb - L < nb - 1 ? nb - L : nb - 1;  // V(klast) is what a block n_blocks would get
+    // element i of a round's output and its successor i + 64, without a division per element (WC is a multiple of C)
+    const int q64 = (int)(64 / WC), r64 = (int)(64 % WC), c64 = 64 % C;
+    const int bl0 = (int)(lane / WC), c0 = lane % C;
+    const long rem0 = lane - bl0 * WC;
+    for (long k0 = 0; k0 <= klast; k0 += 64) {
+        const long k = k0 + lane;
+        const bool live = k <= klast;
+        bool pub = false;
+        if (live) {
+            const int p0 = picks[k * K];
+            if (p0 >= 0 && p0 < A) pub = map == nullptr || !(map[k * A + p0] < a.min_peak);
+        }
+        for (int c = 0; c < C; ++c) {
+            int p = -1;
+            if (pub && c < K) p = picks[k * K + c];
+            const bool upd = p >= 0 && p < A;
+            const unsigned long long m = __ballot(upd);
+            const unsigned long long below = m & (lane == 63 ? ~0ull : ((2ull << lane) - 1));
+            const int src = below ? 63 - __clzll((long long)below) : 0;
+            const int got = __shfl(p, src, 64);
+            const int before = __shfl(cur, c, 64);
+            const int v = below ? got : before;
+            vs[lane * C + c] = v;
+            const int last = __shfl(v, 63, 64);  // lanes past klast update nothing: V_c(klast) at the end
+            if (lane == c) cur = last;
+        }
+        __syncthreads();
+        int bl = bl0, c = c0;
+        long rem = rem0;
+        for (long i = lane; i < 64 * WC; i += 64) {  // the frames of blocks k0 + latency ..., [frame][column]: i = bl * WC + rem, c = i mod C
+            const long kk = k0 + bl;
+            if (kk <= klast && kk + L < nb) trk[(kk + L) * WC + rem] = vs[bl * C + c];
+            bl += q64;
+            rem += r64;
+            if (rem >= WC) {
+                rem -= WC;
+                ++bl;
+            }
+            c += c64;
+            if (c >= C) c -= C;
+        }
+        __syncthreads();
+    }
+    if (lane < C) carry[lane] = cur;
 }
 
 // ---- Capon --------------------------------------------------------------------------------------------------------------------------
@@ -568,6 +708,19 @@ hipError_t launch_doa_reduce(const DoaReduceArgs &a, hipStream_t s) {
 
 hipError_t launch_track_from_peaks(const TrackFromPeaksArgs &a, int n_streams, hipStream_t s) {
     BF_LAUNCH(track_from_peaks_kernel, dim3((unsigned)n_streams), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_doa_pick(const DoaPickArgs &a, hipStream_t s) {
+    if (a.n_rows < 1 || a.n_angles < 1 || a.n_angles > 64 * kPickSlots || a.k < 1 || a.k > kPickMax) return hipErrorInvalidValue;
+    const long cap = 1L << 20;  // a wavefront walks rows r, r + grid, ... beyond this many
+    BF_LAUNCH(doa_pick_kernel, dim3((unsigned)(a.n_rows < cap ? a.n_rows : cap)), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_ctrack_from_picks(const CtrackFromPicksArgs &a, int n_streams, hipStream_t s) {
+    if (a.n_cols < 1 || a.n_cols > kPickMax || a.k < 1 || a.k > kPickMax) return hipErrorInvalidValue;
+    BF_LAUNCH(ctrack_from_picks_kernel, dim3((unsigned)n_streams), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

@@ -535,6 +535,53 @@ int bf_ctrack_set_angles(bf_handle *h, const double *angles_deg, int n_angles);
 int bf_process_batch_device_ctracked(bf_handle *h, const float *x_dev, size_t n_frames, float *y_dev, void *spectrum_dev,
                                      const int32_t *track_dev, int n_cols, void *hip_stream);
 
+/* ---- multi-source picks and their column track, on the device ------------------------------------------------------------------------
+ * The device half of controllers.pick_sources / DoaSources / sources_track: with these two a caller closes the multi-source loop in
+ * four enqueues on one stream and no host synchronisation -- bf_doa_process_device (the Capon map), bf_doa_pick_device,
+ * bf_ctrack_from_picks_device, bf_process_batch_device_ctracked (controllers.follow_sources_device, examples/follow_sources_node.cpp).
+ * Neither takes a handle; each is one small launch on hip_stream. */
+#define BF_DOA_MAX_PICKS 16   /* = BF_MAX_INTERF + 1: a look direction and every interferer */
+/* The k strongest separated peaks of every map row.  map_dev: [n_streams][n_blocks][n_angles] as bf_doa_process_device writes it;
+ * angles_dev: [n_angles] doubles ON THE DEVICE, the candidate grid in degrees (any order, any range); picks_dev:
+ * [n_streams][n_blocks][k] int32, strongest first, unused places -1.  Per row:
+ *   1. m = the row's maximum, floor = rel_floor * m; every angle is free.
+ *   2. For j = 0 .. k-1: d = the free index with the largest value, the lowest index on ties.  Stop if nothing is free or
+ *      row[d] < floor.  Otherwise picks[j] = d, d is no longer free, and every free i with sep(angles[i], angles[d]) < min_sep_deg
+ *      is no longer free.
+ *   3. sep(a, b):  t = (a - b) + 180.0;  r = fmod(t, 360.0);  if r < 0 then r += 360.0;  the result is |r - 180.0| -- every step in
+ *      double and in exactly this order.  Each step is an exact or a correctly rounded IEEE operation, so the device, the host
+ *      (beamform_amd/csrc/doa_pick.hpp) and numpy's % agree bit for bit.
+ * For rows without NaN the picks are exactly those of controllers.pick_sources (a value of -inf, which its masking cannot tell from
+ * a suppressed angle, is outside this claim too; maps are in [0, 1]).  A row holding a NaN is outside the contract: the kernel still
+ * terminates and writes nothing but -1 or an index in 0 .. n_angles-1.  Rows are independent (one wavefront each, registers only):
+ * the bytes do not depend on the launch.
+ * BF_EINVAL, checked before any device work: n_angles outside 1 .. BF_DOA_MAX_ANGLES, n_streams < 1, k outside 1 .. BF_DOA_MAX_PICKS,
+ * a non-finite or negative min_sep_deg, a non-finite rel_floor, a NULL pointer.  n_blocks = 0 is BF_OK and launches nothing. */
+int bf_doa_pick_device(const double *map_dev, const double *angles_dev, int n_angles, int n_streams, size_t n_blocks, int k,
+                       double min_sep_deg, double rel_floor, int32_t *picks_dev, void *hip_stream);
+/* From picks to a column track: controllers.sources_track with a DoaSources controller, stated per column.
+ * picks_dev: [n_streams][n_blocks][k]; map_dev: [n_streams][n_blocks][n_angles], may be NULL when min_peak <= 0; carry_dev:
+ * [n_streams][n_cols] int32, in and out; track_dev: [n_streams][n_blocks * frames_per_block][n_cols], the layout
+ * bf_process_batch_device_ctracked reads.
+ *   Publishing: block b publishes when p0 = picks[s][b][0] is in 0 .. n_angles-1 and the map is NULL or map[s][b][p0] is not below
+ *   min_peak (a NaN publishes, as controllers.DoaSources and bf_track_from_peaks_device have it).
+ *   Column updates: a publishing block updates column c, 0 <= c < min(n_cols, k), when picks[s][b][c] is in 0 .. n_angles-1.  A column
+ *   the publication does not mention keeps its value, columns >= k are never updated, picks beyond n_cols are dropped.
+ *   Frames: every frame of block b gets, per column, the value of the latest update of that column by a block b' <= b - latency_blocks;
+ *   if there is none, carry[s][c] as it was on entry.
+ *   Carry: on exit carry[s][c] is what a block n_blocks would get, so that consecutive calls continue one stream -- exactly for
+ *   latency_blocks <= 1 (carry is one index per column: a longer latency forgets what the last latency_blocks - 1 blocks of the
+ *   previous call published).  Start with -1 everywhere: "the handle's own column".
+ * A pick outside the map neither publishes nor updates and is never read through; a value read from carry is copied as it stands and
+ * never used as an index.  The track holds the picks themselves: indices into the grid the picker was given, which is the grid to
+ * install with bf_ctrack_set_angles.
+ * BF_EINVAL, checked before any device work: n_angles < 1, k outside 1 .. BF_DOA_MAX_PICKS, n_streams < 1, frames_per_block < 1,
+ * latency_blocks < 0, n_cols outside 1 .. BF_MAX_INTERF + 1, NULL picks / carry / track, NULL map with min_peak > 0.  n_blocks = 0 is
+ * BF_OK (carry stays). */
+int bf_ctrack_from_picks_device(const int32_t *picks_dev, const double *map_dev, int n_angles, int k, int n_streams, size_t n_blocks,
+                                int frames_per_block, int latency_blocks, double min_peak, int n_cols, int32_t *carry_dev,
+                                int32_t *track_dev, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
