@@ -64,11 +64,13 @@ class BfConfig(C.Structure):
         ("gsc_use_vad", C.c_int), ("gsc_vad_threshold", C.c_double), ("gsc_mu0", C.c_double), ("gsc_mu_max", C.c_double),
         ("gsc_filter_size", C.c_int),
         ("gss_out_sources", C.c_int),
+        ("gss_postfilter", C.c_int),
     ]
 
 
 #: defaults of parameters added after the first golden fixtures were written (launch/gsc.launch:6-11)
-_LATER_KEYS = dict(gsc_use_vad=0, gsc_vad_threshold=0.1, gsc_mu0=0.0001, gsc_mu_max=0.1, gsc_filter_size=128, gss_out_sources=0)
+_LATER_KEYS = dict(gsc_use_vad=0, gsc_vad_threshold=0.1, gsc_mu0=0.0001, gsc_mu_max=0.1, gsc_filter_size=128, gss_out_sources=0,
+                   gss_postfilter=0)
 
 
 class BfError(RuntimeError):
@@ -410,8 +412,9 @@ def resampler_default_table():
 
 def config_from_params(p: dict, device: int = 0, n_streams: int = 1, layout: int = BF_PLANAR,
                        das_impl: int = BF_DAS_F64, n_dirs: int = 1, precision: int = BF_PRECISION_REFERENCE,
-                       gss_out_sources: int = None) -> BfConfig:
-    """bf_config from a beamform_amd.params dict (launch defaults first, then overrides).  gss_out_sources: the dict's value unless given."""
+                       gss_out_sources: int = None, gss_postfilter: int = None) -> BfConfig:
+    """bf_config from a beamform_amd.params dict (launch defaults first, then overrides).  gss_out_sources / gss_postfilter: the dict's
+    value unless given."""
     L = load()
     c = BfConfig()
     rc = L.bf_config_init(C.byref(c), ALGO_ID[p["algo"]])
@@ -430,10 +433,12 @@ def config_from_params(p: dict, device: int = 0, n_streams: int = 1, layout: int
               "mag_mult", "mag_threshold", "min_mag", "smooth_size", "mcra_alphaS", "mcra_alphaD", "mcra_alphaD2",
               "mcra_delta", "mcra_L", "mpf_alphaS", "mpf_eta", "mpf_rev_gamma", "mpf_rev_delta", "noise_floor",
               "out_only_noise", "out_only_mcra", "gsc_use_vad", "gsc_vad_threshold", "gsc_mu0", "gsc_mu_max",
-              "gsc_filter_size", "gss_out_sources"):
+              "gsc_filter_size", "gss_out_sources", "gss_postfilter"):
         setattr(c, k, p[k] if k in p else _LATER_KEYS[k])  # fixtures written before a key existed
     if gss_out_sources is not None:
         c.gss_out_sources = gss_out_sources
+    if gss_postfilter is not None:
+        c.gss_postfilter = gss_postfilter
     c.device, c.n_streams, c.layout, c.das_impl, c.n_dirs = device, n_streams, layout, das_impl, n_dirs
     c.precision = precision
     return c
@@ -457,11 +462,14 @@ class Beamformer:
     """One beamformer node behind the C ABI (das|mvdr|lcmv|gss|phase|phasempf|mcra|gsc)."""
 
     def __init__(self, params: dict, device: int = 0, n_streams: int = 1, layout: int = BF_PLANAR,
-                 das_impl: int = BF_DAS_F64, n_dirs: int = 1, precision: int = BF_PRECISION_REFERENCE, gss_out_sources: int = None):
+                 das_impl: int = BF_DAS_F64, n_dirs: int = 1, precision: int = BF_PRECISION_REFERENCE, gss_out_sources: int = None,
+                 gss_postfilter: int = None):
         """gss_out_sources = R > 1 (gss only): every beam yields its R separated sources, not only the first (bf_config.gss_out_sources);
-        the outputs gain an axis of length R, innermost among the stream axes."""
+        the outputs gain an axis of length R, innermost among the stream axes.  gss_postfilter = 1 (gss only): every separated source
+        goes through the multi-source post-filter (bf_config.gss_postfilter: noise, leak of the other sources and reverberation come off
+        its magnitude)."""
         self._L = load()
-        self.cfg = config_from_params(params, device, n_streams, layout, das_impl, n_dirs, precision, gss_out_sources)
+        self.cfg = config_from_params(params, device, n_streams, layout, das_impl, n_dirs, precision, gss_out_sources, gss_postfilter)
         self.n_dirs = max(1, n_dirs)
         self.n_rows = max(1, self.cfg.gss_out_sources)
         self.n_out = n_streams * self.n_dirs * self.n_rows  # output streams: [stream][dir][row]

@@ -236,6 +236,9 @@ int bf_create(const bf_config *cfg, bf_handle **out) {
     if (cfg->gss_out_sources < 0 || cfg->gss_out_sources > BF_MAX_INTERF + 1) return fail(nullptr, BF_EINVAL, "gss_out_sources out of range");
     if (cfg->gss_out_sources > 1 && cfg->algo != BF_GSS)
         return fail(nullptr, BF_EINVAL, "gss_out_sources: only gss separates sources (the other nodes have one output per beam)");
+    if (cfg->gss_postfilter != 0 && cfg->gss_postfilter != 1) return fail(nullptr, BF_EINVAL, "gss_postfilter must be 0 or 1");
+    if (cfg->gss_postfilter != 0 && cfg->algo != BF_GSS)
+        return fail(nullptr, BF_EINVAL, "gss_postfilter: only gss has separated sources to filter");
     if (cfg->layout != BF_PLANAR && cfg->layout != BF_INTERLEAVED) return fail(nullptr, BF_EINVAL, "layout");
     if (cfg->precision != BF_PRECISION_REFERENCE && cfg->precision != BF_PRECISION_MIXED) return fail(nullptr, BF_EINVAL, "precision");
     if (cfg->das_impl != BF_DAS_FUSED_F32 && cfg->das_impl != BF_DAS_F64) return fail(nullptr, BF_EINVAL, "das_impl");
@@ -817,8 +820,11 @@ static uint64_t state_cfg_hash(const bf_handle *h) {
 }
 
 // header word `das_impl`: the das arithmetic, and above it gss's rows per beam minus one (the blob carries that many overlap-add tails per
-// beam: a handle of another row count must refuse it; one row leaves the word, and so the blob, as it always was)
-static uint32_t state_impl_word(const bf_handle *h) { return (uint32_t)h->cfg.das_impl | ((uint32_t)(h->n_rows - 1) << 16); }
+// beam: a handle of another row count must refuse it; one row leaves the word, and so the blob, as it always was), and in bit 24 gss's
+// post-filter (the blob then carries the filter's state per row; off leaves the word as it was)
+static uint32_t state_impl_word(const bf_handle *h) {
+    return (uint32_t)h->cfg.das_impl | ((uint32_t)(h->n_rows - 1) << 16) | ((uint32_t)(h->cfg.gss_postfilter != 0) << 24);
+}
 
 size_t bf_state_size(const bf_handle *h) {
     if (!h) return 0;

@@ -19,6 +19,7 @@ namespace bf {
 // carries a steering track (bf_process_batch_device_tracked: a table index per (stream, frame); das / phase / phasempf, one look direction).
 // ctrack_cols (last once more: a shape written without it means 0 = none): the batch carries a column track
 // (bf_process_batch_device_ctracked: a table index per (stream, frame, constraint column); mvdr / lcmv, one look direction).
+// gss_postfilter (last yet again: a shape written without it means 0 = off): bf_config.gss_postfilter, ignored by every node but gss.
 struct ChainShape {
     int algo, n_fft, layout, n_mics, n_streams, n_dirs, kp1, past_windows, precision;
     bool dump;
@@ -32,6 +33,7 @@ struct ChainShape {
     int gss_rows;
     bool track;
     int ctrack_cols;
+    int gss_postfilter;
 };
 
 // The kernels of each stage, template arguments behind them as ChainPlan holds them:
@@ -40,6 +42,7 @@ struct ChainShape {
 //   bins   pointwise_bins_kernel<mp, algo>, mpf_mask_kernel<mp>, mcra_node_kernel, gsc_align_kernel, mvdr_fast_kernel<mp, km, !z48>,
 //          cov2d_kernel<km, wps, !z48>, mvdr_lcmv_kernel<mp, km>, gss_kernel<mp, km>, gss_lane_kernel<mp, km>
 //   rec    phasempf's pass over the frames: mpf_recursion_kernel, or mpf_rec_istft_kernel, which runs the backward transform too
+//   post   gss_postfilter_kernel<RP> behind gss's per-bin kernel (ChainPlan::postfilter), in front of expand_spectrum_kernel
 //   istft  istft_w64_kernel<band_rows>, istft32_kernel, istft_small_kernel, istft_split_kernel, istft_generic_kernel + ola_generic_kernel
 //          with ChainPlan::track their twins that resolve the steering table per frame: stft_bins_w64_track_kernel + fused_tail_track_kernel,
 //          pointwise_track_kernel<mp, algo>, mpf_mask_track_kernel<mp>; with ChainPlan::ctrack mvdr_fast_track_kernel<mp, km, !z48> and
@@ -75,6 +78,10 @@ struct ChainPlan {
     // the per-bin kernel is the column-track twin of mvdr_fast_kernel / mvdr_lcmv_kernel: the constraint columns of a frame come from the
     // batch's track (BinsArgs::track with track_cols entries per frame); mvdr / lcmv with one look direction only
     bool ctrack;
+    // gss with bf_config.gss_postfilter: gss_postfilter_kernel<post_rp> runs in place over the rows of the per-bin stage (one lane owns
+    // all rows of its (beam, problem): no second row buffer, yh_bytes stays what it is); post_rp = the rows padded to 1 / 2 / 4 / 8 / 16
+    bool postfilter;
+    int post_rp;
     bool fused() const { return front >= ChainFront::kFusedW64; }
     bool rec_istft() const { return rec == ChainRec::kRecIstft; }
 };
@@ -98,6 +105,8 @@ inline ChainPlan chain_decide(const ChainShape &c) {
     p.algo = a; p.layout = c.layout; p.z48 = cov && mixed; p.rows = R;
     p.track = c.track && D == 1 && (pointwise || mpf);
     p.ctrack = c.ctrack_cols > 0 && D == 1 && cov;
+    p.postfilter = a == BF_GSS && c.gss_postfilter != 0;
+    p.post_rp = !p.postfilter ? 0 : R <= 1 ? 1 : R <= 2 ? 2 : R <= 4 ? 4 : R <= 8 ? 8 : 16;
     // nodes without a frame history, up to 8 microphones, one look direction: STFT and per-bin stage in one launch, spectra never leave the CU.
     // A tracked batch only at N = 1024: the fused fronts of the other sizes keep a thread's steering entries in registers across frames
     const bool fused = c.fused_bins != 0 && N <= 2048 && M <= 8 && D == 1 && (pointwise || mpf) && (!p.track || N == 1024);

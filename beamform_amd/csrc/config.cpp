@@ -109,6 +109,7 @@ int bf_config_init(bf_config *c, int algo) {
     c->das_impl = BF_DAS_F64;  // the reference's arithmetic (das.cpp:16-24); BF_DAS_FUSED_F32 is the opt-in
     c->precision = BF_PRECISION_REFERENCE;  // ... between the transforms too; BF_PRECISION_MIXED is the opt-in
     c->gss_out_sources = 0;  // gss emits this_yf(0) alone, as gss.cpp:120-121 does
+    c->gss_postfilter = 0;   // ... and without a post-filter
     return BF_OK;
 }
 
@@ -177,6 +178,7 @@ int bf_config_parse_yaml(bf_config *c, const char *text) {
         if (key == "rosjack_window_size") { c->hop = (int)d; continue; }
         if (key == "rosjack_sample_rate") { c->sample_rate = d; continue; }
         BF_KEY_I(gss_out_sources)  // build-specific: no launch file sets it
+        BF_KEY_I(gss_postfilter)
 #undef BF_KEY_D
 #undef BF_KEY_I
     }

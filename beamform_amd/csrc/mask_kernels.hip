@@ -425,6 +425,98 @@ __global__ __launch_bounds__(64) void mpf_recursion_kernel(BinsArgs a, double *a
     }
 }
 
+// gss's multi-source post-filter (bf_config.gss_postfilter, Valin et al. 2007): behind the gss per-bin kernel every live row r < n_live
+// = min(sources, rows) of a beam is replaced by the MPF block's output with soi = the row and int2 = the other live rows' |.|^2, summed in
+// ascending row order (a.cfg arrives with out_amp = 1: gss's backward path applies it).  One lane per (beam, problem) owns ALL rows of its
+// problem and works in place -- a row's result overwrites what the other rows' int2 needs, so a frame's rows are read into registers
+// before any is written -- serial over the frames, the state of every row in registers (RP = the rows padded to a power of two), the
+// rows of the next frames requested ahead as mpf_recursion_kernel does.  State: a.mpf = [beam * rows + r][kMpfVecs * kN + 8], the layout
+// phasempf keeps per stream; rows >= n_live are neither read nor written (exact zeros from the gss kernels) and their state stays put.
+template <int RP>
+__global__ __launch_bounds__(64) void gss_postfilter_kernel(BinsArgs a, int n_live) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= a.n_streams * kNQ) return;
+    const int s = idx / kNQ, q = idx % kNQ;
+    const int j = q_bin(q);
+    const int R = a.gss_rows;
+    const long row_stride = a.n_frames * kYhStride;  // between two rows of a beam
+    constexpr long kStateRow = kMpfVecs * kN + 8;
+    double *sv = a.mpf + (long)s * R * kStateRow;
+    f64x2 *rows = a.Yh + (long)s * R * row_stride + q;
+    MpfState st[RP];
+    int cL[RP];
+    bool firstL[RP];
+#pragma unroll
+    for (int r = 0; r < RP; ++r) {
+        st[r] = MpfState{0, 0, 0, 0, 0, 0, 0};
+        cL[r] = 0;
+        firstL[r] = true;
+        if (r < n_live) {
+            const double *v = sv + r * kStateRow;
+            st[r] = MpfState{v[0 * kN + j], v[1 * kN + j], v[2 * kN + j], v[3 * kN + j], v[4 * kN + j], v[5 * kN + j], v[6 * kN + j]};
+            cL[r] = (int)v[kMpfVecs * kN + 0];
+            firstL[r] = v[kMpfVecs * kN + 1] == 0.0;  // "first_L is over" flag: a zeroed state = cold start
+        }
+    }
+    // frames in flight: as many register sets as the row count leaves room for
+    constexpr int kAhead = RP <= 4 ? 4 : 1;
+    cd in_r[kAhead][RP];
+#pragma unroll
+    for (int k = 0; k < kAhead; ++k) {
+        const long tt = k < a.n_frames ? k : a.n_frames - 1;
+#pragma unroll
+        for (int r = 0; r < RP; ++r) in_r[k][r] = r < n_live ? ld(rows + r * row_stride + tt * kYhStride) : cd{0, 0};
+    }
+    for (long t0 = 0; t0 < a.n_frames; t0 += kAhead) {
+#pragma unroll
+      for (int k = 0; k < kAhead; ++k) {
+        const long t = t0 + k;
+        if (t >= a.n_frames) break;
+        cd y[RP];
+        double n2[RP];
+#pragma unroll
+        for (int r = 0; r < RP; ++r) {
+            y[r] = in_r[k][r];
+            n2[r] = j == 0 ? 0.0 : norm2(y[r]);  // int2[0] = 0; rows >= n_live hold zeros: adding them changes no bit
+        }
+        {
+            const long tn = t + kAhead < a.n_frames ? t + kAhead : a.n_frames - 1;
+#pragma unroll
+            for (int r = 0; r < RP; ++r)
+                if (r < n_live) in_r[k][r] = ld(rows + r * row_stride + tn * kYhStride);
+        }
+#pragma unroll
+        for (int r = 0; r < RP; ++r) {
+            if (r >= n_live) continue;
+            double int2 = 0.0;
+#pragma unroll
+            for (int r2 = 0; r2 < RP; ++r2)
+                if (r2 != r) int2 += n2[r2];
+            const bool reset = cL[r] > a.cfg.mcra_L;  // phasempf.cpp:161
+            if (reset) {
+                cL[r] = 1;
+                firstL[r] = false;
+            } else {
+                cL[r]++;
+            }
+            const cd o = mpf_step(st[r], a.cfg, j, y[r], int2, reset, firstL[r], cL[r]);
+            rows[r * row_stride + t * kYhStride] = f64x2{o.x, o.y};
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < RP; ++r) {
+        if (r >= n_live) continue;
+        double *v = sv + r * kStateRow;
+        v[0 * kN + j] = st[r].Sprev; v[1 * kN + j] = st[r].Stmp; v[2 * kN + j] = st[r].Smin; v[3 * kN + j] = st[r].lam;
+        v[4 * kN + j] = st[r].Z; v[5 * kN + j] = st[r].rev0; v[6 * kN + j] = st[r].rev1;
+        if (q == 0) {
+            v[kMpfVecs * kN + 0] = (double)cL[r];
+            v[kMpfVecs * kN + 1] = firstL[r] ? 0.0 : 1.0;
+        }
+    }
+}
+
 #if BF_NFFT == 1024
 // ---- phasempf with many streams: the recursion and the backward transform in one kernel ---------------------------------------------
 // With as many streams as CUs the recursion (one lane per (stream, problem), serial over the frames) and the backward transform (one
@@ -1449,6 +1541,27 @@ hipError_t launch_bins_end(const ChainPlan &p, const BinsArgs &a, hipStream_t s)
 #if BF_NFFT == 1024
     if (p.rec == ChainRec::kRecIstft) BF_LAUNCH(mpf_rec_istft_kernel, dim3((unsigned)a.n_streams), dim3(kRiThreads), 0, s, a, aux);
 #endif
+    const hipError_t e = hipGetLastError();
+    // (gss with its post-filter: the dump shows the filtered rows -- launch_gss_postfilter expands behind the filter)
+    return e == hipSuccess && p.expand && !p.postfilter ? launch_expand_spectrum(a.Yh, a.spectrum, (long)a.n_streams * p.rows * a.n_frames, s) : e;
+}
+
+// gss's post-filter over the rows the per-bin stage left in Yh (ChainPlan::postfilter), then the spectrum dump.  The filter leaves out_amp
+// to gss's backward path: the kernel's copy of the configuration has out_amp = 1
+hipError_t launch_gss_postfilter(const ChainPlan &p, const BinsArgs &a, hipStream_t s) {
+    if (!p.postfilter || a.gss_rows != p.rows || p.rows > p.post_rp || a.mpf == nullptr) return hipErrorInvalidValue;
+    BinsArgs b = a;
+    b.cfg.out_amp = 1.0;
+    const int n_live = a.kp1 < p.rows ? a.kp1 : p.rows;  // rows that exist in this batch: min(sources, rows)
+    const dim3 grid((unsigned)((a.n_streams * kNQ + 63) / 64));
+    switch (p.post_rp) {
+        case 1: BF_LAUNCH(gss_postfilter_kernel<1>, grid, dim3(64), 0, s, b, n_live); break;
+        case 2: BF_LAUNCH(gss_postfilter_kernel<2>, grid, dim3(64), 0, s, b, n_live); break;
+        case 4: BF_LAUNCH(gss_postfilter_kernel<4>, grid, dim3(64), 0, s, b, n_live); break;
+        case 8: BF_LAUNCH(gss_postfilter_kernel<8>, grid, dim3(64), 0, s, b, n_live); break;
+        case 16: BF_LAUNCH(gss_postfilter_kernel<16>, grid, dim3(64), 0, s, b, n_live); break;
+        default: return hipErrorInvalidValue;
+    }
     const hipError_t e = hipGetLastError();
     return e == hipSuccess && p.expand ? launch_expand_spectrum(a.Yh, a.spectrum, (long)a.n_streams * p.rows * a.n_frames, s) : e;
 }

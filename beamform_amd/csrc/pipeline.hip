@@ -118,7 +118,7 @@ class BinPipelineImpl : public Engine {
             ENGINE_HIP(d_gssW_.alloc(gss_bytes() / sizeof(f64x2)));
             ENGINE_HIP(hipMemset(d_gssW_.get(), 0, gss_bytes()));  // defined content until the first run applies W = C^H
         }
-        if (cfg_.algo == BF_PHASEMPF || cfg_.algo == BF_MCRA) ENGINE_HIP(d_mpf_.alloc(mpf_bytes() / sizeof(double)));
+        if (mpf_bytes()) ENGINE_HIP(d_mpf_.alloc(mpf_bytes() / sizeof(double)));  // phasempf, mcra, gss with its post-filter
         if (cfg_.algo == BF_PHASEMPF) ENGINE_HIP(d_smooth_.alloc(smooth_bytes() / sizeof(double)));
         if (time_node_) ENGINE_HIP(d_nlms_.alloc(nlms_bytes() / sizeof(float)));
         return BF_OK;
@@ -134,6 +134,8 @@ class BinPipelineImpl : public Engine {
         if (d_smooth_.get()) ENGINE_HIP(hipMemsetAsync(d_smooth_.get(), 0, smooth_bytes(), st)); // calloc past_samples (phasempf.cpp:510)
         if (d_nlms_.get()) ENGINE_HIP(hipMemsetAsync(d_nlms_.get(), 0, nlms_bytes(), st));       // calloc block_matrix/filter/last_outputs (gsc.cpp:278-285)
         gss_reset_mask_ = ~0ull;  // sep_matrix = weights^H (gss.cpp:90-93), done on the stream at next run
+        // (until then the matrices are dead; zeroed as init() leaves them, so that a reset handle's state blob is a new handle's)
+        if (d_gssW_.get()) ENGINE_HIP(hipMemsetAsync(d_gssW_.get(), 0, gss_bytes(), st));
         return BF_OK;
     }
 
@@ -230,6 +232,7 @@ class BinPipelineImpl : public Engine {
     // recursive per-beam state is sized by OUTPUT streams (input streams x look directions)
     size_t gss_bytes() const { return cfg_.algo == BF_GSS ? (size_t)So_ * N_ * kMaxCols * M_ * sizeof(f64x2) : 0; }
     size_t mpf_bytes() const {
+        if (post_filter_) return (size_t)So_ * R_ * (kMpfVecs * N_ + 8) * sizeof(double);  // gss's post-filter: phasempf's block per output row
         return (cfg_.algo == BF_PHASEMPF || cfg_.algo == BF_MCRA) ? (size_t)So_ * (kMpfVecs * N_ + 8) * sizeof(double) : 0;
     }
     size_t smooth_bytes() const { return cfg_.algo == BF_PHASEMPF ? (size_t)So_ * 64 * sizeof(double) : 0; }
@@ -261,6 +264,7 @@ class BinPipelineImpl : public Engine {
     const bool band_node_ = cov_node_ || cfg_.algo == BF_GSS;             // only the bins inside [freq_min, freq_max] are processed
     const bool time_node_ = cfg_.algo == BF_GSC;                          // the adaptive stage runs on samples: no single y_fft
     const bool single_ch_ = cfg_.algo == BF_MCRA;                         // only channel 0 is transformed (mcra.cpp:72-73)
+    const bool post_filter_ = cfg_.algo == BF_GSS && cfg_.gss_postfilter != 0;  // the multi-source post-filter runs behind the gss kernels
     const bool post_amp_ = band_node_;                                    // out_amp is applied behind the backward transform
     const bool yraw_target_ = cfg_.algo == BF_PHASEMPF || time_node_;     // the backward transform feeds the smoother / the NLMS stage through d_yraw_
     int skip_lo_, skip_hi_ = 0;        // StftArgs::skip_lo / skip_hi (init(); N_, 0 = store everything)
@@ -290,7 +294,7 @@ class BinPipelineImpl : public Engine {
     int tail_cur_ = 0;
     DeviceBuffer<char> d_zhist_;     // [stream][Phist][NP][N] elements of zsz_ bytes: packed spectra of the previous Phist frames
     DeviceBuffer<f64x2> d_gssW_;     // [stream][bin][KP1][M]
-    DeviceBuffer<double> d_mpf_;     // [stream][kMpfVecs*N + 8]
+    DeviceBuffer<double> d_mpf_;     // [stream][kMpfVecs*N + 8]; gss's post-filter: [stream][row][kMpfVecs*N + 8]
     DeviceBuffer<double> d_smooth_;  // [stream][64]
     DeviceBuffer<float> d_nlms_;     // gsc: [stream][(2(M-1)+1) * filter_size]
     unsigned long long gss_reset_mask_ = ~0ull;  // look directions whose demixing matrices restart at the next run
@@ -350,7 +354,7 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
                                                 cfg_.precision, spectrum != nullptr, F, n_cus_, cfg_.gsc_filter_size, cfg_.smooth_size,
                                                 band_yh_lo_, band_yh_hi_, (reinterpret_cast<size_t>(y) & 15) == 0, sw.fused_bins,
                                                 sw.stft_small, sw.stft_split, sw.mvdr_group, sw.gss_group, sw.gsc_serial, R_, snap.track != nullptr && snap.track_cols == 0,
-                                                snap.track != nullptr ? snap.track_cols : 0});
+                                                snap.track != nullptr ? snap.track_cols : 0, post_filter_ ? 1 : 0});
     float *const hist = d_hist2_[hist_cur_].get();
     const long FT = Phist_ + F;  // frames in the Z workspace per stream
     ENGINE_HIP(d_Z_.reserve(p.z_bytes));
@@ -423,6 +427,7 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
         ENGINE_HIP(ks_->stft(p, sa, n_cus_, stream));
     ENGINE_HIP(carry_last_hop(hist, x, F, H_, M_, S_, layout, mic_stride, (long)F * H_ * M_, stream));
     if (!p.fused()) ENGINE_HIP(ks_->bins(p, ba, n_cus_, stream));
+    if (p.postfilter) ENGINE_HIP(ks_->gss_postfilter(p, ba, stream));  // gss: the rows are filtered in place in front of the dump and the backward transform
     if (Phist_ > 0)  // keep the last Phist frames' spectra for the next call
         ENGINE_HIP(hipMemcpy2DAsync(d_zhist_.get(), (size_t)Phist_ * frame_elems * zsz_, (const char *)Z + (size_t)F * frame_elems * zsz_,
                                   (size_t)FT * frame_elems * zsz_, (size_t)Phist_ * frame_elems * zsz_, (size_t)S_,

@@ -83,7 +83,8 @@ struct BinsArgs {
     long steer_dir_stride;       // f64x2 elements between the steering tables of two look directions
     bf_config cfg;
     f64x2 *gssW;         // [stream][N][kp1][n_mics]
-    double *mpf;         // [stream][kMpfVecs*N + 8] (the mcra node uses vectors 0..3 and the two scalars)
+    double *mpf;         // [stream][kMpfVecs*N + 8] (the mcra node uses vectors 0..3 and the two scalars); gss with its post-filter:
+                         // [stream][gss_rows][kMpfVecs*N + 8], a block per output row
     unsigned long long gss_reset_mask;  // bit d: look direction d re-initialises W = C^H (gss.cpp:90-93) in this batch
     int z48;             // mvdr / lcmv with BF_PRECISION_MIXED: Z holds z48 elements; 0 (the default) = full f64x2 spectra
     // phasempf with many streams (N = 1024, default precision, no dump): the recursion kernel runs the backward transform too
@@ -178,6 +179,8 @@ hipError_t launch_gss(const ChainPlan &p, const BinsArgs &a, hipStream_t s);    
 hipError_t launch_gsc_align(const BinsArgs &a, hipStream_t s);                                  // gsc_gss_kernels.hip
 // what follows the per-bin kernel on the chained and on the fused route: phasempf's recursion over the frames, the spectrum dump.  mask_kernels.hip
 hipError_t launch_bins_end(const ChainPlan &p, const BinsArgs &a, hipStream_t s);
+// gss with bf_config.gss_postfilter: gss_postfilter_kernel in place over the rows of the per-bin stage, then the spectrum dump.  mask_kernels.hip
+hipError_t launch_gss_postfilter(const ChainPlan &p, const BinsArgs &a, hipStream_t s);
 hipError_t launch_expand_spectrum(const f64x2 *Yh, f64x2 *spectrum, long frames, hipStream_t s);  // stft_istft.hip
 hipError_t launch_istft(const ChainPlan &p, const IstftArgs &a, int n_cus, hipStream_t s);
 // gsc.cpp:120-181: the sample-serial float32 NLMS sidelobe canceller over the phase-aligned microphone signals.
@@ -199,6 +202,7 @@ struct KernelSet {
     hipError_t (*istft)(const ChainPlan &, const IstftArgs &, int, hipStream_t);
     hipError_t (*smooth)(const ChainPlan &, const float *, float *, double *, long, int, hipStream_t);
     hipError_t (*gsc_nlms)(const ChainPlan &, const float *, float *, float *, long, int, int, const bf_config &, hipStream_t);
+    hipError_t (*gss_postfilter)(const ChainPlan &, const BinsArgs &, hipStream_t);
 };
 const KernelSet *kernel_set_n128();
 const KernelSet *kernel_set_n256();

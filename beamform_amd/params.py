@@ -55,6 +55,7 @@ _BASE = dict(
     out_only_noise=0, out_only_mcra=0,
     gsc_use_vad=0, gsc_vad_threshold=0.1, gsc_mu0=0.0001, gsc_mu_max=0.1, gsc_filter_size=128,
     gss_out_sources=0,  # build-specific (bf_config.gss_out_sources): 0/1 = the reference's single output, R > 1 = every separated source
+    gss_postfilter=0,   # build-specific (bf_config.gss_postfilter): 1 = the multi-source post-filter over gss's separated sources
 )
 
 
@@ -64,6 +65,7 @@ def make_params(algo: str, n_mics: int = 8, **overrides) -> dict:
     `mics` defaults to the first `n_mics` entries of the aira16 layout
     (SURVEY.md 8d).  `interf` is the list of interferer angles (lcmv/gss).
     `gss_out_sources` = R > 1 makes gss emit its R separated sources per beam.
+    `gss_postfilter` = 1 runs the multi-source post-filter over them.
     """
     if algo not in ALGO_ID:
         raise ValueError(f"unknown algo {algo!r}")

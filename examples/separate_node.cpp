@@ -1,11 +1,13 @@
 // separate_node.cpp -- geometric source separation with every source written out: one WAV per separated source.
 //
-//   separate_node <beamform_config.yaml> <in.wav|in.f32> <out_prefix> [n_sources]
+//   separate_node <beamform_config.yaml> <in.wav|in.f32> <out_prefix> [n_sources] [postfilter]
 //
 // The reference's gss node computes all separated sources every frame and publishes the first (gss.cpp:120-121).  Here the
 // config's look direction (initial_angle) and its interferers (angle_interf<k>) are the sources; n_sources (default: the yaml's
 // gss_out_sources, else 1 + interferers) of them are written to <out_prefix>0.wav (the look direction), <out_prefix>1.wav
 // (angle_interf1), ... as rosjack's write_file option writes its one stream: mono PCM16 (rosjack.cpp:189-210, 404-409).
+// A trailing `postfilter` (or the yaml's gss_postfilter: 1) runs the multi-source post-filter over the separated sources before they are
+// written (bf_config.gss_postfilter: stationary noise, the leak of the other sources and reverberation come off each magnitude).
 // in.f32: planar float32 [n_mics][n_samples]; in.wav: a multichannel WAV file (its first n_mics channels, its sample rate).
 // The whole file is one batch (bf_process_batch); a trailing partial period is dropped, as JACK would never deliver it.
 #include <cstdio>
@@ -23,13 +25,17 @@ static bool ends_with(const char *s, const char *suf) {
 
 int main(int argc, char **argv) {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s <config.yaml> <in.wav|in.f32> <out_prefix> [n_sources]\n", argv[0]);
+        fprintf(stderr, "usage: %s <config.yaml> <in.wav|in.f32> <out_prefix> [n_sources] [postfilter]\n", argv[0]);
         return 2;
     }
     bf_config cfg;
     if (bf_config_init(&cfg, BF_GSS) != BF_OK || bf_config_load_yaml(&cfg, argv[1]) != BF_OK) {
         fprintf(stderr, "bad config %s\n", argv[1]);
         return 2;
+    }
+    if (argc > 4 && !strcmp(argv[argc - 1], "postfilter")) {
+        cfg.gss_postfilter = 1;
+        --argc;
     }
     if (argc > 4) cfg.gss_out_sources = atoi(argv[4]);
     if (cfg.gss_out_sources < 1) cfg.gss_out_sources = cfg.n_interf + 1;
@@ -69,6 +75,7 @@ int main(int argc, char **argv) {
             bf_wav_writer_write(w, &y[(size_t)r * len + k * (size_t)cfg.hop], (size_t)cfg.hop);
         bf_wav_writer_close(w);
     }
-    fprintf(stderr, "gss: %zu callbacks, %d mics, %d interferers, %d sources -> %s0..%d.wav\n", frames, M, cfg.n_interf, R, argv[3], R - 1);
+    fprintf(stderr, "gss: %zu callbacks, %d mics, %d interferers, %d sources%s -> %s0..%d.wav\n", frames, M, cfg.n_interf, R,
+            cfg.gss_postfilter ? ", post-filtered" : "", argv[3], R - 1);
     return 0;
 }

@@ -158,6 +158,27 @@ typedef struct bf_config {
                                       counts output streams as n_streams * n_dirs (y, spectrum_dev, bf_stream_rms, bf_process_hop,
                                       the state blob's tails), read n_streams * n_dirs * R.  Row 0 is the R = 1 node's output bit
                                       for bit; R = 1 runs the very kernels it always ran.  Above 1 with another algo: BF_EINVAL */
+    int gss_postfilter;            /* gss: the multi-source post-filter of Valin et al. 2007 over the separated sources (0 = off, the
+                                      default and the reference node; 1 = on; anything else, or non-zero with another algo:
+                                      BF_EINVAL).  With R = max(1, gss_out_sources) rows per beam and S_t = 1 + interferers sources
+                                      in force at frame t, every row r < min(S_t, R) is replaced, bin by bin, by the output of the
+                                      reference's MPF block (phasempf.cpp:140-191, 254-295: MCRA noise + leak of the other sources +
+                                      reverberation, taken off the magnitude) fed with
+                                        soi  = Y_r[t]                                  (the row as gss stores it with the filter off)
+                                        int2 = sum over r' != r, r' < min(S_t, R), of |Y_r'[t][j]|^2, in ascending r'
+                                      and soi2[0] = int2[0] = 0.  Every quirk of that block is kept as phasempf has it (0.75 soi2 at
+                                      bins 1 and N-1, Sf[0] = |soi[0]|, kq = 1 - rev_gamma / rev_delta, the alphaD2 / alphaD pair,
+                                      output bin 0 = 0, out_only_noise, out_only_mcra).  One difference: out_amp is NOT applied
+                                      inside the filter -- the magnitude is |soi| - Lambda, or noise_floor when that is negative --
+                                      and gss's backward path applies out_amp as on every row.  Rows r >= min(S_t, R) are not
+                                      touched in frame t: they stay exact zeros and their state does not advance.  Parameters: the
+                                      mcra_*, mpf_*, noise_floor, out_only_noise and out_only_mcra fields above (bf_config_init:
+                                      phasempf.launch's values).  State: every output row has its own seven vectors and its own
+                                      current_L / first_L pair (phasempf's per-stream layout); it carries across frames, batches and
+                                      bf_process_hop calls, is NOT restarted by bf_set_theta or bf_set_interference (those restart
+                                      sep_matrix; the noise estimate is about the room), is zeroed by bf_reset and travels in the
+                                      state blob, which a handle without the filter refuses (and the other way round).  The
+                                      spectrum dump shows the filtered rows; R = 1 filters row 0 with int2 = 0 */
 } bf_config;
 #define BF_MAX_DIRS 64
 
@@ -333,7 +354,7 @@ int bf_get_weights(bf_handle *h, double *w_host);
 /* Checkpoint of all per-stream state (ring hop, OLA tail, covariance history,
  * GSS demixing matrices, MCRA/MPF vectors, smoothing tail).  The reference has
  * no counterpart (state lives in process globals).  A blob is accepted only by a handle of the same shape, gss_out_sources
- * included (one overlap-add tail per output stream). */
+ * and gss_postfilter included (one overlap-add tail per output stream; with the post-filter its state per output row). */
 size_t bf_state_size(const bf_handle *h);
 int bf_get_state(bf_handle *h, void *blob_host, size_t size);
 int bf_set_state(bf_handle *h, const void *blob_host, size_t size);
