@@ -229,6 +229,50 @@ def test_yaml_reader_follows_handle_params():
         os.remove(path)
 
 
+#: every parameter key of the launch files -> its bf_config field; the second table: the spellings the mcra node reads (mcra.cpp:180-217)
+YAML_KEYS = {
+    "initial_angle": "theta", "past_windows": "past_windows", "freq_mag_threshold": "freq_mag_threshold", "freq_max": "freq_max",
+    "freq_min": "freq_min", "out_amp": "out_amp", "interf_angle_threshold": "interf_angle_threshold", "mu": "mu", "lambda": "lambda_",
+    "min_phase": "min_phase", "mag_mult": "mag_mult", "mag_threshold": "mag_threshold", "min_mag": "min_mag", "smooth_size": "smooth_size",
+    "MCRA_alphaS": "mcra_alphaS", "MCRA_alphaD": "mcra_alphaD", "MCRA_alphaD2": "mcra_alphaD2", "MCRA_delta": "mcra_delta", "MCRA_L": "mcra_L",
+    "MPF_alphaS": "mpf_alphaS", "MPF_eta": "mpf_eta", "MPF_rev_gamma": "mpf_rev_gamma", "MPF_rev_delta": "mpf_rev_delta",
+    "noise_floor": "noise_floor", "out_only_noise": "out_only_noise", "out_only_mcra": "out_only_mcra",
+    "use_vad": "gsc_use_vad", "vad_threshold": "gsc_vad_threshold", "mu0": "gsc_mu0", "mu_max": "gsc_mu_max", "filter_size": "gsc_filter_size",
+    "rosjack_window_size": "hop", "rosjack_sample_rate": "sample_rate", "gss_out_sources": "gss_out_sources", "gss_postfilter": "gss_postfilter",
+}
+YAML_KEYS_MCRA = {"alphaS": "mcra_alphaS", "alphaD": "mcra_alphaD", "alphaD2": "mcra_alphaD2", "delta": "mcra_delta", "L": "mcra_L"}
+
+
+def test_yaml_reader_puts_every_key_into_its_own_field():
+    """Every key gets a value no other key has (integers, so that the int fields keep theirs): a reader that stores one twin into the
+    other's field -- alphaS / alphaD, MCRA_alphaS / MPF_alphaS, mu / mu0 -- or drops a key shows.  Both spellings of the MCRA keys."""
+    from beamform_amd import capi
+    lib = capi.load()
+    source = open(os.path.join(ROOT, "beamform_amd", "csrc", "config.cpp")).read()
+    fields = {n for n, _ in capi.BfConfig._fields_}
+    for algo, table, first in ((5, YAML_KEYS, 101), (6, {**YAML_KEYS, **YAML_KEYS_MCRA}, 301)):
+        assert set(table.values()) <= fields
+        for spelled in ((YAML_KEYS,) if algo == 5 else (YAML_KEYS, YAML_KEYS_MCRA)):   # one spelling at a time: the two write the same field
+            want = {key: first + 2 * i for i, key in enumerate(spelled)}
+            assert len(set(want.values())) == len(want)
+            c = capi.BfConfig()
+            assert lib.bf_config_init(C.byref(c), algo) == 0
+            before = {f: getattr(c, f) for f in set(table.values())}
+            text = "".join(f"{key}: {v}\n" for key, v in want.items()).encode()
+            assert lib.bf_config_parse_yaml(C.byref(c), text) == 0
+            for key, v in want.items():
+                assert getattr(c, spelled[key]) == v, (algo, key, spelled[key], getattr(c, spelled[key]))
+            for f in set(table.values()) - set(spelled.values()):   # and nothing else moved
+                assert getattr(c, f) == before[f], f
+    # the unprefixed spellings belong to the mcra node alone
+    c = capi.BfConfig()
+    lib.bf_config_init(C.byref(c), 5)
+    assert lib.bf_config_parse_yaml(C.byref(c), b"alphaS: 0.5\nL: 7\n") == 0 and (c.mcra_alphaS, c.mcra_L) == (0.95, 50)
+    # the table above is the reader's whole key list
+    read = set(re.findall(r'key == "([A-Za-z_0-9]+)"', source)) | set(re.findall(r"BF_KEY_[DI]\(([a-z_0-9]+)\)", source)) - {"name"}
+    assert read - {"verbose"} == set(YAML_KEYS) | set(YAML_KEYS_MCRA), read ^ (set(YAML_KEYS) | set(YAML_KEYS_MCRA))
+
+
 def test_create_fails_loudly_without_gpu_or_with_bad_config():
     import torch
     from beamform_amd import capi
