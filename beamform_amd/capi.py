@@ -65,12 +65,13 @@ class BfConfig(C.Structure):
         ("gsc_filter_size", C.c_int),
         ("gss_out_sources", C.c_int),
         ("gss_postfilter", C.c_int),
+        ("lcmv_out_beams", C.c_int),
     ]
 
 
 #: defaults of parameters added after the first golden fixtures were written (launch/gsc.launch:6-11)
 _LATER_KEYS = dict(gsc_use_vad=0, gsc_vad_threshold=0.1, gsc_mu0=0.0001, gsc_mu_max=0.1, gsc_filter_size=128, gss_out_sources=0,
-                   gss_postfilter=0)
+                   gss_postfilter=0, lcmv_out_beams=0)
 
 
 class BfError(RuntimeError):
@@ -412,9 +413,9 @@ def resampler_default_table():
 
 def config_from_params(p: dict, device: int = 0, n_streams: int = 1, layout: int = BF_PLANAR,
                        das_impl: int = BF_DAS_F64, n_dirs: int = 1, precision: int = BF_PRECISION_REFERENCE,
-                       gss_out_sources: int = None, gss_postfilter: int = None) -> BfConfig:
-    """bf_config from a beamform_amd.params dict (launch defaults first, then overrides).  gss_out_sources / gss_postfilter: the dict's
-    value unless given."""
+                       gss_out_sources: int = None, gss_postfilter: int = None, lcmv_out_beams: int = None) -> BfConfig:
+    """bf_config from a beamform_amd.params dict (launch defaults first, then overrides).  gss_out_sources / gss_postfilter /
+    lcmv_out_beams: the dict's value unless given."""
     L = load()
     c = BfConfig()
     rc = L.bf_config_init(C.byref(c), ALGO_ID[p["algo"]])
@@ -433,12 +434,14 @@ def config_from_params(p: dict, device: int = 0, n_streams: int = 1, layout: int
               "mag_mult", "mag_threshold", "min_mag", "smooth_size", "mcra_alphaS", "mcra_alphaD", "mcra_alphaD2",
               "mcra_delta", "mcra_L", "mpf_alphaS", "mpf_eta", "mpf_rev_gamma", "mpf_rev_delta", "noise_floor",
               "out_only_noise", "out_only_mcra", "gsc_use_vad", "gsc_vad_threshold", "gsc_mu0", "gsc_mu_max",
-              "gsc_filter_size", "gss_out_sources", "gss_postfilter"):
+              "gsc_filter_size", "gss_out_sources", "gss_postfilter", "lcmv_out_beams"):
         setattr(c, k, p[k] if k in p else _LATER_KEYS[k])  # fixtures written before a key existed
     if gss_out_sources is not None:
         c.gss_out_sources = gss_out_sources
     if gss_postfilter is not None:
         c.gss_postfilter = gss_postfilter
+    if lcmv_out_beams is not None:
+        c.lcmv_out_beams = lcmv_out_beams
     c.device, c.n_streams, c.layout, c.das_impl, c.n_dirs = device, n_streams, layout, das_impl, n_dirs
     c.precision = precision
     return c
@@ -463,15 +466,17 @@ class Beamformer:
 
     def __init__(self, params: dict, device: int = 0, n_streams: int = 1, layout: int = BF_PLANAR,
                  das_impl: int = BF_DAS_F64, n_dirs: int = 1, precision: int = BF_PRECISION_REFERENCE, gss_out_sources: int = None,
-                 gss_postfilter: int = None):
+                 gss_postfilter: int = None, lcmv_out_beams: int = None):
         """gss_out_sources = R > 1 (gss only): every beam yields its R separated sources, not only the first (bf_config.gss_out_sources);
         the outputs gain an axis of length R, innermost among the stream axes.  gss_postfilter = 1 (gss only): every separated source
         goes through the multi-source post-filter (bf_config.gss_postfilter: noise, leak of the other sources and reverberation come off
-        its magnitude)."""
+        its magnitude).  lcmv_out_beams = R > 1 (lcmv only): every beam yields R signals, row r looking at constraint column r (the look
+        direction, then the interferers) with nulls on the other columns (bf_config.lcmv_out_beams); same extra axis as gss_out_sources."""
         self._L = load()
-        self.cfg = config_from_params(params, device, n_streams, layout, das_impl, n_dirs, precision, gss_out_sources, gss_postfilter)
+        self.cfg = config_from_params(params, device, n_streams, layout, das_impl, n_dirs, precision, gss_out_sources, gss_postfilter,
+                                      lcmv_out_beams)
         self.n_dirs = max(1, n_dirs)
-        self.n_rows = max(1, self.cfg.gss_out_sources)
+        self.n_rows = max(1, self.cfg.gss_out_sources, self.cfg.lcmv_out_beams)  # (bf_create refuses both above 1)
         self.n_out = n_streams * self.n_dirs * self.n_rows  # output streams: [stream][dir][row]
         self.M, self.H, self.N = params["n_mics"], params["hop"], 2 * params["hop"]
         self.S = len(params["interf"]) + 1 if params["algo"] in ("lcmv", "gss") else 1
@@ -506,7 +511,7 @@ class Beamformer:
 
     def stream_rms(self, y_ptr: int, n_frames: int, stream: int = 0) -> np.ndarray:
         """RMS of every output stream of a device-resident batch -> [n_streams, n_dirs] float64 ([n_streams, n_dirs, R] with
-        gss_out_sources = R > 1)."""
+        gss_out_sources / lcmv_out_beams = R > 1)."""
         out = (C.c_double * self.n_out)()
         self._chk(self._L.bf_stream_rms(self._h, y_ptr, n_frames, out, stream or None), "bf_stream_rms")
         shape = (self.n_streams, self.n_dirs) + ((self.n_rows,) if self.n_rows > 1 else ())
@@ -542,7 +547,7 @@ class Beamformer:
 
     def process_hop(self, x: np.ndarray) -> np.ndarray:
         """x [M, H] float32 (host) -> [H] float32: one jack_callback ([n_dirs, H] with look directions, [n_dirs, R, H] or [R, H] with
-        gss_out_sources = R > 1)."""
+        gss_out_sources / lcmv_out_beams = R > 1)."""
         x = np.ascontiguousarray(x, np.float32)
         assert x.shape == (self.M, self.H)
         ptrs = (C.c_void_p * self.M)(*[x[m].ctypes.data for m in range(self.M)])
@@ -553,7 +558,7 @@ class Beamformer:
 
     def process(self, x: np.ndarray, out: np.ndarray = None) -> np.ndarray:
         """Host batch. planar: x [S, M, F*H] (or [M, F*H] when S == 1); interleaved: [S, F*H, M].  -> [output streams, F*H] ([F*H] when
-        there is one), output stream = stream * n_dirs + dir; with gss_out_sources = R > 1 the rows are an axis of their own behind it:
+        there is one), output stream = stream * n_dirs + dir; with gss_out_sources / lcmv_out_beams = R > 1 the rows are an axis of their own behind it:
         [n_streams * n_dirs, R, F*H], or [R, F*H] for one beam."""
         x = np.ascontiguousarray(x, np.float32)
         n = x.size // (self.n_streams * self.M * self.H)

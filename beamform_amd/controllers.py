@@ -467,7 +467,8 @@ def follow_sources_tracked(node, doa, x: np.ndarray, frames_per_block: int, cont
     node: beamform_amd.capi.Beamformer (mvdr or lcmv, one stream); its track angles are replaced by doa.angles, and its theta and
     interferers are left at the last publication, as follow_sources leaves them.  doa: beamform_amd.capi.Doa on the same geometry,
     one stream, W = frames_per_block, angles = controller.angles.  x: [M, F*hop] float32 on the host, F a multiple of frames_per_block.
-    Returns (y [F*hop], published: list of (block index, theta, tuple of interferer angles))."""
+    Returns (y [F*hop] -- [R, F*hop] when the node has lcmv_out_beams = R > 1: row r follows column r of the track --, published: list of
+    (block index, theta, tuple of interferer angles))."""
     import torch
     H, W = node.H, int(frames_per_block)
     F = x.shape[1] // H
@@ -476,7 +477,8 @@ def follow_sources_tracked(node, doa, x: np.ndarray, frames_per_block: int, cont
     st = torch.cuda.current_stream().cuda_stream
     xd = torch.from_numpy(np.ascontiguousarray(x, np.float32)).cuda()
     maps = torch.empty((nb, A), dtype=torch.float64, device="cuda")
-    yd = torch.empty((nb * W * H,), dtype=torch.float32, device="cuda")
+    R = int(getattr(node, "n_out", 1))  # lcmv_out_beams: a row per beam
+    yd = torch.empty((R, nb * W * H) if R > 1 else (nb * W * H,), dtype=torch.float32, device="cuda")
     doa.process_device(xd.data_ptr(), nb * W, maps.data_ptr(), 0, st)
     track, published = sources_track(maps.cpu().numpy(), controller, W, n_cols, 1)
     td = torch.from_numpy(track).cuda()
@@ -505,7 +507,8 @@ def follow_sources_device(node, doa, x: np.ndarray, frames_per_block: int, k: in
     angles; with min_sep_deg > 0 a duplicate is never picked anyway).
 
     node, doa, x: as follow_sources_tracked takes them; the node is left at the last publication in the same way.
-    Returns (y [F*hop], published: list of (block index, theta, tuple of interferer angles))."""
+    Returns (y [F*hop] -- [R, F*hop] when the node has lcmv_out_beams = R > 1 --, published: list of (block index, theta, tuple of
+    interferer angles))."""
     import torch
     from .capi import ctrack_from_picks_device, doa_pick_device
     H, W, k = node.H, int(frames_per_block), int(k)
@@ -519,7 +522,8 @@ def follow_sources_device(node, doa, x: np.ndarray, frames_per_block: int, k: in
     picks = torch.empty((nb, k), dtype=torch.int32, device="cuda")
     carry = torch.full((n_cols,), -1, dtype=torch.int32, device="cuda")
     track = torch.empty((nb * W, n_cols), dtype=torch.int32, device="cuda")
-    yd = torch.empty((nb * W * H,), dtype=torch.float32, device="cuda")
+    R = int(getattr(node, "n_out", 1))  # lcmv_out_beams: a row per beam
+    yd = torch.empty((R, nb * W * H) if R > 1 else (nb * W * H,), dtype=torch.float32, device="cuda")
     doa.process_device(xd.data_ptr(), nb * W, maps.data_ptr(), 0, st)
     doa_pick_device(maps.data_ptr(), ad.data_ptr(), A, 1, nb, k, min_sep_deg, rel_floor, picks.data_ptr(), st)
     ctrack_from_picks_device(picks.data_ptr(), maps.data_ptr(), A, k, 1, nb, W, 1, min_peak, n_cols, carry.data_ptr(), track.data_ptr(), st)

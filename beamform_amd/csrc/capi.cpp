@@ -41,7 +41,7 @@ struct bf_handle {
     bf_config cfg;
     int M = 0, H = 0, N = 0, S = 1, n_streams = 1;  // n_streams: input streams
     int n_dirs = 1, n_out = 1;                      // look directions per input stream; output streams = n_streams * n_dirs * n_rows
-    int n_rows = 1;                                 // gss: separated sources emitted per beam (bf_config.gss_out_sources)
+    int n_rows = 1;                                 // gss: separated sources emitted per beam (bf_config.gss_out_sources); lcmv: beams (lcmv_out_beams)
     int device = 0, n_cus = 256;
     std::string err;
 
@@ -236,6 +236,10 @@ int bf_create(const bf_config *cfg, bf_handle **out) {
     if (cfg->gss_out_sources < 0 || cfg->gss_out_sources > BF_MAX_INTERF + 1) return fail(nullptr, BF_EINVAL, "gss_out_sources out of range");
     if (cfg->gss_out_sources > 1 && cfg->algo != BF_GSS)
         return fail(nullptr, BF_EINVAL, "gss_out_sources: only gss separates sources (the other nodes have one output per beam)");
+    if (cfg->lcmv_out_beams < 0 || cfg->lcmv_out_beams > BF_MAX_INTERF + 1) return fail(nullptr, BF_EINVAL, "lcmv_out_beams out of range");
+    if (cfg->lcmv_out_beams > 1 && cfg->algo != BF_LCMV)
+        return fail(nullptr, BF_EINVAL, "lcmv_out_beams: only lcmv has a beam per constraint column");
+    if (cfg->lcmv_out_beams > 1 && cfg->gss_out_sources > 1) return fail(nullptr, BF_EINVAL, "lcmv_out_beams and gss_out_sources exclude each other");
     if (cfg->gss_postfilter != 0 && cfg->gss_postfilter != 1) return fail(nullptr, BF_EINVAL, "gss_postfilter must be 0 or 1");
     if (cfg->gss_postfilter != 0 && cfg->algo != BF_GSS)
         return fail(nullptr, BF_EINVAL, "gss_postfilter: only gss has separated sources to filter");
@@ -256,7 +260,7 @@ int bf_create(const bf_config *cfg, bf_handle **out) {
     h->n_streams = cfg->n_streams;
     h->n_dirs = cfg->n_dirs > 1 ? cfg->n_dirs : 1;
     h->cfg.n_dirs = h->n_dirs;
-    h->n_rows = cfg->gss_out_sources > 1 ? cfg->gss_out_sources : 1;
+    h->n_rows = cfg->gss_out_sources > 1 ? cfg->gss_out_sources : cfg->lcmv_out_beams > 1 ? cfg->lcmv_out_beams : 1;
     h->n_out = h->n_streams * h->n_dirs * h->n_rows;
     h->device = cfg->device;
     h->angle.assign(h->n_dirs, cfg->theta);
@@ -679,6 +683,7 @@ int bf_shard_run(bf_handle *h, const float *x_feed_dev, const bf_shard *sh, floa
     if (!h || !sh) return BF_EINVAL;
     if (h->n_streams != 1 || h->n_dirs != 1)
         return fail(h, BF_EINVAL, "frame-range sharding drives one input stream and one look direction per handle");
+    if (h->cfg.algo == BF_LCMV && h->n_rows > 1) return fail(h, BF_EINVAL, "frame-range sharding: the feed buffer is one stream (lcmv_out_beams > 1)");
     const long long n_feed = bf_shard_n_feed(sh);
     if (n_feed < 0 || sh->warm < 0 || sh->lead < 0) return fail(h, BF_EINVAL, "malformed shard");
     int rc = bf_reset_async(h, hip_stream);  // the rank's node knows nothing about the frames before its slice
@@ -819,7 +824,7 @@ static uint64_t state_cfg_hash(const bf_handle *h) {
     return x;
 }
 
-// header word `das_impl`: the das arithmetic, and above it gss's rows per beam minus one (the blob carries that many overlap-add tails per
+// header word `das_impl`: the das arithmetic, and above it gss's (lcmv's) rows per beam minus one (the blob carries that many overlap-add tails per
 // beam: a handle of another row count must refuse it; one row leaves the word, and so the blob, as it always was), and in bit 24 gss's
 // post-filter (the blob then carries the filter's state per row; off leaves the word as it was)
 static uint32_t state_impl_word(const bf_handle *h) {

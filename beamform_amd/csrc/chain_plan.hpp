@@ -20,6 +20,8 @@ namespace bf {
 // ctrack_cols (last once more: a shape written without it means 0 = none): the batch carries a column track
 // (bf_process_batch_device_ctracked: a table index per (stream, frame, constraint column); mvdr / lcmv, one look direction).
 // gss_postfilter (last yet again: a shape written without it means 0 = off): bf_config.gss_postfilter, ignored by every node but gss.
+// lcmv_rows (last, as the others: a shape written without it means one): beams lcmv emits per stream and look direction
+// (bf_config.lcmv_out_beams; 0 = 1, ignored by every other node).
 struct ChainShape {
     int algo, n_fft, layout, n_mics, n_streams, n_dirs, kp1, past_windows, precision;
     bool dump;
@@ -34,6 +36,7 @@ struct ChainShape {
     bool track;
     int ctrack_cols;
     int gss_postfilter;
+    int lcmv_rows;
 };
 
 // The kernels of each stage, template arguments behind them as ChainPlan holds them:
@@ -71,7 +74,9 @@ struct ChainPlan {
     int yh_lo, yh_hi;
     size_t z_bytes, yh_bytes, yraw_elems, frames_elems;  // d_Z_, d_Yh_, d_yraw_, d_frames_ of BinPipelineImpl
     // gss: rows per beam behind the per-bin stage (1: gss_kernel / gss_lane_kernel store y_fft = this_yf(0), gss.cpp:120-121; more: their
-    // _all variants store this_yf(0 .. rows - 1) as output streams beam * rows + r, and everything behind them runs over So * rows streams)
+    // _all variants store this_yf(0 .. rows - 1) as output streams beam * rows + r, and everything behind them runs over So * rows streams).
+    // lcmv: beams per stream and look direction (1: the per-bin kernels store (G^-1 g)_0; more: mvdr_fast_rows_kernel / mvdr_fast_track_rows_kernel /
+    // cov2d_rows_kernel, or the group kernel counting at run time, store (G^-1 g)_r as row r -- which kernel family runs does not depend on it)
     int rows;
     // the front / per-bin kernels are the track twins: the steering pointer of a frame comes from the batch's track (BinsArgs::track)
     bool track;
@@ -98,7 +103,7 @@ inline ChainPlan chain_decide(const ChainShape &c) {
     const bool dump = c.dump && !gsc;  // time-domain node: there is no single y_fft, the dump reads as zeros
     const bool mixed = c.precision == BF_PRECISION_MIXED;
     const int NP = ((a == BF_MCRA ? 1 : M) + 1) / 2, D = gsc ? M : c.n_dirs;  // gsc: one aligned output per microphone
-    const int R = (a == BF_GSS && c.gss_rows > 1) ? c.gss_rows : 1;
+    const int R = (a == BF_GSS && c.gss_rows > 1) ? c.gss_rows : (a == BF_LCMV && c.lcmv_rows > 1) ? c.lcmv_rows : 1;
     const size_t S = (size_t)c.n_streams, So = S * D, F = (size_t)c.n_frames, P = cov ? (size_t)c.past_windows : 0;
     const int mp4 = M <= 4 ? 4 : M <= 8 ? 8 : M <= 16 ? 16 : 32, km = kp1 <= 1 ? 1 : 4;
     ChainPlan p{};

@@ -110,6 +110,7 @@ int bf_config_init(bf_config *c, int algo) {
     c->precision = BF_PRECISION_REFERENCE;  // ... between the transforms too; BF_PRECISION_MIXED is the opt-in
     c->gss_out_sources = 0;  // gss emits this_yf(0) alone, as gss.cpp:120-121 does
     c->gss_postfilter = 0;   // ... and without a post-filter
+    c->lcmv_out_beams = 0;   // lcmv keeps W.col(0) alone, as lcmv.cpp:119 does
     return BF_OK;
 }
 

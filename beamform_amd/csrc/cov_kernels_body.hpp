@@ -4,6 +4,9 @@
 //                                                     column track (bf_process_batch_device_ctracked, BinsArgs::track / track_cols)
 // Textual inclusion, as gss_kernels_body.hpp: the untracked kernels keep their names in the launch trace and compile to the instructions
 // they always were (a __global__ wrapper around a shared inlined body moved their SGPR counts and a few AGPR / scratch figures).
+//   BF_COV_ROWS 1 (with either BF_COV_TRACK)          mvdr_fast_rows_kernel, mvdr_fast_track_rows_kernel: the lane kernel's twins that store
+//                                                     every beam of lcmv (bf_config.lcmv_out_beams, BinsArgs::gss_rows rows per stream); the
+//                                                     group kernel is defined by the BF_COV_ROWS 0 inclusions only: it counts its rows at run time
 // No include guard: meant to be included more than once.
 
 // KC = constraint columns: 1 = mvdr (the steering vector); 2..4 = lcmv with up to KC - 1 interferers (lcmv.cpp:102-130): the
@@ -12,9 +15,17 @@
 // Z128: the spectra are complex doubles (the default, BF_PRECISION_REFERENCE: 16 bytes per element) instead of z48 (BF_PRECISION_MIXED: 12 bytes); both stored halved
 // TRACK (mvdr_fast_track_kernel): a column-tracked batch (bf_process_batch_device_ctracked) -- the columns of frame t come from the tables its
 // track entries name (BinsArgs::track: [stream][frame][track_cols]), looked up per lane, since the lanes of a wavefront sit in different tiles.
+// BF_COV_ROWS (mvdr_fast_rows_kernel, mvdr_fast_track_rows_kernel; lcmv only, KC >= 2): the whole solution gv[0 .. KC-1] of G y = g is stored, entry r
+// = column r of W^H x = the beam that looks at constraint column r with nulls on the others, as row r of the stream's a.gss_rows rows
+// (Yh = [stream][rows][frame][kYhStride]).  Rows past the columns in force are zero; behind a closed gate every row in force is 0.01 X_0
+// (lcmv.cpp:121).  The arithmetic is the one-row kernel's: row 0 is its output bit for bit.  With BF_COV_ROWS 0 the preprocessor leaves the
+// kernel's tokens as they were before the rows existed.
 template <int MP, int KC, bool Z128>
 __global__ __launch_bounds__(64, 1) void BF_COV_NAME(mvdr_fast)(BinsArgs a, FastPlan fp) {
     constexpr bool TRACK = BF_COV_TRACK;
+#if BF_COV_ROWS
+    constexpr int NR = KC;  // rows whose value lives in registers
+#endif
     constexpr int NT = MP * (MP + 1) / 2;
     constexpr long kZB = Z128 ? (long)sizeof(f64x2) : (long)sizeof(z48);  // bytes per stored element
     const int lane = threadIdx.x;
@@ -43,7 +54,20 @@ __global__ __launch_bounds__(64, 1) void BF_COV_NAME(mvdr_fast)(BinsArgs a, Fast
     const unsigned vn = (unsigned)(((long)dt * NP * kN + kneg) * kZB);
     const long frame_bytes = (long)NP * kN * kZB;
     const f64x2 *steer = a.steer + (long)(s % a.n_dirs) * a.steer_dir_stride + j;
+#if BF_COV_ROWS
+    const int n_rows = a.gss_rows;
+    const long yidx = ((long)s * n_rows * a.n_frames + tA0 + dt) * kYhStride + q;
+    // the frame's values into its rows -- the KC in registers, exact zeros behind them (rows past the kernel's columns)
+    auto st_rows = [&](long idx, const cd (&yv)[NR]) {
+        const long yrow = a.n_frames * kYhStride;
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+            if (r < n_rows) st_y(a, idx + r * yrow, q, yv[r]);
+        for (int r = NR; r < n_rows; ++r) st_y(a, idx + r * yrow, q, cd{0, 0});
+    };
+#else
     const long yidx = ((long)s * a.n_frames + tA0 + dt) * kYhStride + q;
+#endif
 
     // Spectra are prefetched one frame ahead by global->LDS DMA (global_load_lds_dwordx3: no VGPRs; lane l's 12 bytes
     // land at row base + 16 l -- measured, tools/ubench/lds_dma_x3.hip -- so a row is 64 slots of 16 bytes): a wavefront
@@ -167,6 +191,11 @@ __global__ __launch_bounds__(64, 1) void BF_COV_NAME(mvdr_fast)(BinsArgs a, Fast
     const float thr32 = (float)(a.cfg.freq_mag_threshold * (double)((unsigned)M * (unsigned)kN));
     cd y_prev{0, 0};  // frame it - 1's output: stored one iteration late, behind the next frame's DMA requests, so that no s_waitcnt vmcnt(0)
                       // of an iteration waits for a store issued a few instructions earlier
+#if BF_COV_ROWS
+    cd yr_prev[NR];   // the same, a value per row
+#pragma unroll
+    for (int r = 0; r < NR; ++r) yr_prev[r] = cd{0, 0};
+#endif
     if constexpr (DEEP) BF_DMA_WAIT();  // (the steering vector and the ring's first two frames are there whatever P is: hipcc's model enters the loop with nothing pending)
     int sn = 0;  // DEEP: ring slot of frame it (it mod 3)
     for (long it = 0; it < n_it; ++it) {
@@ -233,14 +262,22 @@ __global__ __launch_bounds__(64, 1) void BF_COV_NAME(mvdr_fast)(BinsArgs a, Fast
             // emptied -- in this order: the next top-of-loop wait lets exactly the youngest MP requests stand
             __builtin_amdgcn_sched_barrier(0);
             dma_rows(Zu + (it - P) * frame_bytes, 3);
+#if BF_COV_ROWS
+            if (it > 0 && it - 1 < cnt) st_rows(yidx + (it - 1) * kYhStride, yr_prev);
+#else
             if (it > 0 && it - 1 < cnt) st_y(a, yidx + (it - 1) * kYhStride, q, y_prev);
+#endif
             dma_rows(Zu + (it + 2 < n_it ? it + 2 : n_it - 1) * frame_bytes, sp);
             __builtin_amdgcn_sched_barrier(0);
         } else {
             BF_DMA_WAIT();
             __builtin_amdgcn_sched_barrier(0);
             dma_frame(it + 1 < n_it ? it + 1 : it, true, pb ^ 1);
+#if BF_COV_ROWS
+            if (it > 0 && it - 1 < cnt) st_rows(yidx + (it - 1) * kYhStride, yr_prev);
+#else
             if (it > 0 && it - 1 < cnt) st_y(a, yidx + (it - 1) * kYhStride, q, y_prev);
+#endif
             __builtin_amdgcn_sched_barrier(0);
         }
         cd X[MP];
@@ -267,6 +304,11 @@ __global__ __launch_bounds__(64, 1) void BF_COV_NAME(mvdr_fast)(BinsArgs a, Fast
         }
         cd y = X[0] * 0.01;  // gate closed: mvdr.cpp:96
         if (q == 0 && !fp.solve0) y = a.cfg.algo == BF_LCMV ? cd{0, 0} : X[0];  // mvdr.cpp:76; lcmv has no such rule: problem 0 out of band reads as zero
+#if BF_COV_ROWS
+        cd yr[NR];  // what a closed gate or an out-of-band problem 0 leaves on every row in force
+#pragma unroll
+        for (int r = 0; r < NR; ++r) yr[r] = r < a.kp1 ? y : cd{0, 0};
+#endif
         if (__builtin_amdgcn_ballot_w64(open && solve_q) != 0) {
             cd A[NT];
 #pragma unroll
@@ -360,19 +402,37 @@ __global__ __launch_bounds__(64, 1) void BF_COV_NAME(mvdr_fast)(BinsArgs a, Fast
                     gv[k] = acc * pinvs[k];
                 }
                 if (open && solve_q) y = gv[0];
+#if BF_COV_ROWS
+                if (open && solve_q) {
+#pragma unroll
+                    for (int r = 0; r < NR; ++r) yr[r] = r < a.kp1 ? gv[r] : cd{0, 0};
+                }
+#endif
             }
         }
         y_prev = y;
+#if BF_COV_ROWS
+#pragma unroll
+        for (int r = 0; r < NR; ++r) yr_prev[r] = yr[r];
+#endif
         pb ^= 1;
         sn = sn == 2 ? 0 : sn + 1;
     }
     BF_DMA_WAIT();  // (the last iterations' idle requests)
+#if BF_COV_ROWS
+    if (n_it > 0 && n_it - 1 < cnt) st_rows(yidx + (n_it - 1) * kYhStride, yr_prev);
+#else
     if (n_it > 0 && n_it - 1 < cnt) st_y(a, yidx + (n_it - 1) * kYhStride, q, y_prev);
+#endif
 #undef BF_DMA_WAIT
 }
 
+#if !BF_COV_ROWS
+
 // TRACK (mvdr_lcmv_track_kernel): a column-tracked batch -- cst[] is reloaded at every frame from the tables the frame's track entries name
 // (the rule of the lane kernel above).  Correct, not tuned: the entries are read where they are used.
+// Rows (lcmv_out_beams; a.gss_rows > 1, lcmv only): entry r of the solution of G y = g goes to row r of the stream's rows, as the lane kernel's
+// twins have it -- counted at run time here: with one row the loop runs once over today's value.
 template <int MP, int KM>
 __global__ __launch_bounds__(256) void BF_COV_NAME(mvdr_lcmv)(BinsArgs a, int tile, int tiles_per_stream) {
     constexpr bool TRACK = BF_COV_TRACK;
@@ -399,7 +459,8 @@ __global__ __launch_bounds__(256) void BF_COV_NAME(mvdr_lcmv)(BinsArgs a, int ti
     const int M = a.n_mics, NP = (M + 1) >> 1, KP1 = a.kp1, P = a.cfg.past_windows;
     const int j = q_bin(q);
     const bool lcmv = a.cfg.algo == BF_LCMV;
-    const long yidx = ((long)s * a.n_frames) * kYhStride + q;
+    const int n_rows = a.gss_rows;
+    const long yidx = ((long)s * n_rows * a.n_frames) * kYhStride + q, yrow = a.n_frames * kYhStride;
     const long z0 = ((long)(s / a.n_dirs) * a.frames_ws + a.frame_off) * NP * kN;  // element index of frame 0 of this batch
     const f64x2 *steer = a.steer + (long)(s % a.n_dirs) * a.steer_dir_stride;
 
@@ -434,7 +495,8 @@ __global__ __launch_bounds__(256) void BF_COV_NAME(mvdr_lcmv)(BinsArgs a, int ti
                 y = s_x[grp][0];
                 __builtin_amdgcn_wave_barrier();
             }
-            if (i == 0) st_y(a, yidx + t * kYhStride, q, y);
+            if (i == 0)
+                for (int r = 0; r < n_rows; ++r) st_y(a, yidx + r * yrow + t * kYhStride, q, y);  // (more than one row: lcmv, y = 0)
         }
         return;
     }
@@ -584,8 +646,16 @@ __global__ __launch_bounds__(256) void BF_COV_NAME(mvdr_lcmv)(BinsArgs a, int ti
                 gv[k] = acc * pinvs[k];
             }
             y = gv[0];
+            if (i == 0) {  // the other beams: entry r looks at column r; rows past the columns in force are zero
+#pragma unroll
+                for (int r = 1; r < KM; ++r)
+                    if (r < n_rows) st_y(a, yidx + r * yrow + t * kYhStride, q, r < KP1 ? gv[r] : cd{0, 0});
+                for (int r = KM; r < n_rows; ++r) st_y(a, yidx + r * yrow + t * kYhStride, q, cd{0, 0});
+            }
         } else {
-            y = s_x[grp][0] * 0.01;  // in_fft(0,j)*0.01 (mvdr.cpp:96)
+            y = s_x[grp][0] * 0.01;  // in_fft(0,j)*0.01 (mvdr.cpp:96), on every row in force (lcmv.cpp:121)
+            if (i == 0)
+                for (int r = 1; r < n_rows; ++r) st_y(a, yidx + r * yrow + t * kYhStride, q, r < KP1 ? y : cd{0, 0});
         }
         if (i == 0) st_y(a, yidx + t * kYhStride, q, y);
         // slide the covariance window: + x_t x_t^H - x_{t-P} x_{t-P}^H (mvdr.cpp:100-101)
@@ -594,3 +664,4 @@ __global__ __launch_bounds__(256) void BF_COV_NAME(mvdr_lcmv)(BinsArgs a, int ti
         __builtin_amdgcn_wave_barrier();
     }
 }
+#endif  // !BF_COV_ROWS

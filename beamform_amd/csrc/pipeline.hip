@@ -50,6 +50,7 @@ class BinPipelineImpl : public Engine {
         if (time_node_) D_ = M_;                            // gsc: one aligned output per microphone (do_overlap_bymic)
         So_ = S_ * D_;                                      // beams (output streams of every node but gss with several rows)
         R_ = (c.algo == BF_GSS && c.gss_out_sources > 1) ? c.gss_out_sources : 1;  // separated sources emitted per beam (gss.cpp:120-121 keeps one)
+        if (c.algo == BF_LCMV && c.lcmv_out_beams > 1) R_ = c.lcmv_out_beams;     // lcmv: a beam per constraint column (lcmv.cpp:119 keeps column 0)
         const bool multi = (c.algo == BF_LCMV || c.algo == BF_GSS);
         KP1_ = multi ? c.n_interf + 1 : 1;
         Phist_ = cov_node_ ? c.past_windows : 0;
@@ -353,8 +354,8 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
     const ChainPlan p = chain_decide(ChainShape{cfg_.algo, N_, layout, M_, S_, cfg_.n_dirs > 1 ? cfg_.n_dirs : 1, snap.kp1, cfg_.past_windows,
                                                 cfg_.precision, spectrum != nullptr, F, n_cus_, cfg_.gsc_filter_size, cfg_.smooth_size,
                                                 band_yh_lo_, band_yh_hi_, (reinterpret_cast<size_t>(y) & 15) == 0, sw.fused_bins,
-                                                sw.stft_small, sw.stft_split, sw.mvdr_group, sw.gss_group, sw.gsc_serial, R_, snap.track != nullptr && snap.track_cols == 0,
-                                                snap.track != nullptr ? snap.track_cols : 0, post_filter_ ? 1 : 0});
+                                                sw.stft_small, sw.stft_split, sw.mvdr_group, sw.gss_group, sw.gsc_serial, cfg_.algo == BF_GSS ? R_ : 1, snap.track != nullptr && snap.track_cols == 0,
+                                                snap.track != nullptr ? snap.track_cols : 0, post_filter_ ? 1 : 0, cfg_.algo == BF_LCMV ? R_ : 1});
     float *const hist = d_hist2_[hist_cur_].get();
     const long FT = Phist_ + F;  // frames in the Z workspace per stream
     ENGINE_HIP(d_Z_.reserve(p.z_bytes));
@@ -406,7 +407,7 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
     IstftArgs ia;
     ia.Yh = Yh; ia.y = yraw_target_ ? d_yraw_.get() : y; ia.tail_in = d_tail_[tail_cur_].get();
     ia.tail_out = d_tail_[tail_cur_ ^ 1].get(); ia.tw = d_tw_.get(); ia.win = d_win_.get(); ia.n_frames = F;
-    ia.n_streams = So_ * p.rows;  // gss: every row of a beam is an output stream (beam * rows + r) with its own overlap-add tail
+    ia.n_streams = So_ * p.rows;  // gss, lcmv with several beams: every row of a beam is an output stream (beam * rows + r) with its own overlap-add tail
     ia.tw32 = d_tw32_.get();
     ia.tw_w64 = d_tw_w64_.get();
     ia.yh32 = ba.yh32; ia.yh_lo = ba.yh_lo; ia.yh_hi = ba.yh_hi;

@@ -69,7 +69,7 @@ struct StftArgs {
 
 struct BinsArgs {
     const f64x2 *Z;      // [stream][frames_ws][NP][N] f64x2 (z48 elements for mvdr / lcmv: reinterpret)
-    f64x2 *Yh;           // [stream][n_frames][kYhStride]: y_fft of problems q = 0..N/2+1 (f32x2 rows when yh32); gss with gss_rows > 1:
+    f64x2 *Yh;           // [stream][n_frames][kYhStride]: y_fft of problems q = 0..N/2+1 (f32x2 rows when yh32); gss / lcmv with gss_rows > 1:
                          // [stream][gss_rows][n_frames][kYhStride]
     int yh32;            // mvdr / lcmv in front of the fp32 backward transform: rows are f32x2 and only the problems
                          // 0 and yh_lo..yh_hi are written (the rest is zero by definition: mvdr.cpp:103) -- istft32 knows
@@ -97,7 +97,8 @@ struct BinsArgs {
     const double *rec_win = nullptr;
     int mpf32;           // phasempf in front of the fp32 backward transform: the recursion leaves y_fft as f32x2 rows in the slots of its
                          // |out_int|^2 input (8 bytes each, same [stream][frame][kYhStride] layout, behind the f64x2 rows)
-    int gss_rows = 1;    // gss: separated sources stored per beam (ChainPlan::rows); n_streams, Z, steer, gssW and the reset mask stay per BEAM
+    int gss_rows = 1;    // rows stored per beam (ChainPlan::rows) -- gss: separated sources (bf_config.gss_out_sources); lcmv: one beam per constraint
+                         // column (bf_config.lcmv_out_beams); n_streams, Z, steer, gssW and the reset mask stay per BEAM
     // steering track of the batch (ChainPlan::track; das / phase / phasempf, one look direction): frame t of stream s is weighted with
     // track_tables + track[s * n_frames + t] * track_stride when that index lies in 0 .. track_n-1, with `steer` otherwise
     const int32_t *track = nullptr;        // [stream][n_frames]

@@ -56,6 +56,7 @@ _BASE = dict(
     gsc_use_vad=0, gsc_vad_threshold=0.1, gsc_mu0=0.0001, gsc_mu_max=0.1, gsc_filter_size=128,
     gss_out_sources=0,  # build-specific (bf_config.gss_out_sources): 0/1 = the reference's single output, R > 1 = every separated source
     gss_postfilter=0,   # build-specific (bf_config.gss_postfilter): 1 = the multi-source post-filter over gss's separated sources
+    lcmv_out_beams=0,   # build-specific (bf_config.lcmv_out_beams): 0/1 = the reference's single output, R > 1 = a beam per constraint column
 )
 
 
@@ -66,6 +67,7 @@ def make_params(algo: str, n_mics: int = 8, **overrides) -> dict:
     (SURVEY.md 8d).  `interf` is the list of interferer angles (lcmv/gss).
     `gss_out_sources` = R > 1 makes gss emit its R separated sources per beam.
     `gss_postfilter` = 1 runs the multi-source post-filter over them.
+    `lcmv_out_beams` = R > 1 makes lcmv emit a beam per constraint column (the look direction, then the interferers).
     """
     if algo not in ALGO_ID:
         raise ValueError(f"unknown algo {algo!r}")

@@ -99,6 +99,8 @@ def run_shard(bf, x_feed_ptr: int, sh: Shard, y_feed_ptr: int, stream: int = 0, 
     """
     if bf.n_streams != 1 or bf.n_dirs != 1:
         raise ValueError("frame-range sharding drives one input stream and one look direction per handle")
+    if getattr(getattr(bf, "cfg", None), "lcmv_out_beams", 0) > 1:  # as bf_shard_run refuses it
+        raise ValueError("frame-range sharding: y_feed is one stream (lcmv_out_beams > 1)")
     if reset:
         bf.reset_async(stream)
     if sh.n_feed > 0:

@@ -1,7 +1,7 @@
 // follow_sources_node.cpp -- an lcmv node that follows the sources a Capon map shows, with the whole loop on the device.
 //
 //   follow_sources_node <beamform_config.yaml> <in.wav> <out.wav> <frames_per_block> <angle_lo> <angle_hi> <angle_step>
-//                       [k=2] [min_sep_deg=30] [rel_floor=0] [min_peak=0] [freq_lo=100] [freq_hi=16000]
+//                       [k=2] [min_sep_deg=30] [rel_floor=0] [min_peak=0] [freq_lo=100] [freq_hi=16000] [beams=1]
 //
 // The config's look direction (initial_angle) and its interferers (angle_interf<k>) are where the node starts; the candidate grid is
 // angle_lo, angle_lo + angle_step, ... below angle_hi (degrees).  Per block of frames_per_block periods the strongest peak of the
@@ -11,6 +11,8 @@
 // Picks and maps come back once, at the end: one line per publishing block on stdout,
 //   "<block> <theta_deg> <interferer_deg> ..."
 // and the output as rosjack's write_file option writes it: mono PCM16 (rosjack.cpp:189-210, 404-409).
+// beams = R > 1 (bf_config.lcmv_out_beams): one signal per constraint column -- row r follows column r of the track (0: the look
+// direction, r: interferer r) with nulls on the others -- written to <out.wav>.<r>.wav, one file per row, instead of <out.wav>.
 // in.wav: a multichannel WAV file (its first n_mics channels, its sample rate).  Trailing periods that do not fill a block are dropped.
 #include <hip/hip_runtime.h>
 
@@ -43,7 +45,7 @@ int main(int argc, char **argv) {
     if (argc < 8) {
         fprintf(stderr,
                 "usage: %s <config.yaml> <in.wav> <out.wav> <frames_per_block> <angle_lo> <angle_hi> <angle_step> [k=2] [min_sep_deg=30] "
-                "[rel_floor=0] [min_peak=0] [freq_lo=100] [freq_hi=16000]\n",
+                "[rel_floor=0] [min_peak=0] [freq_lo=100] [freq_hi=16000] [beams=1]\n",
                 argv[0]);
         return 2;
     }
@@ -58,7 +60,9 @@ int main(int argc, char **argv) {
     const double min_sep = argc > 9 ? atof(argv[9]) : 30.0, rel_floor = argc > 10 ? atof(argv[10]) : 0.0;
     const double min_peak = argc > 11 ? atof(argv[11]) : 0.0;
     const double freq_lo = argc > 12 ? atof(argv[12]) : 100.0, freq_hi = argc > 13 ? atof(argv[13]) : 16000.0;
-    if (W < 1 || !(step > 0) || !(hi > lo) || (hi - lo) / step > BF_DOA_MAX_ANGLES) {
+    const int beams = argc > 14 ? atoi(argv[14]) : 1;
+    if (beams > 1) cfg.lcmv_out_beams = beams;
+    if (W < 1 || beams < 1 || !(step > 0) || !(hi > lo) || (hi - lo) / step > BF_DOA_MAX_ANGLES) {
         fprintf(stderr, "bad block length or grid\n");
         return 2;
     }
@@ -77,7 +81,7 @@ int main(int argc, char **argv) {
     }
     cfg.sample_rate = rate;
     const size_t nb = n / ((size_t)H * W), frames = nb * W, len = frames * (size_t)H;
-    std::vector<float> x((size_t)M * len), y(len);
+    std::vector<float> x((size_t)M * len), y((size_t)beams * len);  // y: [beams][len]
     for (int m = 0; m < M; ++m) memcpy(&x[(size_t)m * len], planar + (size_t)m * n, len * sizeof(float));  // the first n_mics channels
     bf_wav_free(planar);
 
@@ -132,13 +136,18 @@ int main(int argc, char **argv) {
         printf("\n");
         ++n_pub;
     }
-    bf_wav_writer *w = nullptr;
-    if (bf_wav_writer_open(argv[3], (int)cfg.sample_rate, &w) != BF_OK) {
-        fprintf(stderr, "cannot write %s\n", argv[3]);
-        return 2;
+    for (int r = 0; r < beams; ++r) {
+        char name[4096];
+        if (beams > 1) snprintf(name, sizeof(name), "%s.%d.wav", argv[3], r);
+        else snprintf(name, sizeof(name), "%s", argv[3]);
+        bf_wav_writer *w = nullptr;
+        if (bf_wav_writer_open(name, (int)cfg.sample_rate, &w) != BF_OK) {
+            fprintf(stderr, "cannot write %s\n", name);
+            return 2;
+        }
+        for (size_t t = 0; t < frames; ++t) bf_wav_writer_write(w, &y[(size_t)r * len + t * (size_t)H], (size_t)H);  // one sf_write_float per callback
+        bf_wav_writer_close(w);
     }
-    for (size_t t = 0; t < frames; ++t) bf_wav_writer_write(w, &y[t * (size_t)H], (size_t)H);  // one sf_write_float per callback
-    bf_wav_writer_close(w);
     fprintf(stderr, "lcmv: %zu callbacks in blocks of %d, %d mics, %d interferers, %d angles, %zu publications -> %s\n", frames, W, M,
             cfg.n_interf, A, n_pub, argv[3]);
     return 0;

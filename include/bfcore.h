@@ -179,6 +179,31 @@ typedef struct bf_config {
                                       sep_matrix; the noise estimate is about the room), is zeroed by bf_reset and travels in the
                                       state blob, which a handle without the filter refuses (and the other way round).  The
                                       spectrum dump shows the filtered rows; R = 1 filters row 0 with int2 = 0 */
+    int lcmv_out_beams;            /* lcmv: beams emitted per input stream and look direction, R (0/1 = one, the reference node; up to
+                                      BF_MAX_INTERF + 1).  lcmv.cpp:116 forms W = R^-1 C (C^H R^-1 C)^-1 and keeps W.col(0)
+                                      (lcmv.cpp:119); column c of W is the beam that looks at constraint column c with unit gain and
+                                      puts nulls on every other column.  With R > 1 each beam yields R output streams, index
+                                      (stream * n_dirs + dir) * R + r, and with S_t = 1 + interferers columns in force at frame t
+                                        row r < S_t   is, frame by frame, the output of the reference's node with `angle` and
+                                                      interference_angles[r-1] exchanged and the same past frames (W(C P) = W(C) P for
+                                                      a column permutation P): out of band 0; gate closed 0.01 X_0 on EVERY such row
+                                                      (lcmv.cpp:121 -- unlike gss, whose rows >= 1 are 0 behind a closed gate);
+                                                      microphone 0's entry of each column as the handle has it (quirk Q3 on all columns
+                                                      alike); the frames the reference turns into NaN (cold start, singular R) are
+                                                      non-finite on the row; out_amp, window and overlap-add as row 0, own tail
+                                        row r >= S_t  exact zeros in the spectrum; in time exact zeros once its tail has been added.
+                                      R is fixed at create; a structural bf_set_interference may change S between batches: a row
+                                      that starts to exist simply starts (there is no recursive state to restart).  In a
+                                      column-tracked batch (bf_process_batch_device_ctracked) row r of a frame looks at whatever
+                                      angle column r of that frame's track names: follow K + 1 talkers, get K + 1 signals.
+                                      Wherever this header counts output streams as n_streams * n_dirs, or says "read n_streams *
+                                      n_dirs * R" for gss (y, spectrum_dev, bf_stream_rms, the [n_dirs][R][nframes] of
+                                      bf_process_hop, the state blob), the same holds here.  The state blob holds one overlap-add
+                                      tail per output row and nothing else new; a blob is accepted only by a handle with the same
+                                      R.  Row 0 is the R = 1 node's output (bit for bit with at least one interferer in force;
+                                      without any, to rounding); R = 1 runs the very kernels it always ran.  Above 1 with another
+                                      algo, negative, above BF_MAX_INTERF + 1, or above 1 together with gss_out_sources > 1:
+                                      BF_EINVAL.  bf_shard_run with R > 1: BF_EINVAL (its feed buffer is one stream) */
 } bf_config;
 #define BF_MAX_DIRS 64
 
@@ -390,7 +415,8 @@ long long bf_shard_n_feed(const bf_shard *s);     /* hops fed: lead + warm + own
 long long bf_shard_n_drop(const bf_shard *s);     /* output hops in front of the owned range that are discarded: warm + lead */
 /* One rank's step: cold start + the fed hops, enqueued on `hip_stream` without host synchronisation.  x_feed_dev holds hops
  * [first_feed, hi) of the global stream in the handle's layout, y_feed_dev n_feed * hop floats; the owned hops start at
- * element n_drop * hop of y_feed_dev.  One input stream, one look direction. */
+ * element n_drop * hop of y_feed_dev.  One input stream, one look direction, one output row: lcmv with lcmv_out_beams > 1 is
+ * BF_EINVAL (y_feed_dev is one stream). */
 int bf_shard_run(bf_handle *h, const float *x_feed_dev, const bf_shard *shard, float *y_feed_dev, void *hip_stream);
 
 /* Timing hook for bench.py: runs bf_process_batch_device `iters` times between

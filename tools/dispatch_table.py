@@ -80,7 +80,8 @@ def main():
     row("gss, 2 interferers, 64 streams", "gss", 0, (-60.0, 90.0), streams=64)
     lines = ["# Dispatch table (generated: `make dispatch-table` on a GPU box; tools/dispatch_table.py)", "",
              "One 96-frame batch per row, traced by `bf_trace_begin` / `bf_trace_end`: the kernels the library launched, in order (default `bf_config.precision` unless the row says otherwise).",
-             "Names as rocprofv3 prints them, `bf::` dropped; `n1024::` etc. = the FFT size the kernel file was compiled for.", "",
+             "Names as rocprofv3 prints them, `bf::` dropped; `n1024::` etc. = the FFT size the kernel file was compiled for.",
+             "Rows per beam: a handle with `gss_out_sources` / `lcmv_out_beams` = R > 1 launches, shape for shape, the row-storing twin of the per-bin kernel listed (`gss_kernel_all`, `gss_lane_kernel_all`; `mvdr_fast_rows_kernel`, `mvdr_fast_track_rows_kernel`, `cov2d_rows_kernel<4, 2, .>`; `mvdr_lcmv_kernel` and its track twin count rows at run time), and everything behind it over R times the streams; R = 1 launches exactly the rows below.", "",
              "| node | period | layout | mics | dirs | dump | kernels |", "|---|---|---|---|---|---|---|"]
     lines += [f"| {a} | {b} | {c} | {d} | {e} | {f} | `{g}` |" for a, b, c, d, e, f, g in rows]
     text = "\n".join(lines) + "\n"
