@@ -34,13 +34,14 @@ EXPORTS = (
     "bf_resampler_process_device", "bf_resampler_process", "bf_resampler_destroy", "bf_resampler_default_table",
     "bf_resampler_set_mode", "bf_resampler_callback", "bf_resampler_callback_device",
     "bf_doa_create", "bf_doa_set_phat_floor", "bf_doa_set_method", "bf_doa_set_loading", "bf_doa_process_device", "bf_doa_process",
+    "bf_doa_set_sources", "bf_doa_set_music_floor", "bf_doa_process_device_eig", "bf_doa_process_eig",
     "bf_doa_reset", "bf_doa_destroy",
     "bf_track_set_angles", "bf_process_batch_device_tracked", "bf_track_from_peaks_device",
     "bf_ctrack_set_angles", "bf_process_batch_device_ctracked",
     "bf_doa_pick_device", "bf_ctrack_from_picks_device",
 )
 BF_DOA_MAX_ANGLES = 1024
-BF_DOA_SRP_PHAT, BF_DOA_CAPON = 0, 1   # bf_doa_method
+BF_DOA_SRP_PHAT, BF_DOA_CAPON, BF_DOA_MUSIC = 0, 1, 2   # bf_doa_method
 BF_TRACK_MAX_ANGLES = 1024   # = BF_DOA_MAX_ANGLES: a Doa peak index is a track index
 BF_DOA_MAX_PICKS = 16        # = BF_MAX_INTERF + 1: a look direction and every interferer
 
@@ -208,6 +209,10 @@ def load():
     L.bf_doa_set_loading.argtypes = [C.c_void_p, C.c_double]
     L.bf_doa_process_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bf_doa_process.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.bf_doa_set_sources.argtypes = [C.c_void_p, C.c_int]
+    L.bf_doa_set_music_floor.argtypes = [C.c_void_p, C.c_double]
+    L.bf_doa_process_device_eig.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bf_doa_process_eig.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bf_doa_reset.argtypes = [C.c_void_p]
     L.bf_doa_destroy.argtypes = [C.c_void_p]
     L.bf_doa_destroy.restype = None
@@ -666,7 +671,7 @@ def ctrack_from_picks_device(picks_ptr: int, map_ptr: int, n_angles: int, k: int
 
 
 class Doa:
-    """Direction-of-arrival maps (bf_doa_*; SRP-PHAT by default, Capon through set_method): per block of `frames_per_block` frames, the PHAT-weighted steered response
+    """Direction-of-arrival maps (bf_doa_*; SRP-PHAT by default, Capon and MUSIC through set_method): per block of `frames_per_block` frames, the PHAT-weighted steered response
     power of every angle in `angles` (degrees) over the band [freq_lo, freq_hi] Hz, and the index of the best angle.  `params`
     supplies the geometry, hop and sample rate (a beamform_amd.params dict); the angle of a peak is what das takes in set_theta."""
 
@@ -702,9 +707,10 @@ class Doa:
         self._chk(self._L.bf_doa_set_phat_floor(self._h, float(eps)), "bf_doa_set_phat_floor")
 
     def set_method(self, method):
-        """"srp_phat" (the default) or "capon" (or the BF_DOA_* constant): the map the next process call computes.  The Capon map
-        tells several sources apart where the SRP-PHAT map shows the strongest one's sidelobes (controllers.follow_sources)."""
-        m = {"srp_phat": BF_DOA_SRP_PHAT, "capon": BF_DOA_CAPON}.get(method, method)
+        """"srp_phat" (the default), "capon" or "music" (or the BF_DOA_* constant): the map the next process call computes.  The Capon map
+        tells several sources apart where the SRP-PHAT map shows the strongest one's sidelobes (controllers.follow_sources); the MUSIC
+        map does so from the noise subspace of the same covariances, and comes with the eigenvalue profile (process(x, eig=True))."""
+        m = {"srp_phat": BF_DOA_SRP_PHAT, "capon": BF_DOA_CAPON, "music": BF_DOA_MUSIC}.get(method, method)
         if isinstance(m, str):
             raise ValueError(f"unknown Doa method {method!r}")
         self._chk(self._L.bf_doa_set_method(self._h, int(m)), "bf_doa_set_method")
@@ -713,21 +719,40 @@ class Doa:
         """Capon's diagonal loading, in (0, 1] (default 1e-3)."""
         self._chk(self._L.bf_doa_set_loading(self._h, float(delta)), "bf_doa_set_loading")
 
+    def set_sources(self, n_sources: int):
+        """MUSIC's signal-subspace dimension, 1 .. n_mics - 1 (default 1); controllers.count_sources reads it off a profile."""
+        self._chk(self._L.bf_doa_set_sources(self._h, int(n_sources)), "bf_doa_set_sources")
+
+    def set_music_floor(self, mu: float):
+        """MUSIC's map is mu / (mu + the noise-subspace response), mu in (0, 1] (default 1e-2): the contrast, never the order."""
+        self._chk(self._L.bf_doa_set_music_floor(self._h, float(mu)), "bf_doa_set_music_floor")
+
     def reset(self):
         self._chk(self._L.bf_doa_reset(self._h), "bf_doa_reset")
 
-    def process(self, x: np.ndarray):
+    def process(self, x: np.ndarray, eig: bool = False):
         """Host batch, layout as Beamformer.process -> (map [n_streams, n_blocks, n_angles] float64, peak [n_streams, n_blocks] int32);
-        the leading axis is dropped when n_streams == 1."""
+        the leading axis is dropped when n_streams == 1.  eig=True (the MUSIC method only): (map, peak, E) with the eigenvalue profile
+        E [n_streams, n_blocks, n_mics] float64, descending."""
         x = np.ascontiguousarray(x, np.float32)
         n = x.size // (self.n_streams * self.M * self.H)
         nb = n // self.W if self.W else 0
         m = np.empty((self.n_streams, nb, self.angles.size), np.float64)
         p = np.empty((self.n_streams, nb), np.int32)
+        if eig:
+            e = np.empty((self.n_streams, nb, self.M), np.float64)
+            self._chk(self._L.bf_doa_process_eig(self._h, x.ctypes.data, n, m.ctypes.data, p.ctypes.data, e.ctypes.data),
+                      "bf_doa_process_eig")
+            return (m[0], p[0], e[0]) if self.n_streams == 1 else (m, p, e)
         self._chk(self._L.bf_doa_process(self._h, x.ctypes.data, n, m.ctypes.data, p.ctypes.data), "bf_doa_process")
         return (m[0], p[0]) if self.n_streams == 1 else (m, p)
 
-    def process_device(self, x_ptr: int, n_frames: int, map_ptr: int = 0, peak_ptr: int = 0, stream: int = 0):
-        """Device buffers: map [n_streams][n_frames/W][n_angles] float64 and / or peak [n_streams][n_frames/W] int32."""
+    def process_device(self, x_ptr: int, n_frames: int, map_ptr: int = 0, peak_ptr: int = 0, stream: int = 0, eig_ptr: int = 0):
+        """Device buffers: map [n_streams][n_frames/W][n_angles] float64 and / or peak [n_streams][n_frames/W] int32; eig_ptr (the MUSIC
+        method only): the eigenvalue profile [n_streams][n_frames/W][n_mics] float64."""
+        if eig_ptr:
+            self._chk(self._L.bf_doa_process_device_eig(self._h, x_ptr, n_frames, map_ptr or None, peak_ptr or None, eig_ptr,
+                                                        stream or None), "bf_doa_process_device_eig")
+            return
         self._chk(self._L.bf_doa_process_device(self._h, x_ptr, n_frames, map_ptr or None, peak_ptr or None, stream or None),
                   "bf_doa_process_device")

@@ -369,6 +369,20 @@ def pick_sources(row, angles, k: int, min_sep_deg: float, rel_floor: float = 0.0
     return picks
 
 
+def count_sources(E_row, rel: float = 0.02, n_max: int = None) -> int:
+    """The number of sources one eigenvalue profile shows (capi.Doa.set_method("music"), process(x, eig=True): a row of E, descending):
+    the leading entries with E[i] >= rel * E[0], at least 1 and at most `n_max` (default: len - 1, the most MUSIC can separate).
+    The count is the evidence for pick_sources' k and Doa.set_sources; rel = 0.02 keeps a second source 17 dB under the first and
+    drops the sensor noise of the project's scenes (EXPERIMENTS.md has the profiles it was read from)."""
+    e = np.asarray(E_row, dtype=np.float64).ravel()
+    if n_max is None:
+        n_max = e.size - 1
+    n = 0
+    while n < e.size and e[n] >= float(rel) * e[0]:
+        n += 1
+    return max(1, min(n, int(n_max)))
+
+
 class DoaSources:
     """A publisher of a look direction and its interferers from one map row: on_map(row) returns (theta, [interferer angles]) --
     pick_sources' strongest pick and the rest in order -- or None when the strongest value is below `min_peak`."""

@@ -1,4 +1,4 @@
-// doa.cpp -- bf_doa_*: SRP-PHAT and Capon direction-of-arrival maps over the nodes' frames (include/bfcore.h, DESIGN.md "Direction-of-arrival
+// doa.cpp -- bf_doa_*: SRP-PHAT, Capon and MUSIC direction-of-arrival maps over the nodes' frames (include/bfcore.h, DESIGN.md "Direction-of-arrival
 // maps").  Host side: argument checks, the steering table (SteeringSet, the weights das steers with), scratch sizing and the launch
 // sequence per chunk of frames.  Every per-frame operation runs in the gfx950 kernels (pipeline_kernels.hpp launch_stft,
 // doa_kernels.hip); there is no CPU fallback.
@@ -24,12 +24,14 @@ struct bf_doa {
     double eps = 1e-10;
     int method = BF_DOA_SRP_PHAT;                 // bf_doa_set_method
     double delta = 1e-3;                          // bf_doa_set_loading
+    int n_sources = 1;                            // bf_doa_set_sources
+    double mu = 1e-2;                             // bf_doa_set_music_floor
     std::string err;
     const KernelSet *ks = nullptr;
     hipStream_t stream = nullptr;                 // bf_doa_process (host buffers)
     DeviceBuffer<f64x2> d_steer, d_tw;            // [bin - klo][mic][angle]; forward-transform twiddles
-    DeviceBuffer<f64x2> d_steer_capon;            // [angle][mic][bin - klo]: built when Capon is first selected
-    DeviceBuffer<f64x2> d_ws;                     // Capon above 8 microphones: the covariance triangles of one chunk
+    DeviceBuffer<f64x2> d_steer_capon;            // [angle][mic][bin - klo]: built when Capon or MUSIC is first selected
+    DeviceBuffer<f64x2> d_ws;                     // Capon and MUSIC above 8 microphones: the per-bin matrices of one chunk
     DeviceBuffer<double> d_win;                   // sqrt-Hann
     DeviceBuffer<float> d_hist;                   // [stream][hop before the next frame], layout as the input
     // scratch for one chunk of `cap` frames (allocated on first use, grown up to the budget, kept)
@@ -41,6 +43,7 @@ struct bf_doa {
     DeviceBuffer<float> d_x;
     DeviceBuffer<double> d_map;
     DeviceBuffer<int32_t> d_peak;
+    DeviceBuffer<double> d_eig;
 };
 
 namespace {
@@ -138,9 +141,12 @@ int enqueue_stft(bf_doa *d, const float *xc, long n, long frames_ws, long mic_st
     return BF_OK;
 }
 
-// One batch of the Capon method: per chunk the forward transforms, doa_capon_kernel, the reduction over the band's segments.
-int capon_process_device(bf_doa *d, const float *x_dev, long F, double *map_dev, int32_t *peak_dev, hipStream_t s) {
-    const CaponPlan plan = capon_decide(CaponShape{d->M, d->S, d->N, d->D, d->nK, d->W, F});
+// One batch of the Capon or the MUSIC method: per chunk the forward transforms, the per-bin kernel (doa_capon_kernel / doa_music_kernel),
+// the reduction over the band's segments; MUSIC's eigenvalue profile takes a second reduction of the same kind.
+int cov_process_device(bf_doa *d, const float *x_dev, long F, double *map_dev, int32_t *peak_dev, double *eig_dev, hipStream_t s) {
+    const bool music = d->method == BF_DOA_MUSIC;
+    const CaponShape shape{d->M, d->S, d->N, d->D, d->nK, d->W, F};
+    const CaponPlan plan = music ? music_decide(shape) : capon_decide(shape);
     int rc = ensure_capon_scratch(d, plan);
     if (rc != BF_OK) return rc;
     const int M = d->M, H = d->H;
@@ -169,7 +175,13 @@ int capon_process_device(bf_doa *d, const float *x_dev, long F, double *map_dev,
         ca.n_bins = d->nK;
         ca.n_segments = plan.segments;
         ca.frames_per_block = d->W;
-        DOA_HIP(d, launch_capon(ca, plan, s));
+        if (music) {
+            ca.epart = d->d_part.get() + (size_t)plan.segments * d->S * CB * d->D;  // behind the chunk's angle rows
+            ca.n_sources = d->n_sources;
+            DOA_HIP(d, launch_music(ca, plan, s));
+        } else {
+            DOA_HIP(d, launch_capon(ca, plan, s));
+        }
         DoaReduceArgs ra;  // a block's partial sums are laid out as one frame's: the segments in order, the scale, the argmax
         ra.part = d->d_part.get();
         ra.map = map_dev;
@@ -183,7 +195,19 @@ int capon_process_device(bf_doa *d, const float *x_dev, long F, double *map_dev,
         ra.n_angles = d->D;
         ra.n_segments = plan.segments;
         ra.frames_per_block = 1;
-        DOA_HIP(d, launch_doa_reduce(ra, s));
+        if (music) {  // P = mu / (mu + sum / |K|)
+            ra.mu = d->mu;
+            ra.denom = (double)d->nK;
+        }
+        if (map_dev || peak_dev) DOA_HIP(d, launch_doa_reduce(ra, s));
+        if (eig_dev) {  // the profile: M "angles" per block, the plain mean over the band, no peak
+            ra.part = ca.epart;
+            ra.map = eig_dev;
+            ra.peak = nullptr;
+            ra.n_angles = M;
+            ra.mu = 0.0;
+            DOA_HIP(d, launch_doa_reduce(ra, s));
+        }
         DOA_HIP(d, carry_last_hop(d->d_hist.get(), xc, n, H, M, d->S, d->layout, mic_stride, stream_stride, s));
     }
     return BF_OK;
@@ -290,9 +314,9 @@ int bf_doa_set_phat_floor(bf_doa *d, double eps) {
 }
 
 int bf_doa_set_method(bf_doa *d, int method) {
-    if (!d || (method != BF_DOA_SRP_PHAT && method != BF_DOA_CAPON))
+    if (!d || (method != BF_DOA_SRP_PHAT && method != BF_DOA_CAPON && method != BF_DOA_MUSIC))
         return fail(d, BF_EINVAL, "bf_doa_set_method: NULL handle or unknown method");
-    if (method == BF_DOA_CAPON && d->d_steer_capon.size() == 0) {  // the first selection: the table with the bins innermost
+    if (method != BF_DOA_SRP_PHAT && d->d_steer_capon.size() == 0) {  // the first selection: the table with the bins innermost
         DOA_HIP(d, hipSetDevice(d->device));
         if (d->d_steer_capon.alloc(d->d_steer.size()) != hipSuccess) {
             (void)hipGetLastError();
@@ -316,15 +340,37 @@ int bf_doa_set_loading(bf_doa *d, double delta) {
     return BF_OK;
 }
 
+int bf_doa_set_sources(bf_doa *d, int n_sources) {
+    if (!d || n_sources < 1 || n_sources > d->M - 1)
+        return fail(d, BF_EINVAL, "bf_doa_set_sources: n_sources must be in 1 .. n_mics - 1");
+    d->n_sources = n_sources;
+    return BF_OK;
+}
+
+int bf_doa_set_music_floor(bf_doa *d, double mu) {
+    if (!d || !std::isfinite(mu) || !(mu > 0) || !(mu <= 1))
+        return fail(d, BF_EINVAL, "bf_doa_set_music_floor: mu must be finite and in (0, 1]");
+    d->mu = mu;
+    return BF_OK;
+}
+
 int bf_doa_process_device(bf_doa *d, const float *x_dev, size_t n_frames, double *map_dev, int32_t *peak_dev, void *hip_stream) {
     if (!d) return fail(nullptr, BF_EINVAL, "bf_doa_process_device: handle is NULL");
     if (!map_dev && !peak_dev) return fail(d, BF_EINVAL, "bf_doa_process_device: map and peak are both NULL");
+    return bf_doa_process_device_eig(d, x_dev, n_frames, map_dev, peak_dev, nullptr, hip_stream);
+}
+
+int bf_doa_process_device_eig(bf_doa *d, const float *x_dev, size_t n_frames, double *map_dev, int32_t *peak_dev, double *eig_dev,
+                              void *hip_stream) {
+    if (!d) return fail(nullptr, BF_EINVAL, "bf_doa_process_device: handle is NULL");
+    if (!map_dev && !peak_dev && !eig_dev) return fail(d, BF_EINVAL, "bf_doa_process_device: map, peak and eig are all NULL");
+    if (eig_dev && d->method != BF_DOA_MUSIC) return fail(d, BF_EINVAL, "bf_doa_process_device: eig needs the MUSIC method");
     if (n_frames % (size_t)d->W != 0) return fail(d, BF_EINVAL, "bf_doa_process_device: n_frames is not a multiple of frames_per_block");
     if (n_frames == 0) return BF_OK;
     if (!x_dev) return fail(d, BF_EINVAL, "bf_doa_process_device: x is NULL");
     hipStream_t s = (hipStream_t)hip_stream;
     DOA_HIP(d, hipSetDevice(d->device));
-    if (d->method == BF_DOA_CAPON) return capon_process_device(d, x_dev, (long)n_frames, map_dev, peak_dev, s);
+    if (d->method != BF_DOA_SRP_PHAT) return cov_process_device(d, x_dev, (long)n_frames, map_dev, peak_dev, eig_dev, s);
     const long F = (long)n_frames, CF = std::min(chunk_budget(d), F);
     int rc = ensure_scratch(d, CF);
     if (rc != BF_OK) return rc;
@@ -376,15 +422,23 @@ int bf_doa_process_device(bf_doa *d, const float *x_dev, size_t n_frames, double
 int bf_doa_process(bf_doa *d, const float *x_host, size_t n_frames, double *map_host, int32_t *peak_host) {
     if (!d) return fail(nullptr, BF_EINVAL, "bf_doa_process: handle is NULL");
     if (!map_host && !peak_host) return fail(d, BF_EINVAL, "bf_doa_process: map and peak are both NULL");
+    return bf_doa_process_eig(d, x_host, n_frames, map_host, peak_host, nullptr);
+}
+
+int bf_doa_process_eig(bf_doa *d, const float *x_host, size_t n_frames, double *map_host, int32_t *peak_host, double *eig_host) {
+    if (!d) return fail(nullptr, BF_EINVAL, "bf_doa_process: handle is NULL");
+    if (!map_host && !peak_host && !eig_host) return fail(d, BF_EINVAL, "bf_doa_process: map, peak and eig are all NULL");
+    if (eig_host && d->method != BF_DOA_MUSIC) return fail(d, BF_EINVAL, "bf_doa_process: eig needs the MUSIC method");
     if (n_frames % (size_t)d->W != 0) return fail(d, BF_EINVAL, "bf_doa_process: n_frames is not a multiple of frames_per_block");
     if (n_frames == 0) return BF_OK;
     if (!x_host) return fail(d, BF_EINVAL, "bf_doa_process: x is NULL");
     DOA_HIP(d, hipSetDevice(d->device));
-    const size_t xe = (size_t)d->S * d->M * n_frames * d->H, nb = (size_t)d->S * (n_frames / d->W), me = nb * d->D;
-    if (xe > d->d_x.size() || (map_host && me > d->d_map.size()) || (peak_host && nb > d->d_peak.size())) {
+    const size_t xe = (size_t)d->S * d->M * n_frames * d->H, nb = (size_t)d->S * (n_frames / d->W), me = nb * d->D, ee = nb * d->M;
+    if (xe > d->d_x.size() || (map_host && me > d->d_map.size()) || (peak_host && nb > d->d_peak.size()) ||
+        (eig_host && ee > d->d_eig.size())) {
         DOA_HIP(d, hipStreamSynchronize(d->stream));  // a batch still in flight may use the old staging
         if (d->d_x.reserve(xe) != hipSuccess || (map_host && d->d_map.reserve(me) != hipSuccess) ||
-            (peak_host && d->d_peak.reserve(nb) != hipSuccess)) {
+            (peak_host && d->d_peak.reserve(nb) != hipSuccess) || (eig_host && d->d_eig.reserve(ee) != hipSuccess)) {
             (void)hipGetLastError();
             return fail(d, BF_ENOMEM, "bf_doa_process staging");
         }
@@ -392,9 +446,11 @@ int bf_doa_process(bf_doa *d, const float *x_host, size_t n_frames, double *map_
     float *const d_x = d->d_x.get();
     double *const d_map = map_host ? d->d_map.get() : nullptr;
     int32_t *const d_peak = peak_host ? d->d_peak.get() : nullptr;
+    double *const d_eig = eig_host ? d->d_eig.get() : nullptr;
     DOA_HIP(d, hipMemcpyAsync(d_x, x_host, xe * sizeof(float), hipMemcpyHostToDevice, d->stream));
-    const int rc = bf_doa_process_device(d, d_x, n_frames, d_map, d_peak, d->stream);
+    const int rc = bf_doa_process_device_eig(d, d_x, n_frames, d_map, d_peak, d_eig, d->stream);
     if (rc != BF_OK) return rc;
+    if (eig_host) DOA_HIP(d, hipMemcpyAsync(eig_host, d_eig, ee * sizeof(double), hipMemcpyDeviceToHost, d->stream));
     if (map_host) DOA_HIP(d, hipMemcpyAsync(map_host, d_map, me * sizeof(double), hipMemcpyDeviceToHost, d->stream));
     if (peak_host) DOA_HIP(d, hipMemcpyAsync(peak_host, d_peak, nb * sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
     DOA_HIP(d, hipStreamSynchronize(d->stream));

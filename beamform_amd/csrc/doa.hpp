@@ -2,7 +2,8 @@
 // The spectra come from the bin pipeline's forward transform (pipeline_kernels.hpp launch_stft, packed microphone pairs, halved).
 //
 // The Capon (MVDR) map is the handle's second method (bf_doa_set_method): its launch decisions are the plain C++ of capon_decide below,
-// which the CPU suite compiles on its own (-DBF_DOA_PLAN_ONLY: no HIP header is read in front of the #ifndef).
+// which the CPU suite compiles on its own (-DBF_DOA_PLAN_ONLY: no HIP header is read in front of the #ifndef).  The MUSIC map, the third
+// method, runs on the same per-bin covariances: music_decide is capon_decide with the eigenvectors' room and the profile's partial sums.
 #pragma once
 
 #include <cstddef>
@@ -38,15 +39,16 @@ struct CaponPlan {
     size_t table_bytes;     // the steering table in the kernel's layout, [angle][mic][bin - klo] complex doubles
 };
 
-inline CaponPlan capon_decide(const CaponShape &c) {
+// ws_elems: complex doubles per problem in the work space (kWorkspace); part_cols: doubles per (segment, stream, block) of partial sums
+inline CaponPlan cov_decide(const CaponShape &c, size_t ws_elems, size_t part_cols) {
     CaponPlan p{};
     const size_t M = (size_t)c.n_mics, S = (size_t)c.n_streams, NP = (M + 1) / 2, W = (size_t)c.frames_per_block;
     p.path = c.n_mics <= kCaponRegMics ? CaponPath::kRegisters : CaponPath::kWorkspace;
     p.mp = p.path == CaponPath::kRegisters ? 2 * (int)NP : 0;
     p.segments = capon_segments(c.n_bins);
-    p.ws_elems = p.path == CaponPath::kWorkspace ? (int)(M * (M + 1) / 2 + M) : 0;
+    p.ws_elems = p.path == CaponPath::kWorkspace ? (int)ws_elems : 0;
     const size_t G = (size_t)p.segments;
-    const size_t z_block = W * S * NP * (size_t)c.nfft * 16, part_block = G * S * (size_t)c.n_angles * 8;
+    const size_t z_block = W * S * NP * (size_t)c.nfft * 16, part_block = G * S * part_cols * 8;
     const size_t ws_block = (size_t)p.ws_elems * S * G * kCaponSegBins * 16;
     long nb = (long)(kCaponChunkBytes / (z_block + part_block + ws_block));
     const long batch = c.n_frames / c.frames_per_block;
@@ -61,6 +63,19 @@ inline CaponPlan capon_decide(const CaponShape &c) {
     p.ws_bytes = ws_block * (size_t)nb;
     p.table_bytes = (size_t)c.n_angles * M * (size_t)c.n_bins * 16;
     return p;
+}
+
+// Capon: the lower triangle of R with its diagonal + the solve's vector; one partial sum per angle
+inline CaponPlan capon_decide(const CaponShape &c) {
+    const size_t M = (size_t)c.n_mics;
+    return cov_decide(c, M * (M + 1) / 2 + M, (size_t)c.n_angles);
+}
+
+// MUSIC: the triangle, the frame's spectra (then the columns' noise weights), the eigenvectors; one partial sum per angle, then, behind
+// the chunk's angle rows, one per eigenvalue: [segment][stream][chunk block][angle] ++ [segment][stream][chunk block][mic]
+inline CaponPlan music_decide(const CaponShape &c) {
+    const size_t M = (size_t)c.n_mics;
+    return cov_decide(c, M * (M + 1) / 2 + M + M * M, (size_t)c.n_angles + M);
 }
 
 }  // namespace bf
@@ -97,6 +112,7 @@ struct DoaReduceArgs {
     double *map;               // [stream][map_blocks][angle] (nullable)
     int *peak;                 // [stream][map_blocks] (nullable)
     double scale;              // 1 / (W |K| M^2)
+    double mu = 0.0, denom = 1.0;  // mu > 0 (MUSIC): the value is mu / (mu + sum / denom) and scale is not used
     long frames_ws, map_blocks, block0;  // block0: index of the chunk's first block in the caller's map
     long n_blocks;             // blocks of this chunk
     int n_streams, n_angles, n_segments, frames_per_block;
@@ -154,10 +170,15 @@ struct CaponArgs {
     double delta;              // the diagonal loading
     long frames_ws, blocks_ws, n_blocks;  // blocks of this chunk
     int n_streams, n_mics, nfft, n_angles, klo, n_bins, n_segments, frames_per_block;
+    // MUSIC only (launch_music)
+    double *epart = nullptr;   // [segment][stream][blocks_ws][mic]: sum over the segment's bins of lambda_i(k), descending
+    int n_sources = 0;         // the signal subspace's dimension, 1 .. n_mics - 1
 };
 // [bin][mic][angle] -> [angle][mic][bin]
 hipError_t launch_capon_table(const f64x2 *src, f64x2 *dst, int n_bins, int n_mics, int n_angles, hipStream_t s);
 hipError_t launch_capon(const CaponArgs &a, const CaponPlan &p, hipStream_t s);
+// MUSIC: part gets sum over the segment's bins of nu_d(k), epart the eigenvalues (p: music_decide's plan)
+hipError_t launch_music(const CaponArgs &a, const CaponPlan &p, hipStream_t s);
 
 }  // namespace bf
 #endif  // BF_DOA_PLAN_ONLY

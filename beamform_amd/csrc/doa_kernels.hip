@@ -25,11 +25,22 @@
 //                         (doa_capon_kernel<MP>); above, the triangle lives in a work space in memory (doa_capon_ws_kernel).
 //   doa_reduce_kernel     as above with one "frame" per block: segments in ascending order, the scale 1 / |K|, the argmax
 //
+// The MUSIC map and the eigenvalue profile, the third method, on the same covariances:
+//
+//   R / tau = sum_i lambda_i v_i v_i^H (descending),  nu_d(k) = 1 / M sum_{i > n} |v_i^H a_d|^2  (1 at tau <= 0, and lambda = 0)
+//   P[s][b][d] = mu / (mu + 1 / |K| sum_{k in K} nu_d(k)),  E[s][b][i] = 1 / |K| sum_{k in K} lambda_i(k)
+//
+//   doa_music_kernel      doa_capon_kernel's lane and covariance, then doa_eig.hpp's Jacobi sweeps (a fixed count) in registers, the ranks
+//                         of the eigenvalues, per angle the products with the noise columns; partial sums per (segment, stream, block,
+//                         angle) and per (segment, stream, block, eigenvalue slot).  Above 8 microphones doa_music_ws_kernel, in memory.
+//   doa_reduce_kernel     the map (mu / (mu + sum / |K|)) and the peak; a second launch for the profile (the plain mean, no peak)
+//
 // Behind the maps, without a handle: doa_pick_kernel (bf_doa_pick_device: the k strongest separated peaks of every row) and the two
 // track builders, track_from_peaks_kernel and ctrack_from_picks_kernel (one look angle, or one angle per constraint column, per frame).
 #include <climits>
 
 #include "doa.hpp"
+#include "doa_eig.hpp"
 #include "doa_pick.hpp"
 #include "launch_trace.hpp"
 
@@ -217,6 +228,7 @@ __global__ __launch_bounds__(kDoaBlock) void doa_map_kernel(DoaMapArgs a) {
 }
 
 // One workgroup per (stream, block): P = scale * sum_{t in block} (sum_g part[g][t]) in that order, then the lowest index of the maximum.
+// MUSIC (mu > 0): P = mu / (mu + sum / denom), a division so that |K| ones give exactly mu / (mu + 1).
 __global__ __launch_bounds__(kDoaBlock) void doa_reduce_kernel(DoaReduceArgs a) {
     __shared__ double bv[kDoaBlock];
     __shared__ int bi[kDoaBlock];
@@ -232,7 +244,7 @@ __global__ __launch_bounds__(kDoaBlock) void doa_reduce_kernel(DoaReduceArgs a) 
             for (int g = 0; g < a.n_segments; ++g) v += a.part[(((long)g * a.n_streams + s) * a.frames_ws + t) * D + d];
             acc += v;
         }
-        const double val = acc * a.scale;
+        const double val = a.mu > 0.0 ? a.mu / (a.mu + acc / a.denom) : acc * a.scale;
         if (a.map) a.map[((long)s * a.map_blocks + a.block0 + b) * D + d] = val;
         if (val > best) {  // ascending d per thread: the first maximum is kept
             best = val;
@@ -456,22 +468,12 @@ __global__ __launch_bounds__(kDoaBlock) void capon_table_kernel(const f64x2 *src
     }
 }
 
-// MP = 2 x microphone pairs (2, 4, 6, 8).  An odd count's last pair has a zero partner channel: its spectrum (the transform's rounding
-// residue) is never formed -- row MP-1 of R~ is pinned to the identity and its steering entry to 0, so it adds nothing to |u|^2.
-// The strict lower triangle of R (then of L) and the real diagonal (then 1 / L_ii) are registers; every loop below is unrolled.
-template <int MP>
-__global__ __launch_bounds__(64) void doa_capon_kernel(CaponArgs a) {
+// R = sum over the block's W frames (ascending) of X X^H for one bin: the strict lower triangle and the real diagonal, in registers.
+// zr: the block's first frame, [frame][pair][N] packed pair rows.  A zero partner channel (an odd count's last pair) is never formed.
+template <int MP, int NTA>
+__device__ __forceinline__ void cov_accumulate(const f64x2 *zr, int k, int N, int M, int W, double (&Rr)[NTA], double (&Ri)[NTA],
+                                               double (&Rd)[MP]) {
     constexpr int NT = MP * (MP - 1) / 2, NP = MP / 2;
-    const int lane = threadIdx.x, G = a.n_segments;
-    const long b = blockIdx.x / G;
-    const int g = (int)(blockIdx.x - b * G), s = blockIdx.y;
-    const int M = a.n_mics, N = a.nfft, D = a.n_angles, W = a.frames_per_block, nK = a.n_bins;
-    int kk = g * kCaponSegBins + lane;
-    const bool live = kk < nK;  // the band's last segment: the lanes past the band work on its last bin and add 0
-    if (!live) kk = nK - 1;
-    const int k = a.klo + kk;
-    const f64x2 *zr = a.Z + ((long)s * a.frames_ws + b * W) * NP * N;
-    double Rr[NT > 0 ? NT : 1], Ri[NT > 0 ? NT : 1], Rd[MP];
 #pragma unroll
     for (int e = 0; e < NT; ++e) Rr[e] = Ri[e] = 0.0;
 #pragma unroll
@@ -498,6 +500,25 @@ __global__ __launch_bounds__(64) void doa_capon_kernel(CaponArgs a) {
             Rd[i] = fma(xi[i], xi[i], fma(xr[i], xr[i], Rd[i]));
         }
     }
+}
+
+// MP = 2 x microphone pairs (2, 4, 6, 8).  An odd count's last pair has a zero partner channel: its spectrum (the transform's rounding
+// residue) is never formed -- row MP-1 of R~ is pinned to the identity and its steering entry to 0, so it adds nothing to |u|^2.
+// The strict lower triangle of R (then of L) and the real diagonal (then 1 / L_ii) are registers; every loop below is unrolled.
+template <int MP>
+__global__ __launch_bounds__(64) void doa_capon_kernel(CaponArgs a) {
+    constexpr int NT = MP * (MP - 1) / 2, NP = MP / 2;
+    const int lane = threadIdx.x, G = a.n_segments;
+    const long b = blockIdx.x / G;
+    const int g = (int)(blockIdx.x - b * G), s = blockIdx.y;
+    const int M = a.n_mics, N = a.nfft, D = a.n_angles, W = a.frames_per_block, nK = a.n_bins;
+    int kk = g * kCaponSegBins + lane;
+    const bool live = kk < nK;  // the band's last segment: the lanes past the band work on its last bin and add 0
+    if (!live) kk = nK - 1;
+    const int k = a.klo + kk;
+    const f64x2 *zr = a.Z + ((long)s * a.frames_ws + b * W) * NP * N;
+    double Rr[NT > 0 ? NT : 1], Ri[NT > 0 ? NT : 1], Rd[MP];
+    cov_accumulate<MP>(zr, k, N, M, W, Rr, Ri, Rd);
     double tau = 0.0;
 #pragma unroll
     for (int i = 0; i < MP; ++i) tau += Rd[i];  // (the pinned row's entry is an exact 0)
@@ -655,6 +676,207 @@ __global__ __launch_bounds__(64) void doa_capon_ws_kernel(CaponArgs a) {
     }
 }
 
+// ---- MUSIC --------------------------------------------------------------------------------------------------------------------------
+// The Capon kernels' lane per (stream, block, bin) and covariance; then R / tau = V diag(lambda) V^H by doa_eig.hpp's Jacobi sweeps (a fixed
+// count: no lane waits for another), the eigenvalues' ranks by comparisons, and per angle nu = 1 / M sum_{noise i} |v_i^H a_d|^2.
+// The store of the register kernels: the strict lower triangle, the real diagonal and V as plain arrays.  doa_eig.hpp indexes them with
+// constants only, so they are registers: 64 + 128 doubles at MP = 8 (DESIGN.md has the compiler's resource report).
+template <int MP>
+struct EigRegs {
+    static constexpr int NT = MP * (MP - 1) / 2;
+    double Rr[NT], Ri[NT], Rd[MP], Vr[MP * MP], Vi[MP * MP];
+    __device__ __forceinline__ double diag(int i) const { return Rd[i]; }
+    __device__ __forceinline__ void set_diag(int i, double v) { Rd[i] = v; }
+    __device__ __forceinline__ EigC low(int i, int c) const { return EigC{Rr[i * (i - 1) / 2 + c], Ri[i * (i - 1) / 2 + c]}; }
+    __device__ __forceinline__ void set_low(int i, int c, EigC z) {
+        Rr[i * (i - 1) / 2 + c] = z.re;
+        Ri[i * (i - 1) / 2 + c] = z.im;
+    }
+    __device__ __forceinline__ EigC vec(int r, int c) const { return EigC{Vr[r * MP + c], Vi[r * MP + c]}; }
+    __device__ __forceinline__ void set_vec(int r, int c, EigC z) {
+        Vr[r * MP + c] = z.re;
+        Vi[r * MP + c] = z.im;
+    }
+};
+
+// MP = 2 x microphone pairs (2, 4, 6, 8).  An odd count's zero partner channel is never formed: row and column MP-1 are zero with -1 on
+// the diagonal and a zero steering entry.  No rotation touches them (their pivots are exact zeros), the eigenvalue -1 sorts last, so
+// its vector e_{MP-1} is always noise (n_sources <= M - 1 <= MP - 2) and adds |e^H a|^2 = 0.
+template <int MP>
+__global__ __launch_bounds__(64) void doa_music_kernel(CaponArgs a) {
+    constexpr int NT = MP * (MP - 1) / 2, NP = MP / 2;
+    const int lane = threadIdx.x, G = a.n_segments;
+    const long b = blockIdx.x / G;
+    const int g = (int)(blockIdx.x - b * G), s = blockIdx.y;
+    const int M = a.n_mics, N = a.nfft, D = a.n_angles, W = a.frames_per_block, nK = a.n_bins;
+    int kk = g * kCaponSegBins + lane;
+    const bool live = kk < nK;  // the band's last segment: the lanes past the band work on its last bin and add 0
+    if (!live) kk = nK - 1;
+    const int k = a.klo + kk;
+    const f64x2 *zr = a.Z + ((long)s * a.frames_ws + b * W) * NP * N;
+    EigRegs<MP> e;
+    cov_accumulate<MP>(zr, k, N, M, W, e.Rr, e.Ri, e.Rd);
+    double tau = 0.0;
+#pragma unroll
+    for (int i = 0; i < MP; ++i) tau += e.Rd[i];  // (the pinned row's entry is an exact 0)
+    const bool ok = tau > 0.0;
+    const double inv = ok ? 1.0 / tau : 0.0;  // tau = 0: the zero matrix, V = I; nu and lambda are forced below
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        e.Rr[t] *= inv;
+        e.Ri[t] *= inv;
+    }
+#pragma unroll
+    for (int i = 0; i < MP; ++i) e.Rd[i] = i < M ? e.Rd[i] * inv : -1.0;
+    jacobi_eig<MP>(e, MP, jacobi_sweeps(MP));
+    int rk[MP];
+    double wgt[MP];  // 1: column i of V spans noise
+#pragma unroll
+    for (int i = 0; i < MP; ++i) {
+        rk[i] = eig_rank<MP>(e, MP, i);
+        wgt[i] = rk[i] >= a.n_sources ? 1.0 : 0.0;
+    }
+    // the profile: slot j takes the eigenvalue of rank j; a wavefront's 64 values per slot in one fixed butterfly, lane j keeps slot j
+    double keep = 0.0;
+#pragma unroll
+    for (int j = 0; j < MP; ++j) {
+        double v = 0.0;
+#pragma unroll
+        for (int i = 0; i < MP; ++i) v = rk[i] == j ? fmax(e.Rd[i], 0.0) : v;
+        const double sum = wave_sum64(live && ok ? v : 0.0);
+        if (lane == j) keep = sum;
+    }
+    if (lane < M) a.epart[(((long)g * a.n_streams + s) * a.blocks_ws + b) * M + lane] = keep;
+
+    const f64x2 *st = a.steer + kk;
+    double *row = a.part + (((long)g * a.n_streams + s) * a.blocks_ws + b) * D;
+    f64x2 an[MP];  // the next angle's steering column: requested in front of this angle's products
+#pragma unroll
+    for (int m = 0; m < MP; ++m) an[m] = m < M ? st[(long)m * nK] : f64x2{0.0, 0.0};
+    keep = 0.0;
+    for (int d = 0; d < D; ++d) {
+        double ur[MP], ui[MP];
+#pragma unroll
+        for (int m = 0; m < MP; ++m) {
+            ur[m] = an[m].x;
+            ui[m] = an[m].y;
+        }
+        const int dn = d + 1 < D ? d + 1 : d;
+#pragma unroll
+        for (int m = 0; m < MP; ++m)
+            if (m < M) an[m] = st[((long)dn * M + m) * nK];
+        double q = 0.0;
+#pragma unroll
+        for (int i = 0; i < MP; ++i) {  // y = v_i^H a = sum_m conj(V_mi) a_m
+            double yr = 0.0, yi = 0.0;
+#pragma unroll
+            for (int m = 0; m < MP; ++m) {
+                yr = fma(e.Vi[m * MP + i], ui[m], fma(e.Vr[m * MP + i], ur[m], yr));
+                yi = fma(-e.Vi[m * MP + i], ur[m], fma(e.Vr[m * MP + i], ui[m], yi));
+            }
+            q = fma(wgt[i], fma(yi, yi, yr * yr), q);
+        }
+        const double nu = ok ? q / (double)M : 1.0;
+        const double sum = wave_sum64(live ? nu : 0.0);
+        if (lane == (d & 63)) keep = sum;  // 64 angles' sums leave in one row of stores
+        if ((d & 63) == 63 || d == D - 1) {
+            const int dd = (d & ~63) + lane;
+            if (dd <= d) row[dd] = keep;
+        }
+    }
+}
+
+// More than 8 microphones: the same per-lane algorithm in memory, [element][lane of the grid] as doa_capon_ws_kernel.  Elements: the lower
+// triangle with its diagonal (idx(i, c) = i (i + 1) / 2 + c), the frame's spectra -- later per column (noise weight, rank) -- at NT + i,
+// the eigenvectors V_rc at NT + M + r M + c.  doa_eig.hpp's solver runs on it through the store below.  Correct, not tuned.
+struct EigMem {
+    f64x2 *A;
+    long stride;
+    int M, NT;
+    __device__ __forceinline__ f64x2 &at(int e) const { return A[(long)e * stride]; }
+    __device__ __forceinline__ double diag(int i) const { return at(i * (i + 1) / 2 + i).x; }
+    __device__ __forceinline__ void set_diag(int i, double v) { at(i * (i + 1) / 2 + i).x = v; }
+    __device__ __forceinline__ EigC low(int i, int c) const {
+        const f64x2 z = at(i * (i + 1) / 2 + c);
+        return EigC{z.x, z.y};
+    }
+    __device__ __forceinline__ void set_low(int i, int c, EigC z) { at(i * (i + 1) / 2 + c) = f64x2{z.re, z.im}; }
+    __device__ __forceinline__ EigC vec(int r, int c) const {
+        const f64x2 z = at(NT + M + r * M + c);
+        return EigC{z.x, z.y};
+    }
+    __device__ __forceinline__ void set_vec(int r, int c, EigC z) { at(NT + M + r * M + c) = f64x2{z.re, z.im}; }
+};
+
+__global__ __launch_bounds__(64) void doa_music_ws_kernel(CaponArgs a) {
+    const int lane = threadIdx.x, G = a.n_segments;
+    const long b = blockIdx.x / G;
+    const int g = (int)(blockIdx.x - b * G), s = blockIdx.y;
+    const int M = a.n_mics, NP = (M + 1) / 2, N = a.nfft, D = a.n_angles, W = a.frames_per_block, nK = a.n_bins, NT = M * (M + 1) / 2;
+    int kk = g * kCaponSegBins + lane;
+    const bool live = kk < nK;
+    if (!live) kk = nK - 1;
+    const int k = a.klo + kk;
+    EigMem e{a.ws + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 64 + lane, (long)gridDim.y * gridDim.x * 64, M, NT};
+    const f64x2 *zr = a.Z + ((long)s * a.frames_ws + b * W) * NP * N;
+    for (int t = 0; t < NT; ++t) e.at(t) = f64x2{0.0, 0.0};
+    for (int t = 0; t < W; ++t, zr += (long)NP * N) {
+        for (int m = 0; m < M; ++m) {  // never the zero partner of an odd count: m < M
+            const f64x2 *pr = zr + (long)(m >> 1) * N;
+            e.at(NT + m) = unpack_mic(pr[k], pr[N - k], m & 1);
+        }
+        for (int i = 0; i < M; ++i) {
+            const f64x2 x = e.at(NT + i);
+            for (int c = 0; c < i; ++c) {
+                const f64x2 y = e.at(NT + c);
+                f64x2 &r = e.at(i * (i + 1) / 2 + c);
+                r = f64x2{fma(x.y, y.y, fma(x.x, y.x, r.x)), fma(-x.x, y.y, fma(x.y, y.x, r.y))};
+            }
+            f64x2 &r = e.at(i * (i + 1) / 2 + i);
+            r.x = fma(x.y, x.y, fma(x.x, x.x, r.x));
+        }
+    }
+    double tau = 0.0;
+    for (int i = 0; i < M; ++i) tau += e.diag(i);
+    const bool ok = tau > 0.0;
+    const double inv = ok ? 1.0 / tau : 0.0;
+    for (int t = 0; t < NT; ++t) {
+        f64x2 &r = e.at(t);
+        r = f64x2{r.x * inv, r.y * inv};
+    }
+    jacobi_eig<0>(e, M, jacobi_sweeps(M));
+    for (int i = 0; i < M; ++i) {
+        const int r = eig_rank<0>(e, M, i);
+        e.at(NT + i) = f64x2{r >= a.n_sources ? 1.0 : 0.0, (double)r};
+    }
+    double *erow = a.epart + (((long)g * a.n_streams + s) * a.blocks_ws + b) * M;
+    for (int j = 0; j < M; ++j) {
+        double v = 0.0;
+        for (int i = 0; i < M; ++i)
+            if ((int)e.at(NT + i).y == j) v = fmax(e.diag(i), 0.0);
+        const double sum = wave_sum64(live && ok ? v : 0.0);
+        if (lane == 0) erow[j] = sum;
+    }
+    const f64x2 *st = a.steer + kk;
+    double *row = a.part + (((long)g * a.n_streams + s) * a.blocks_ws + b) * D;
+    for (int d = 0; d < D; ++d) {
+        double q = 0.0;
+        for (int i = 0; i < M; ++i) {
+            double yr = 0.0, yi = 0.0;
+            for (int m = 0; m < M; ++m) {
+                const EigC v = e.vec(m, i);
+                const f64x2 u = st[((long)d * M + m) * nK];
+                yr = fma(v.im, u.y, fma(v.re, u.x, yr));
+                yi = fma(-v.im, u.x, fma(v.re, u.y, yi));
+            }
+            q = fma(e.at(NT + i).x, fma(yi, yi, yr * yr), q);
+        }
+        const double nu = ok ? q / (double)M : 1.0;
+        const double sum = wave_sum64(live ? nu : 0.0);
+        if (lane == 0) row[d] = sum;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_capon_table(const f64x2 *src, f64x2 *dst, int n_bins, int n_mics, int n_angles, hipStream_t s) {
@@ -675,6 +897,23 @@ hipError_t launch_capon(const CaponArgs &a, const CaponPlan &p, hipStream_t s) {
         default:
             if (p.path != CaponPath::kWorkspace || !a.ws) return hipErrorInvalidValue;
             BF_LAUNCH(doa_capon_ws_kernel, grid, dim3(64), 0, s, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_music(const CaponArgs &a, const CaponPlan &p, hipStream_t s) {
+    if (a.n_blocks < 1 || a.n_blocks > p.chunk_blocks || a.n_segments != p.segments || !a.epart || a.n_sources < 1 ||
+        a.n_sources > a.n_mics - 1)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(a.n_blocks * p.segments), p.grid_y);
+    switch (p.mp) {
+        case 2: BF_LAUNCH(doa_music_kernel<2>, grid, dim3(64), 0, s, a); break;
+        case 4: BF_LAUNCH(doa_music_kernel<4>, grid, dim3(64), 0, s, a); break;
+        case 6: BF_LAUNCH(doa_music_kernel<6>, grid, dim3(64), 0, s, a); break;
+        case 8: BF_LAUNCH(doa_music_kernel<8>, grid, dim3(64), 0, s, a); break;
+        default:
+            if (p.path != CaponPath::kWorkspace || !a.ws) return hipErrorInvalidValue;
+            BF_LAUNCH(doa_music_ws_kernel, grid, dim3(64), 0, s, a);
     }
     return hipGetLastError();
 }

@@ -1,7 +1,7 @@
-// follow_sources_node.cpp -- an lcmv node that follows the sources a Capon map shows, with the whole loop on the device.
+// follow_sources_node.cpp -- an lcmv node that follows the sources a Capon (or MUSIC) map shows, with the whole loop on the device.
 //
 //   follow_sources_node <beamform_config.yaml> <in.wav> <out.wav> <frames_per_block> <angle_lo> <angle_hi> <angle_step>
-//                       [k=2] [min_sep_deg=30] [rel_floor=0] [min_peak=0] [freq_lo=100] [freq_hi=16000] [beams=1]
+//                       [k=2] [min_sep_deg=30] [rel_floor=0] [min_peak=0] [freq_lo=100] [freq_hi=16000] [beams=1] [capon|music[:n]]
 //
 // The config's look direction (initial_angle) and its interferers (angle_interf<k>) are where the node starts; the candidate grid is
 // angle_lo, angle_lo + angle_step, ... below angle_hi (degrees).  Per block of frames_per_block periods the strongest peak of the
@@ -13,6 +13,8 @@
 // and the output as rosjack's write_file option writes it: mono PCM16 (rosjack.cpp:189-210, 404-409).
 // beams = R > 1 (bf_config.lcmv_out_beams): one signal per constraint column -- row r follows column r of the track (0: the look
 // direction, r: interferer r) with nulls on the others -- written to <out.wav>.<r>.wav, one file per row, instead of <out.wav>.
+// music[:n]: the MUSIC map instead of the Capon map, with a signal subspace of n dimensions (bf_doa_set_sources; default k, at most
+// n_mics - 1).
 // in.wav: a multichannel WAV file (its first n_mics channels, its sample rate).  Trailing periods that do not fill a block are dropped.
 #include <hip/hip_runtime.h>
 
@@ -45,7 +47,7 @@ int main(int argc, char **argv) {
     if (argc < 8) {
         fprintf(stderr,
                 "usage: %s <config.yaml> <in.wav> <out.wav> <frames_per_block> <angle_lo> <angle_hi> <angle_step> [k=2] [min_sep_deg=30] "
-                "[rel_floor=0] [min_peak=0] [freq_lo=100] [freq_hi=16000] [beams=1]\n",
+                "[rel_floor=0] [min_peak=0] [freq_lo=100] [freq_hi=16000] [beams=1] [capon|music[:n]]\n",
                 argv[0]);
         return 2;
     }
@@ -62,6 +64,12 @@ int main(int argc, char **argv) {
     const double freq_lo = argc > 12 ? atof(argv[12]) : 100.0, freq_hi = argc > 13 ? atof(argv[13]) : 16000.0;
     const int beams = argc > 14 ? atoi(argv[14]) : 1;
     if (beams > 1) cfg.lcmv_out_beams = beams;
+    const char *method = argc > 15 ? argv[15] : "capon";
+    const bool music = strncmp(method, "music", 5) == 0 && (method[5] == '\0' || method[5] == ':');
+    if (!music && strcmp(method, "capon") != 0) {
+        fprintf(stderr, "bad method %s (capon, music or music:<n>)\n", method);
+        return 2;
+    }
     if (W < 1 || beams < 1 || !(step > 0) || !(hi > lo) || (hi - lo) / step > BF_DOA_MAX_ANGLES) {
         fprintf(stderr, "bad block length or grid\n");
         return 2;
@@ -90,7 +98,11 @@ int main(int argc, char **argv) {
     BF(bf_create(&cfg, &node));
     BF(bf_ctrack_set_angles(node, grid.data(), A));
     BF(bf_doa_create(&cfg, grid.data(), A, freq_lo, freq_hi, W, &doa));
-    BF(bf_doa_set_method(doa, BF_DOA_CAPON));
+    BF(bf_doa_set_method(doa, music ? BF_DOA_MUSIC : BF_DOA_CAPON));
+    if (music) {
+        const int n_src = method[5] == ':' ? atoi(method + 6) : (k < M - 1 ? k : M - 1);
+        BF(bf_doa_set_sources(doa, n_src));  // refuses what is outside 1 .. n_mics - 1
+    }
 
     std::vector<double> maps(nb * A);
     std::vector<int32_t> picks(nb * k), carry(n_cols, -1);

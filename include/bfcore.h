@@ -294,15 +294,51 @@ int bf_doa_set_phat_floor(bf_doa *d, double eps);            /* >= 0; default 1e
  * first selected.
  * Both setters take effect at the next bf_doa_process* call (one batch at a time per handle, as ever).  The history hop belongs to the
  * stream, not to the method: switching mid-stream continues the stream.  A handle that never calls them is the SRP-PHAT handle above. */
-enum bf_doa_method { BF_DOA_SRP_PHAT = 0, BF_DOA_CAPON = 1 };
+enum bf_doa_method { BF_DOA_SRP_PHAT = 0, BF_DOA_CAPON = 1, BF_DOA_MUSIC = 2 };
 int bf_doa_set_method(bf_doa *d, int method);                /* default BF_DOA_SRP_PHAT; BF_EINVAL: NULL handle, unknown method */
 int bf_doa_set_loading(bf_doa *d, double delta);             /* Capon's diagonal loading; default 1e-3; BF_EINVAL unless finite and 0 < delta <= 1 */
+/* ---- the MUSIC map and the eigenvalue profile: the handle's third method ---------------------------------------------------------------
+ * The Capon map's resolution is set by its loading and by how well a block's covariance is estimated, and nothing above says how many
+ * sources a block holds.  MUSIC (Schmidt 1986) answers both from the eigendecomposition of the covariance the Capon map already forms:
+ * the noise subspace gives a map whose peaks do not broaden with a loading, the eigenvalues show the number of sources
+ * (controllers.count_sources).  Every consumer of a map (bf_doa_pick_device, bf_ctrack_from_picks_device, the follow_* loops) works on it.
+ *   Frames, X_m(k), the band K and the steering columns a_d = w(theta_d, k) are exactly those above (microphone 0's row is 1, so
+ *   a_d^H a_d = M).  There is no PHAT normalisation and no loading; the PHAT floor and the loading are ignored.
+ *   Covariance: R_{s,b}(k) = sum_{t in block b, ascending} X X^H and tau = trace R, accumulated exactly as in Capon.
+ *   tau > 0:  R^ = R / tau = sum_i lambda_i v_i v_i^H, lambda_1 >= ... >= lambda_M, v_i orthonormal;
+ *             nu_d(k) = (1 / M) sum_{i > n} |v_i^H a_d|^2, n = bf_doa_set_sources (default 1).  This is the noise-subspace form, not
+ *             1 - (the signal part), which would cancel where the map peaks.
+ *   tau = 0:  nu_d(k) = 1 and every lambda_i(k) = 0.
+ *   Map:   P[s][b][d] = mu / (mu + (1 / |K|) sum_{k in K} nu_d(k)), in (0, 1]; P = 1: a_d lies in the signal subspace in every bin.
+ *          The order of the angles in a row is that of the classical incoherent wideband MUSIC spectrum 1 / sum_k a^H E_n E_n^H a for
+ *          every mu; mu (bf_doa_set_music_floor, default 1e-2) only sets the contrast that rel_floor and min_peak see.
+ *   Peak:  peak[s][b] = argmax_d P[s][b][d], the lowest d on ties.
+ *   Profile: E[s][b][i] = (1 / |K|) sum_{k in K} lambda_i(k), i = 0 .. M-1, descending; each entry in [0, 1], a row sums to at most 1
+ *          (to 1 where no bin of the block has tau = 0).
+ * Arithmetic is in double throughout.  Every sum has one fixed order: map, peak and profile bytes do not depend on how a stream is cut
+ * into calls (at block boundaries), on the internal chunking, or on the launch.  The eigendecomposition is a cyclic Jacobi iteration
+ * with a fixed number of sweeps (beamform_amd/csrc/doa_eig.hpp: 8 up to 8 microphones, 11 above), so its bytes depend on the matrix
+ * alone.  No guarantee where lambda_n - lambda_{n+1} is within 1e-6 of lambda_1: the cut between the subspaces is not defined there
+ * (the profile still holds); none for non-finite input or for a subnormal tau.  Any frames_per_block >= 1 is valid (with W < n the
+ * covariance has fewer than n nonzero eigenvalues: that is the clause above).  All of 2 .. BF_MAX_MICS microphones
+ * work.  Up to 8 the covariance triangle and the eigenvectors stay in registers, one wavefront per SIMD (keeping the eigenvectors in LDS
+ * instead would let two wavefronts share a compute unit where the registers let four: DESIGN.md); above 8 they live in device memory
+ * (correct, not tuned; the work space is part of the 256 MiB scratch).  MUSIC shares Capon's second steering table.
+ * Both setters take effect at the next bf_doa_process* call, are ignored by the other methods, and survive a method switch. */
+int bf_doa_set_sources(bf_doa *d, int n_sources);            /* the signal subspace's dimension; default 1; BF_EINVAL unless 1 <= n_sources <= n_mics - 1 */
+int bf_doa_set_music_floor(bf_doa *d, double mu);            /* default 1e-2; BF_EINVAL unless finite and 0 < mu <= 1 */
 /* n_frames: a multiple of frames_per_block (else BF_EINVAL), 0 is a no-op.  x: as bf_process_batch_device reads it (cfg.layout).
  * map: [n_streams][n_frames/W][n_angles] double, peak: [n_streams][n_frames/W] int32; either may be NULL, not both.
  * Enqueued on hip_stream, no host sync.  HIP errors: BF_EIO, text in bf_last_error(NULL). */
 int bf_doa_process_device(bf_doa *d, const float *x_dev, size_t n_frames, double *map_dev, int32_t *peak_dev, void *hip_stream);
 /* The same on host buffers (staged through the device; returns when the results are in map_host / peak_host). */
 int bf_doa_process(bf_doa *d, const float *x_host, size_t n_frames, double *map_host, int32_t *peak_host);
+/* The two calls above plus the eigenvalue profile of the MUSIC method, eig: [n_streams][n_frames/W][n_mics] double.  Any of map, peak
+ * and eig may be NULL, not all three (BF_EINVAL); a non-NULL eig on a handle whose method is not BF_DOA_MUSIC is BF_EINVAL.  With
+ * eig = NULL they are the calls above for every method; those, on a MUSIC handle, write the map and the peak only. */
+int bf_doa_process_device_eig(bf_doa *d, const float *x_dev, size_t n_frames, double *map_dev, int32_t *peak_dev, double *eig_dev,
+                              void *hip_stream);
+int bf_doa_process_eig(bf_doa *d, const float *x_host, size_t n_frames, double *map_host, int32_t *peak_host, double *eig_host);
 int bf_doa_reset(bf_doa *d);                                  /* cold start: history hop zeroed (host-synchronous) */
 void bf_doa_destroy(bf_doa *d);
 /* interf_theta_roscallback (lcmv.cpp:258-309, gss.cpp:288-339): id is 1-based.  id <= current count updates that

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bf_doa: median ms per 65 536-frame batch (8 microphones, hop 512, band 100-16 000 Hz, W = 16) at 72 and 360 angles, HIP events
 around each bf_doa_process_device call on one stream, >= 20 timed runs after warm-up.  Prints one JSON line per shape.
-  time_doa.py [runs] [--method srp_phat|capon|both] [--mics M]"""
+  time_doa.py [runs] [--method srp_phat|capon|music|both|all] [--mics M] [--frames F] [--angles D ...] [--sources N]
+both: srp_phat and capon; all: the three methods.  --sources: MUSIC's signal subspace (default 2)."""
 import argparse
 import json
 import os
@@ -16,17 +17,22 @@ from beamform_amd.params import AIRA16_XY, make_params  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("runs", nargs="?", type=int, default=20)
-ap.add_argument("--method", choices=("srp_phat", "capon", "both"), default="srp_phat")
+ap.add_argument("--method", choices=("srp_phat", "capon", "music", "both", "all"), default="srp_phat")
 ap.add_argument("--mics", type=int, default=8)
+ap.add_argument("--frames", type=int, default=65536)
+ap.add_argument("--angles", type=int, nargs="+", default=[72, 360])
+ap.add_argument("--sources", type=int, default=2)
 args = ap.parse_args()
-F, M, HOP, W = 65536, args.mics, 512, 16
+F, M, HOP, W = args.frames, args.mics, 512, 16
+METHODS = {"both": ("srp_phat", "capon"), "all": ("srp_phat", "capon", "music")}.get(args.method, (args.method,))
 runs = args.runs
 x = torch.rand((M, F * HOP), device="cuda") - 0.5
 s = torch.cuda.current_stream()
-for D, method in ((D, m) for D in (72, 360) for m in (("srp_phat", "capon") if args.method == "both" else (args.method,))):
+for D, method in ((D, m) for D in args.angles for m in METHODS):
     angles = np.linspace(-180.0, 180.0, D, endpoint=False)
     doa = Doa(make_params("das", n_mics=M, hop=HOP, mics=AIRA16_XY[:M]), angles, 100.0, 16000.0, W)
     doa.set_method(method)
+    doa.set_sources(args.sources)
     m = torch.empty((F // W, D), dtype=torch.float64, device="cuda")
     k = torch.empty((F // W,), dtype=torch.int32, device="cuda")
     for _ in range(3):
