@@ -1,7 +1,7 @@
 // doa.cpp -- bf_doa_*: SRP-PHAT, Capon and MUSIC direction-of-arrival maps over the nodes' frames (include/bfcore.h, DESIGN.md "Direction-of-arrival
-// maps").  Host side: argument checks, the steering table (SteeringSet, the weights das steers with), scratch sizing and the launch
-// sequence per chunk of frames.  Every per-frame operation runs in the gfx950 kernels (pipeline_kernels.hpp launch_stft,
-// doa_kernels.hip); there is no CPU fallback.
+// maps").  Host side: argument checks, the steering table (SteeringSet, the weights das steers with), and one batch path for the three
+// methods: doa_decide's plan (doa.hpp) sizes the scratch and the chunks, and one loop runs a chunk's launch sequence.  Every per-frame
+// operation runs in the gfx950 kernels (pipeline_kernels.hpp launch_stft, doa_kernels.hip); there is no CPU fallback.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -20,7 +20,7 @@ using namespace bf;
 
 struct bf_doa {
     int M = 0, H = 0, N = 0, S = 1, NP = 1, layout = 0, device = 0, n_cus = 256;
-    int D = 0, W = 1, klo = 0, nK = 0, G = 1;
+    int D = 0, W = 1, klo = 0, nK = 0;
     double eps = 1e-10;
     int method = BF_DOA_SRP_PHAT;                 // bf_doa_set_method
     double delta = 1e-3;                          // bf_doa_set_loading
@@ -30,15 +30,14 @@ struct bf_doa {
     const KernelSet *ks = nullptr;
     hipStream_t stream = nullptr;                 // bf_doa_process (host buffers)
     DeviceBuffer<f64x2> d_steer, d_tw;            // [bin - klo][mic][angle]; forward-transform twiddles
-    DeviceBuffer<f64x2> d_steer_capon;            // [angle][mic][bin - klo]: built when Capon or MUSIC is first selected
-    DeviceBuffer<f64x2> d_ws;                     // Capon and MUSIC above 8 microphones: the per-bin matrices of one chunk
+    DeviceBuffer<f64x2> d_steer_cov;              // [angle][mic][bin - klo]: built when Capon or MUSIC is first selected
     DeviceBuffer<double> d_win;                   // sqrt-Hann
     DeviceBuffer<float> d_hist;                   // [stream][hop before the next frame], layout as the input
-    // scratch for one chunk of `cap` frames (allocated on first use, grown up to the budget, kept)
-    long cap = 0;
+    // scratch for one chunk (ensure_scratch: grown to the largest plan so far, kept)
     DeviceBuffer<f64x2> d_Z;
-    DeviceBuffer<unsigned> d_flags;
+    DeviceBuffer<unsigned> d_flags;               // SRP-PHAT
     DeviceBuffer<double> d_part;
+    DeviceBuffer<f64x2> d_ws;                     // Capon and MUSIC above 8 microphones: the per-bin matrices
     // staging of bf_doa_process (grown on demand)
     DeviceBuffer<float> d_x;
     DeviceBuffer<double> d_map;
@@ -48,8 +47,8 @@ struct bf_doa {
 
 namespace {
 
-// spectra + partial sums of one chunk stay within about this many bytes (a chunk never holds less than one block)
-constexpr size_t kDoaChunkBytes = 256ull << 20;
+static_assert((int)kDoaSrpPhat == (int)BF_DOA_SRP_PHAT && (int)kDoaCapon == (int)BF_DOA_CAPON && (int)kDoaMusic == (int)BF_DOA_MUSIC,
+              "doa_decide takes the handle's method");
 constexpr size_t kDoaMaxTableBytes = 512ull << 20;
 
 int fail(bf_doa *d, int code, const std::string &what, hipError_t e = hipSuccess) {
@@ -69,38 +68,14 @@ int fail(bf_doa *d, int code, const std::string &what, hipError_t e = hipSuccess
         if (e_ != hipSuccess) return fail((d), BF_EIO, #call, e_);        \
     } while (0)
 
-size_t frame_bytes(const bf_doa *d) {
-    return (size_t)d->S * ((size_t)d->NP * d->N * sizeof(f64x2) + (size_t)d->G * d->D * sizeof(double) + 2 * sizeof(unsigned));
-}
-
-// frames per chunk: a multiple of W within the budget
-long chunk_budget(const bf_doa *d) {
-    long c = (long)(kDoaChunkBytes / frame_bytes(d));
-    c -= c % d->W;
-    return c < d->W ? d->W : c;
-}
-
-int ensure_scratch(bf_doa *d, long frames) {
-    if (frames <= d->cap) return BF_OK;
+// the buffers one chunk of the plan needs; they only ever grow, and a failed growth leaves a buffer empty (it grows again next time)
+int ensure_scratch(bf_doa *d, const DoaPlan &p) {
+    const size_t z = p.z_bytes / sizeof(f64x2), flags = p.flags_bytes / sizeof(unsigned), part = p.part_bytes / sizeof(double),
+                 ws = p.ws_bytes / sizeof(f64x2);
+    if (z <= d->d_Z.size() && flags <= d->d_flags.size() && part <= d->d_part.size() && ws <= d->d_ws.size()) return BF_OK;
     DOA_HIP(d, hipDeviceSynchronize());  // a batch still in flight may read the old buffers
-    d->cap = 0;
-    const size_t S = d->S;
-    if (d->d_Z.reserve(S * frames * d->NP * d->N) != hipSuccess || d->d_flags.reserve(S * (frames + 1) * 2) != hipSuccess ||
-        d->d_part.reserve((size_t)d->G * S * frames * d->D) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(d, BF_ENOMEM, "bf_doa scratch");
-    }
-    d->cap = frames;
-    return BF_OK;
-}
-
-// Capon: the buffers one chunk of the plan needs (the spectra and partial sums share the SRP-PHAT scratch, which only ever grows)
-int ensure_capon_scratch(bf_doa *d, const CaponPlan &p) {
-    const size_t z = p.z_bytes / sizeof(f64x2), part = p.part_bytes / sizeof(double), ws = p.ws_bytes / sizeof(f64x2);
-    if (z <= d->d_Z.size() && part <= d->d_part.size() && ws <= d->d_ws.size()) return BF_OK;
-    DOA_HIP(d, hipDeviceSynchronize());  // a batch still in flight may read the old buffers
-    d->cap = 0;                          // a failed growth leaves a buffer empty
-    if (d->d_Z.reserve(z) != hipSuccess || d->d_part.reserve(part) != hipSuccess || d->d_ws.reserve(ws) != hipSuccess) {
+    if (d->d_Z.reserve(z) != hipSuccess || d->d_flags.reserve(flags) != hipSuccess || d->d_part.reserve(part) != hipSuccess ||
+        d->d_ws.reserve(ws) != hipSuccess) {
         (void)hipGetLastError();
         return fail(d, BF_ENOMEM, "bf_doa scratch");
     }
@@ -138,78 +113,6 @@ int enqueue_stft(bf_doa *d, const float *xc, long n, long frames_ws, long mic_st
     front.layout = d->layout;
     front.front = chain_stft_front(d->N, switches().stft_small, switches().stft_split);
     DOA_HIP(d, d->ks->stft(front, sa, d->n_cus, s));
-    return BF_OK;
-}
-
-// One batch of the Capon or the MUSIC method: per chunk the forward transforms, the per-bin kernel (doa_capon_kernel / doa_music_kernel),
-// the reduction over the band's segments; MUSIC's eigenvalue profile takes a second reduction of the same kind.
-int cov_process_device(bf_doa *d, const float *x_dev, long F, double *map_dev, int32_t *peak_dev, double *eig_dev, hipStream_t s) {
-    const bool music = d->method == BF_DOA_MUSIC;
-    const CaponShape shape{d->M, d->S, d->N, d->D, d->nK, d->W, F};
-    const CaponPlan plan = music ? music_decide(shape) : capon_decide(shape);
-    int rc = ensure_capon_scratch(d, plan);
-    if (rc != BF_OK) return rc;
-    const int M = d->M, H = d->H;
-    const long CF = plan.chunk_frames, CB = plan.chunk_blocks;
-    const long mic_stride = d->layout == BF_PLANAR ? F * H : 1;
-    const long stream_stride = (long)M * F * H;
-    for (long c0 = 0; c0 < F; c0 += CF) {
-        const long n = std::min(CF, F - c0);
-        const float *xc = x_dev + (d->layout == BF_PLANAR ? c0 * H : c0 * (long)H * M);
-        rc = enqueue_stft(d, xc, n, CF, mic_stride, stream_stride, s);
-        if (rc != BF_OK) return rc;
-        CaponArgs ca;
-        ca.Z = d->d_Z.get();
-        ca.steer = d->d_steer_capon.get();
-        ca.part = d->d_part.get();
-        ca.ws = d->d_ws.get();
-        ca.delta = d->delta;
-        ca.frames_ws = CF;
-        ca.blocks_ws = CB;
-        ca.n_blocks = n / d->W;
-        ca.n_streams = d->S;
-        ca.n_mics = M;
-        ca.nfft = d->N;
-        ca.n_angles = d->D;
-        ca.klo = d->klo;
-        ca.n_bins = d->nK;
-        ca.n_segments = plan.segments;
-        ca.frames_per_block = d->W;
-        if (music) {
-            ca.epart = d->d_part.get() + (size_t)plan.segments * d->S * CB * d->D;  // behind the chunk's angle rows
-            ca.n_sources = d->n_sources;
-            DOA_HIP(d, launch_music(ca, plan, s));
-        } else {
-            DOA_HIP(d, launch_capon(ca, plan, s));
-        }
-        DoaReduceArgs ra;  // a block's partial sums are laid out as one frame's: the segments in order, the scale, the argmax
-        ra.part = d->d_part.get();
-        ra.map = map_dev;
-        ra.peak = peak_dev;
-        ra.scale = 1.0 / (double)d->nK;
-        ra.frames_ws = CB;
-        ra.map_blocks = F / d->W;
-        ra.block0 = c0 / d->W;
-        ra.n_blocks = n / d->W;
-        ra.n_streams = d->S;
-        ra.n_angles = d->D;
-        ra.n_segments = plan.segments;
-        ra.frames_per_block = 1;
-        if (music) {  // P = mu / (mu + sum / |K|)
-            ra.mu = d->mu;
-            ra.denom = (double)d->nK;
-        }
-        if (map_dev || peak_dev) DOA_HIP(d, launch_doa_reduce(ra, s));
-        if (eig_dev) {  // the profile: M "angles" per block, the plain mean over the band, no peak
-            ra.part = ca.epart;
-            ra.map = eig_dev;
-            ra.peak = nullptr;
-            ra.n_angles = M;
-            ra.mu = 0.0;
-            DOA_HIP(d, launch_doa_reduce(ra, s));
-        }
-        DOA_HIP(d, carry_last_hop(d->d_hist.get(), xc, n, H, M, d->S, d->layout, mic_stride, stream_stride, s));
-    }
     return BF_OK;
 }
 
@@ -262,7 +165,6 @@ int bf_doa_create(const bf_config *cfg, const double *angles_deg, int n_angles, 
     d->W = frames_per_block;
     d->klo = klo;
     d->nK = nK;
-    d->G = doa_segments(nK);
     d->ks = kernel_set(N);
 #define DOA_CREATE_HIP(call)                                  \
     do {                                                      \
@@ -316,16 +218,16 @@ int bf_doa_set_phat_floor(bf_doa *d, double eps) {
 int bf_doa_set_method(bf_doa *d, int method) {
     if (!d || (method != BF_DOA_SRP_PHAT && method != BF_DOA_CAPON && method != BF_DOA_MUSIC))
         return fail(d, BF_EINVAL, "bf_doa_set_method: NULL handle or unknown method");
-    if (method != BF_DOA_SRP_PHAT && d->d_steer_capon.size() == 0) {  // the first selection: the table with the bins innermost
+    if (method != BF_DOA_SRP_PHAT && d->d_steer_cov.size() == 0) {  // the first selection: the table with the bins innermost
         DOA_HIP(d, hipSetDevice(d->device));
-        if (d->d_steer_capon.alloc(d->d_steer.size()) != hipSuccess) {
+        if (d->d_steer_cov.alloc(d->d_steer.size()) != hipSuccess) {
             (void)hipGetLastError();
             return fail(d, BF_ENOMEM, "bf_doa_set_method: steering table");
         }
-        hipError_t e = launch_capon_table(d->d_steer.get(), d->d_steer_capon.get(), d->nK, d->M, d->D, d->stream);
+        hipError_t e = launch_doa_cov_table(d->d_steer.get(), d->d_steer_cov.get(), d->nK, d->M, d->D, d->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
         if (e != hipSuccess) {
-            d->d_steer_capon = DeviceBuffer<f64x2>();
+            d->d_steer_cov = DeviceBuffer<f64x2>();
             return fail(d, BF_EIO, "bf_doa_set_method: steering table", e);
         }
     }
@@ -370,49 +272,89 @@ int bf_doa_process_device_eig(bf_doa *d, const float *x_dev, size_t n_frames, do
     if (!x_dev) return fail(d, BF_EINVAL, "bf_doa_process_device: x is NULL");
     hipStream_t s = (hipStream_t)hip_stream;
     DOA_HIP(d, hipSetDevice(d->device));
-    if (d->method != BF_DOA_SRP_PHAT) return cov_process_device(d, x_dev, (long)n_frames, map_dev, peak_dev, eig_dev, s);
-    const long F = (long)n_frames, CF = std::min(chunk_budget(d), F);
-    int rc = ensure_scratch(d, CF);
+    const bool srp = d->method == BF_DOA_SRP_PHAT, music = d->method == BF_DOA_MUSIC;
+    const int M = d->M, H = d->H, W = d->W;
+    const long F = (long)n_frames;
+    const DoaPlan plan = doa_decide(DoaShape{M, d->S, d->N, d->D, d->nK, W, F}, d->method);
+    int rc = ensure_scratch(d, plan);
     if (rc != BF_OK) return rc;
-    const int M = d->M, H = d->H;
+    const long CF = plan.chunk_frames;
     const long mic_stride = d->layout == BF_PLANAR ? F * H : 1;
     const long stream_stride = (long)M * F * H;
-    const long nb_total = F / d->W;
+    DoaMapArgs ma;  // SRP-PHAT
+    ma.Z = d->d_Z.get();
+    ma.flags = d->d_flags.get();
+    ma.steer = d->d_steer.get();
+    ma.part = d->d_part.get();
+    ma.eps = d->eps;
+    ma.frames_ws = CF;
+    ma.n_streams = d->S;
+    ma.n_mics = M;
+    ma.nfft = d->N;
+    ma.n_angles = d->D;
+    ma.klo = d->klo;
+    ma.n_bins = d->nK;
+    DoaCovArgs ca;  // Capon and MUSIC
+    ca.Z = d->d_Z.get();
+    ca.steer = d->d_steer_cov.get();
+    ca.part = d->d_part.get();
+    ca.ws = d->d_ws.get();
+    ca.delta = d->delta;
+    ca.frames_ws = CF;
+    ca.blocks_ws = plan.chunk_blocks;
+    ca.n_streams = d->S;
+    ca.n_mics = M;
+    ca.nfft = d->N;
+    ca.n_angles = d->D;
+    ca.klo = d->klo;
+    ca.n_bins = d->nK;
+    ca.n_segments = plan.segments;
+    ca.frames_per_block = W;
+    if (music) {
+        ca.epart = d->d_part.get() + plan.epart_offset;
+        ca.n_sources = d->n_sources;
+    }
+    // SRP-PHAT keeps a row of partial sums per frame and the reduction adds a block's W rows; the covariance methods keep one per block
+    DoaReduceArgs ra;
+    ra.part = d->d_part.get();
+    ra.map = map_dev;
+    ra.peak = peak_dev;
+    ra.scale = srp ? 1.0 / ((double)W * d->nK * M * M) : 1.0 / (double)d->nK;
+    ra.frames_ws = srp ? CF : plan.chunk_blocks;
+    ra.map_blocks = F / W;
+    ra.n_streams = d->S;
+    ra.n_angles = d->D;
+    ra.n_segments = plan.segments;
+    ra.frames_per_block = srp ? W : 1;
+    if (music) {  // P = mu / (mu + sum / |K|)
+        ra.mu = d->mu;
+        ra.denom = (double)d->nK;
+    }
     for (long c0 = 0; c0 < F; c0 += CF) {
         const long n = std::min(CF, F - c0);
         const float *xc = x_dev + (d->layout == BF_PLANAR ? c0 * H : c0 * (long)H * M);
-        DOA_HIP(d, launch_doa_hop_flags(xc, d->d_hist.get(), d->d_flags.get(), n, mic_stride, stream_stride, d->S, M, H, d->layout, s));
+        if (srp) DOA_HIP(d, launch_doa_hop_flags(xc, d->d_hist.get(), d->d_flags.get(), n, mic_stride, stream_stride, d->S, M, H, d->layout, s));
         rc = enqueue_stft(d, xc, n, CF, mic_stride, stream_stride, s);
         if (rc != BF_OK) return rc;
-        DoaMapArgs ma;
-        ma.Z = d->d_Z.get();
-        ma.flags = d->d_flags.get();
-        ma.steer = d->d_steer.get();
-        ma.part = d->d_part.get();
-        ma.eps = d->eps;
-        ma.n_frames = n;
-        ma.frames_ws = CF;
-        ma.n_streams = d->S;
-        ma.n_mics = M;
-        ma.nfft = d->N;
-        ma.n_angles = d->D;
-        ma.klo = d->klo;
-        ma.n_bins = d->nK;
-        DOA_HIP(d, launch_doa_map(ma, s));
-        DoaReduceArgs ra;
-        ra.part = d->d_part.get();
-        ra.map = map_dev;
-        ra.peak = peak_dev;
-        ra.scale = 1.0 / ((double)d->W * d->nK * M * M);
-        ra.frames_ws = CF;
-        ra.map_blocks = nb_total;
-        ra.block0 = c0 / d->W;
-        ra.n_blocks = n / d->W;
-        ra.n_streams = d->S;
-        ra.n_angles = d->D;
-        ra.n_segments = d->G;
-        ra.frames_per_block = d->W;
-        DOA_HIP(d, launch_doa_reduce(ra, s));
+        if (srp) {
+            ma.n_frames = n;
+            DOA_HIP(d, launch_doa_map(ma, plan, s));
+        } else {
+            ca.n_blocks = n / W;
+            DOA_HIP(d, launch_doa_cov(ca, plan, s));
+        }
+        ra.block0 = c0 / W;
+        ra.n_blocks = n / W;
+        if (map_dev || peak_dev) DOA_HIP(d, launch_doa_reduce(ra, s));
+        if (eig_dev) {  // the profile: M "angles" per block, the plain mean over the band, no peak
+            DoaReduceArgs ea = ra;
+            ea.part = ca.epart;
+            ea.map = eig_dev;
+            ea.peak = nullptr;
+            ea.n_angles = M;
+            ea.mu = 0.0;
+            DOA_HIP(d, launch_doa_reduce(ea, s));
+        }
         // the chunk's last hop is the next chunk's (and the next call's) hop -1
         DOA_HIP(d, carry_last_hop(d->d_hist.get(), xc, n, H, M, d->S, d->layout, mic_stride, stream_stride, s));
     }

@@ -1,9 +1,9 @@
-// doa.hpp -- SRP-PHAT direction-of-arrival maps (bf_doa_*, include/bfcore.h): argument blocks and launchers of doa_kernels.hip.
-// The spectra come from the bin pipeline's forward transform (pipeline_kernels.hpp launch_stft, packed microphone pairs, halved).
+// doa.hpp -- direction-of-arrival maps (bf_doa_*, include/bfcore.h) by three methods, SRP-PHAT, Capon (MVDR) and MUSIC: the launch plan of
+// one batch, and the argument blocks and launchers of doa_kernels.hip.  The spectra come from the bin pipeline's forward transform
+// (pipeline_kernels.hpp launch_stft, packed microphone pairs, halved).
 //
-// The Capon (MVDR) map is the handle's second method (bf_doa_set_method): its launch decisions are the plain C++ of capon_decide below,
-// which the CPU suite compiles on its own (-DBF_DOA_PLAN_ONLY: no HIP header is read in front of the #ifndef).  The MUSIC map, the third
-// method, runs on the same per-bin covariances: music_decide is capon_decide with the eigenvectors' room and the profile's partial sums.
+// Every launch decision of a batch is the plain C++ of doa_decide below, which the CPU suite compiles on its own (-DBF_DOA_PLAN_ONLY: no
+// HIP header is read in front of the #ifndef).  doa.cpp sizes its scratch and cuts its chunks by the plan alone.
 #pragma once
 
 #include <cstddef>
@@ -11,71 +11,85 @@
 
 namespace bf {
 
-// ---- Capon map: one pure launch decision per batch -----------------------------------------------------------------------------------
-// One lane per (stream, block, in-band bin) problem, one wavefront per 64 consecutive bins of a block: a band segment.  The segments
-// depend on |K| only, so a block's sum over the band is formed the same way however a stream is cut into calls or chunks.
-constexpr int kCaponSegBins = 64;
-constexpr int kCaponRegMics = 8;                    // up to here the covariance and its factor live in registers
-constexpr size_t kCaponChunkBytes = 256ull << 20;   // spectra + partial sums + work space of one chunk (never less than one block)
-inline int capon_segments(int n_bins) { return (n_bins + kCaponSegBins - 1) / kCaponSegBins; }
+// ---- one pure launch plan per batch ----------------------------------------------------------------------------------------------------
+// A batch runs in chunks of whole blocks (frames_per_block frames each).  Per chunk and in-band bin the method's kernel leaves partial
+// sums over one segment of the band, which doa_reduce_kernel adds in order.  The segments depend on |K| only, so a sum over the band is
+// formed the same way however a stream is cut into calls or chunks.
+//   SRP-PHAT       doa_map_kernel: a workgroup per 64 frames x 32 angles x 48-bin segment; partial sums per (segment, stream, frame, angle)
+//   Capon, MUSIC   one lane per (stream, block, bin), one wavefront per 64-bin segment of a block: the covariance methods; partial sums per
+//                  (segment, stream, block, angle) and, MUSIC only, behind them per (segment, stream, block, eigenvalue slot)
+enum DoaMethod : int { kDoaSrpPhat = 0, kDoaCapon = 1, kDoaMusic = 2 };  // BF_DOA_SRP_PHAT, BF_DOA_CAPON, BF_DOA_MUSIC
+constexpr int kDoaSegBins = 48;                   // SRP-PHAT: in-band bins of one segment
+constexpr int kDoaCovSegBins = 64;                // the covariance methods: a wavefront's lanes
+constexpr int kDoaRegMics = 8;                    // the covariance methods: up to here the matrices of a bin live in registers
+constexpr size_t kDoaChunkBytes = 256ull << 20;   // spectra, hop flags, partial sums and work space of one chunk (never less than one block)
+// Frames of one SRP-PHAT map tile (a workgroup: 4 wavefronts x 4 lane groups x 4 frames) and angles of one tile (16 lanes x 2 angles).
+constexpr int kDoaTileFrames = 64, kDoaTileAngles = 32;
 
-enum class CaponPath : int { kRegisters = 0, kWorkspace = 1 };
+enum class DoaPath : int { kRegisters = 0, kWorkspace = 1, kFrameTiles = 2 };
 
-struct CaponShape {
+struct DoaShape {
     int n_mics, n_streams, nfft, n_angles, n_bins, frames_per_block;
     long n_frames;  // of the batch: a multiple of frames_per_block
 };
-struct CaponPlan {
-    CaponPath path;         // by microphone count alone
-    int mp;                 // kRegisters: the kernel's compile-time row count, 2 x microphone pairs (2, 4, 6, 8); kWorkspace: 0
-    int segments;           // of the band: by |K| alone
-    int ws_elems;           // kWorkspace: complex doubles per problem, the lower triangle of R with its diagonal + the solve's vector
+struct DoaPlan {
+    int method;
+    DoaPath path;           // SRP-PHAT: kFrameTiles; the covariance methods: by microphone count alone
+    int mp;                 // the kernel's compile-time size.  kRegisters: its row count, 2 x microphone pairs (2, 4, 6, 8); kFrameTiles: the
+                            // microphone count where doa_map_kernel has it (2, 4, 8, 16); 0: the count is read at run time
+    int seg_bins, segments; // of the band: by the method and |K| alone
+    int ws_elems;           // kWorkspace: complex doubles per problem (Capon: the lower triangle of R with its diagonal + the solve's vector;
+                            // MUSIC: the triangle, the frame's spectra / the columns' noise weights, the eigenvectors)
     long chunk_blocks;      // blocks of one chunk: what fits the budget, at least one, at most the batch
     long chunk_frames;      // chunk_blocks x frames_per_block
-    unsigned grid_x, grid_y;  // of a full chunk: (segments x chunk_blocks, streams); 64 lanes per workgroup
-    size_t z_bytes;         // packed pair spectra of one chunk
-    size_t part_bytes;      // partial sums of one chunk: [segment][stream][chunk block][angle] doubles
-    size_t ws_bytes;        // kWorkspace: [element][stream][chunk block][segment][lane] complex doubles; kRegisters: 0
-    size_t table_bytes;     // the steering table in the kernel's layout, [angle][mic][bin - klo] complex doubles
+    unsigned grid_x, grid_y, grid_z;  // of a full chunk.  kFrameTiles: (frame tiles x angle tiles, segments, streams), 256 lanes per
+                                      // workgroup; otherwise (segments x chunk_blocks, streams, 1), 64 lanes
+    size_t z_bytes;         // packed pair spectra of one chunk: [stream][chunk frame][pair][nfft] complex doubles
+    size_t flags_bytes;     // SRP-PHAT: [stream][chunk frame + 1][2] unsigned, the hop flags; otherwise 0
+    size_t part_bytes;      // partial sums of one chunk, doubles: [segment][stream][chunk frame or block][angle], and for MUSIC
+    long epart_offset;      // behind them, epart_offset doubles in, [segment][stream][chunk block][mic]; 0 unless MUSIC
+    size_t ws_bytes;        // kWorkspace: [element][stream][chunk block][segment][lane] complex doubles; otherwise 0
+    size_t table_bytes;     // the steering table, angles x mics x bins complex doubles (each method's kernel has its layout)
 };
 
-// ws_elems: complex doubles per problem in the work space (kWorkspace); part_cols: doubles per (segment, stream, block) of partial sums
-inline CaponPlan cov_decide(const CaponShape &c, size_t ws_elems, size_t part_cols) {
-    CaponPlan p{};
-    const size_t M = (size_t)c.n_mics, S = (size_t)c.n_streams, NP = (M + 1) / 2, W = (size_t)c.frames_per_block;
-    p.path = c.n_mics <= kCaponRegMics ? CaponPath::kRegisters : CaponPath::kWorkspace;
-    p.mp = p.path == CaponPath::kRegisters ? 2 * (int)NP : 0;
-    p.segments = capon_segments(c.n_bins);
-    p.ws_elems = p.path == CaponPath::kWorkspace ? (int)ws_elems : 0;
-    const size_t G = (size_t)p.segments;
-    const size_t z_block = W * S * NP * (size_t)c.nfft * 16, part_block = G * S * part_cols * 8;
-    const size_t ws_block = (size_t)p.ws_elems * S * G * kCaponSegBins * 16;
-    long nb = (long)(kCaponChunkBytes / (z_block + part_block + ws_block));
+inline DoaPlan doa_decide(const DoaShape &c, int method) {
+    DoaPlan p{};
+    const bool cov = method != kDoaSrpPhat, music = method == kDoaMusic;
+    const size_t M = (size_t)c.n_mics, S = (size_t)c.n_streams, NP = (M + 1) / 2, W = (size_t)c.frames_per_block, D = (size_t)c.n_angles;
+    p.method = method;
+    p.path = !cov ? DoaPath::kFrameTiles : c.n_mics <= kDoaRegMics ? DoaPath::kRegisters : DoaPath::kWorkspace;
+    if (cov) p.mp = p.path == DoaPath::kRegisters ? 2 * (int)NP : 0;
+    else p.mp = M == 2 || M == 4 || M == 8 || M == 16 ? (int)M : 0;
+    p.seg_bins = cov ? kDoaCovSegBins : kDoaSegBins;
+    p.segments = (c.n_bins + p.seg_bins - 1) / p.seg_bins;
+    if (p.path == DoaPath::kWorkspace) p.ws_elems = (int)(M * (M + 1) / 2 + M + (music ? M * M : 0));
+    // one block's share of every buffer; SRP-PHAT keeps a row of partial sums and a pair of hop flags per frame, the others a row per block
+    const size_t G = (size_t)p.segments, rows = cov ? 1 : W, cols = D + (music ? M : 0);
+    const size_t z_block = W * S * NP * (size_t)c.nfft * 16, part_block = G * S * rows * cols * 8;
+    const size_t flags_block = cov ? 0 : W * S * 2 * sizeof(unsigned);
+    const size_t ws_block = (size_t)p.ws_elems * S * G * kDoaCovSegBins * 16;
+    long nb = (long)(kDoaChunkBytes / (z_block + part_block + flags_block + ws_block));
     const long batch = c.n_frames / c.frames_per_block;
     if (nb < 1) nb = 1;
     if (nb > batch) nb = batch;
     p.chunk_blocks = nb;
     p.chunk_frames = nb * c.frames_per_block;
-    p.grid_x = (unsigned)(G * (size_t)nb);
-    p.grid_y = (unsigned)S;
+    if (cov) {
+        p.grid_x = (unsigned)(G * (size_t)nb);
+        p.grid_y = (unsigned)S;
+        p.grid_z = 1;
+    } else {
+        p.grid_x = (unsigned)(((p.chunk_frames + kDoaTileFrames - 1) / kDoaTileFrames) * ((c.n_angles + kDoaTileAngles - 1) / kDoaTileAngles));
+        p.grid_y = (unsigned)G;
+        p.grid_z = (unsigned)S;
+    }
     p.z_bytes = z_block * (size_t)nb;
+    p.flags_bytes = cov ? 0 : S * ((size_t)p.chunk_frames + 1) * 2 * sizeof(unsigned);  // hop -1 in front of the chunk's frames
     p.part_bytes = part_block * (size_t)nb;
+    p.epart_offset = music ? (long)(G * S * (size_t)nb * D) : 0;
     p.ws_bytes = ws_block * (size_t)nb;
-    p.table_bytes = (size_t)c.n_angles * M * (size_t)c.n_bins * 16;
+    p.table_bytes = D * M * (size_t)c.n_bins * 16;
     return p;
-}
-
-// Capon: the lower triangle of R with its diagonal + the solve's vector; one partial sum per angle
-inline CaponPlan capon_decide(const CaponShape &c) {
-    const size_t M = (size_t)c.n_mics;
-    return cov_decide(c, M * (M + 1) / 2 + M, (size_t)c.n_angles);
-}
-
-// MUSIC: the triangle, the frame's spectra (then the columns' noise weights), the eigenvectors; one partial sum per angle, then, behind
-// the chunk's angle rows, one per eigenvalue: [segment][stream][chunk block][angle] ++ [segment][stream][chunk block][mic]
-inline CaponPlan music_decide(const CaponShape &c) {
-    const size_t M = (size_t)c.n_mics;
-    return cov_decide(c, M * (M + 1) / 2 + M + M * M, (size_t)c.n_angles + M);
 }
 
 }  // namespace bf
@@ -90,13 +104,6 @@ inline CaponPlan music_decide(const CaponShape &c) {
 namespace bf {
 
 void set_last_error(const std::string &msg);  // capi.cpp: the text bf_last_error(NULL) returns
-
-// Frames of one map tile (a workgroup: 4 wavefronts x 4 lane groups x 4 frames) and angles of one tile (16 lanes x 2 angles).
-constexpr int kDoaTileFrames = 64, kDoaTileAngles = 32;
-// In-band bins of one segment of the band: a workgroup sums |y|^2 over one segment, the reduction kernel adds the segments in order.
-// The partition depends only on the band, so every frame's sum is formed the same way however a batch is cut.
-constexpr int kDoaSegBins = 48;
-inline int doa_segments(int n_bins) { return (n_bins + kDoaSegBins - 1) / kDoaSegBins; }
 
 struct DoaMapArgs {
     const f64x2 *Z;            // [stream][frames_ws][NP][N] packed pair spectra, stored halved (StftArgs::halve)
@@ -155,30 +162,30 @@ struct CtrackFromPicksArgs {
 // per hop of x (hops -1 .. n_frames-1, hop -1 = hist) the microphones with a nonzero sample: layout as the stft kernel reads it
 hipError_t launch_doa_hop_flags(const float *x, const float *hist, unsigned *flags, long n_frames, long mic_stride, long stream_stride_x,
                                 int n_streams, int n_mics, int hop, int layout, hipStream_t s);
-hipError_t launch_doa_map(const DoaMapArgs &a, hipStream_t s);
+hipError_t launch_doa_map(const DoaMapArgs &a, const DoaPlan &p, hipStream_t s);
 hipError_t launch_doa_reduce(const DoaReduceArgs &a, hipStream_t s);
 hipError_t launch_track_from_peaks(const TrackFromPeaksArgs &a, int n_streams, hipStream_t s);
 hipError_t launch_doa_pick(const DoaPickArgs &a, hipStream_t s);
 hipError_t launch_ctrack_from_picks(const CtrackFromPicksArgs &a, int n_streams, hipStream_t s);
 
-// ---- Capon map (doa_kernels.hip) -----------------------------------------------------------------------------------------------------
-struct CaponArgs {
-    const f64x2 *Z;            // [stream][frames_ws][NP][N] packed pair spectra, stored halved (only ratios of R enter the map)
+// ---- the covariance methods, Capon and MUSIC (doa_kernels.hip) -------------------------------------------------------------------------
+struct DoaCovArgs {
+    const f64x2 *Z;            // [stream][frames_ws][NP][N] packed pair spectra, stored halved (only ratios of R enter the maps)
     const f64x2 *steer;        // [angle][mic][bin - klo]: consecutive lanes (bins) read consecutive entries
-    double *part;              // [segment][stream][blocks_ws][angle]: sum over the segment's bins of c_d(k), lanes added in one fixed tree
+    double *part;              // [segment][stream][blocks_ws][angle]: sum over the segment's bins of c_d(k) (Capon) or nu_d(k) (MUSIC), lanes
+                               // added in one fixed tree
     f64x2 *ws;                 // kWorkspace only: [element][problem lane of the grid]
-    double delta;              // the diagonal loading
+    double delta;              // Capon: the diagonal loading
     long frames_ws, blocks_ws, n_blocks;  // blocks of this chunk
     int n_streams, n_mics, nfft, n_angles, klo, n_bins, n_segments, frames_per_block;
-    // MUSIC only (launch_music)
+    // MUSIC only
     double *epart = nullptr;   // [segment][stream][blocks_ws][mic]: sum over the segment's bins of lambda_i(k), descending
     int n_sources = 0;         // the signal subspace's dimension, 1 .. n_mics - 1
 };
 // [bin][mic][angle] -> [angle][mic][bin]
-hipError_t launch_capon_table(const f64x2 *src, f64x2 *dst, int n_bins, int n_mics, int n_angles, hipStream_t s);
-hipError_t launch_capon(const CaponArgs &a, const CaponPlan &p, hipStream_t s);
-// MUSIC: part gets sum over the segment's bins of nu_d(k), epart the eigenvalues (p: music_decide's plan)
-hipError_t launch_music(const CaponArgs &a, const CaponPlan &p, hipStream_t s);
+hipError_t launch_doa_cov_table(const f64x2 *src, f64x2 *dst, int n_bins, int n_mics, int n_angles, hipStream_t s);
+// the per-bin kernel of p.method (kDoaCapon or kDoaMusic) on the a.n_blocks blocks of one chunk
+hipError_t launch_doa_cov(const DoaCovArgs &a, const DoaPlan &p, hipStream_t s);
 
 }  // namespace bf
 #endif  // BF_DOA_PLAN_ONLY

@@ -1,4 +1,5 @@
-// doa_kernels.hip -- SRP-PHAT direction-of-arrival maps (bf_doa_*, include/bfcore.h; DESIGN.md "Direction-of-arrival maps").
+// doa_kernels.hip -- direction-of-arrival maps by SRP-PHAT, Capon and MUSIC (bf_doa_*, include/bfcore.h; DESIGN.md "Direction-of-arrival
+// maps"; the launch plan of a batch: doa_decide, doa.hpp).  SRP-PHAT:
 //
 //   P[s][b][d] = 1 / (W |K| M^2) sum_{t in block b} sum_{k in K} | sum_m conj(w_m(theta_d, k)) X^_{s,m,t}(k) |^2,  X^ = X / |X| (0 at |X| <= eps)
 //
@@ -34,6 +35,10 @@
 //                         of the eigenvalues, per angle the products with the noise columns; partial sums per (segment, stream, block,
 //                         angle) and per (segment, stream, block, eigenvalue slot).  Above 8 microphones doa_music_ws_kernel, in memory.
 //   doa_reduce_kernel     the map (mu / (mu + sum / |K|)) and the peak; a second launch for the profile (the plain mean, no peak)
+//
+// The four per-bin kernels of the two covariance methods are one skeleton: CovLane (lane -> problem), cov_accumulate (in registers, or in
+// the work space through EigMem), and for the register kernels walk_angles (prefetch, butterfly, row stores) around the method's
+// per-angle arithmetic.
 //
 // Behind the maps, without a handle: doa_pick_kernel (bf_doa_pick_device: the k strongest separated peaks of every row) and the two
 // track builders, track_from_peaks_kernel and ctrack_from_picks_kernel (one look angle, or one angle per constraint column, per frame).
@@ -445,7 +450,7 @@ __global__ __launch_bounds__(64) void ctrack_from_picks_kernel(CtrackFromPicksAr
     if (lane < C) carry[lane] = cur;
 }
 
-// ---- Capon --------------------------------------------------------------------------------------------------------------------------
+// ---- the covariance methods: Capon and MUSIC ------------------------------------------------------------------------------------------
 // The sum of a wavefront's 64 values: a butterfly, so every lane forms the same six sums in the same order whatever the launch.
 __device__ __forceinline__ double wave_sum64(double v) {
 #pragma unroll
@@ -467,6 +472,78 @@ __global__ __launch_bounds__(kDoaBlock) void capon_table_kernel(const f64x2 *src
         dst[i] = src[((long)kk * n_mics + m) * n_angles + d];
     }
 }
+
+// What the four per-bin kernels share.  One lane per (stream, block, in-band bin) problem, one wavefront per segment of a block: 64
+// consecutive bins.  In the band's last segment the lanes past the band work on its last bin and add 0 (live).
+struct CovLane {
+    long b;           // block of the chunk
+    int g, s;         // segment of the band, stream
+    int kk, k;        // bin of the band, of the transform
+    bool live;
+    const f64x2 *zr;  // the block's first frame: [frame][pair][N] packed pair rows
+    __device__ __forceinline__ CovLane(const DoaCovArgs &a, int NP) {
+        const int G = a.n_segments;
+        b = blockIdx.x / G;
+        g = (int)(blockIdx.x - b * G);
+        s = blockIdx.y;
+        kk = g * kDoaCovSegBins + (int)threadIdx.x;
+        live = kk < a.n_bins;
+        if (!live) kk = a.n_bins - 1;
+        k = a.klo + kk;
+        zr = a.Z + ((long)s * a.frames_ws + b * a.frames_per_block) * NP * a.nfft;
+    }
+    // the wavefront's row of partial sums, `cols` doubles: [segment][stream][blocks_ws][cols]
+    __device__ __forceinline__ double *sums(const DoaCovArgs &a, double *part, int cols) const {
+        return part + (((long)g * a.n_streams + s) * a.blocks_ws + b) * cols;
+    }
+};
+
+// The store of the register kernels (up to 8 microphones): the strict lower triangle, the real diagonal and, for MUSIC, V as plain arrays.
+// doa_eig.hpp indexes them with constants only, so they are registers: 64 + 128 doubles at MP = 8 (DESIGN.md has the compiler's
+// resource report).
+template <int MP>
+struct EigRegs {
+    static constexpr int NT = MP * (MP - 1) / 2;
+    double Rr[NT], Ri[NT], Rd[MP], Vr[MP * MP], Vi[MP * MP];
+    __device__ __forceinline__ double diag(int i) const { return Rd[i]; }
+    __device__ __forceinline__ void set_diag(int i, double v) { Rd[i] = v; }
+    __device__ __forceinline__ EigC low(int i, int c) const { return EigC{Rr[i * (i - 1) / 2 + c], Ri[i * (i - 1) / 2 + c]}; }
+    __device__ __forceinline__ void set_low(int i, int c, EigC z) {
+        Rr[i * (i - 1) / 2 + c] = z.re;
+        Ri[i * (i - 1) / 2 + c] = z.im;
+    }
+    __device__ __forceinline__ EigC vec(int r, int c) const { return EigC{Vr[r * MP + c], Vi[r * MP + c]}; }
+    __device__ __forceinline__ void set_vec(int r, int c, EigC z) {
+        Vr[r * MP + c] = z.re;
+        Vi[r * MP + c] = z.im;
+    }
+};
+
+// The store of the work-space kernels (more than 8 microphones): the same per-lane algorithms in memory, [element][lane of the grid], so
+// consecutive lanes touch consecutive addresses.  Elements: the lower triangle with its diagonal (idx(i, c) = i (i + 1) / 2 + c); at
+// NT + i the frame's spectra, later the solve's vector (Capon) or per column (noise weight, rank) (MUSIC); MUSIC's eigenvectors V_rc at
+// NT + M + r M + c.  Correct, not tuned.
+struct EigMem {
+    f64x2 *A;
+    long stride;
+    int M, NT;
+    __device__ __forceinline__ explicit EigMem(const DoaCovArgs &a)
+        : A(a.ws + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 64 + threadIdx.x), stride((long)gridDim.y * gridDim.x * 64), M(a.n_mics),
+          NT(a.n_mics * (a.n_mics + 1) / 2) {}
+    __device__ __forceinline__ f64x2 &at(int e) const { return A[(long)e * stride]; }
+    __device__ __forceinline__ double diag(int i) const { return at(i * (i + 1) / 2 + i).x; }
+    __device__ __forceinline__ void set_diag(int i, double v) { at(i * (i + 1) / 2 + i).x = v; }
+    __device__ __forceinline__ EigC low(int i, int c) const {
+        const f64x2 z = at(i * (i + 1) / 2 + c);
+        return EigC{z.x, z.y};
+    }
+    __device__ __forceinline__ void set_low(int i, int c, EigC z) { at(i * (i + 1) / 2 + c) = f64x2{z.re, z.im}; }
+    __device__ __forceinline__ EigC vec(int r, int c) const {
+        const f64x2 z = at(NT + M + r * M + c);
+        return EigC{z.x, z.y};
+    }
+    __device__ __forceinline__ void set_vec(int r, int c, EigC z) { at(NT + M + r * M + c) = f64x2{z.re, z.im}; }
+};
 
 // R = sum over the block's W frames (ascending) of X X^H for one bin: the strict lower triangle and the real diagonal, in registers.
 // zr: the block's first frame, [frame][pair][N] packed pair rows.  A zero partner channel (an odd count's last pair) is never formed.
@@ -502,23 +579,71 @@ __device__ __forceinline__ void cov_accumulate(const f64x2 *zr, int k, int N, in
     }
 }
 
+// The same sum in the work space: the triangle with its diagonal, the frame's spectra parked at NT + m.
+__device__ __forceinline__ void cov_accumulate(const EigMem &e, const f64x2 *zr, int k, int N, int W) {
+    const int M = e.M, NP = (M + 1) / 2, NT = e.NT;
+    for (int t = 0; t < NT; ++t) e.at(t) = f64x2{0.0, 0.0};
+    for (int t = 0; t < W; ++t, zr += (long)NP * N) {
+        for (int m = 0; m < M; ++m) {  // never the zero partner of an odd count: m < M
+            const f64x2 *pr = zr + (long)(m >> 1) * N;
+            e.at(NT + m) = unpack_mic(pr[k], pr[N - k], m & 1);
+        }
+        for (int i = 0; i < M; ++i) {
+            const f64x2 x = e.at(NT + i);
+            for (int c = 0; c < i; ++c) {
+                const f64x2 y = e.at(NT + c);
+                f64x2 &r = e.at(i * (i + 1) / 2 + c);
+                r = f64x2{fma(x.y, y.y, fma(x.x, y.x, r.x)), fma(-x.x, y.y, fma(x.y, y.x, r.y))};
+            }
+            f64x2 &r = e.at(i * (i + 1) / 2 + i);
+            r.x = fma(x.y, x.y, fma(x.x, x.x, r.x));
+        }
+    }
+}
+
+// The register kernels' walk over the angles.  The next angle's steering column is requested in front of this angle's arithmetic;
+// value(ur, ui) gives the lane's value for the column in (ur, ui), which it may overwrite; the wavefront's 64 values are added in the one
+// butterfly, lane d mod 64 keeps angle d's sum, and 64 angles' sums leave in one row of stores.
+template <int MP, class Value>
+__device__ __forceinline__ void walk_angles(const DoaCovArgs &a, const CovLane &p, Value value) {
+    const int lane = threadIdx.x, M = a.n_mics, D = a.n_angles, nK = a.n_bins;
+    const f64x2 *st = a.steer + p.kk;
+    double *row = p.sums(a, a.part, D);
+    f64x2 an[MP];
+#pragma unroll
+    for (int m = 0; m < MP; ++m) an[m] = m < M ? st[(long)m * nK] : f64x2{0.0, 0.0};
+    double keep = 0.0;
+    for (int d = 0; d < D; ++d) {
+        double ur[MP], ui[MP];
+#pragma unroll
+        for (int m = 0; m < MP; ++m) {
+            ur[m] = an[m].x;
+            ui[m] = an[m].y;
+        }
+        const int dn = d + 1 < D ? d + 1 : d;
+#pragma unroll
+        for (int m = 0; m < MP; ++m)
+            if (m < M) an[m] = st[((long)dn * M + m) * nK];
+        const double sum = wave_sum64(value(ur, ui));
+        if (lane == (d & 63)) keep = sum;
+        if ((d & 63) == 63 || d == D - 1) {
+            const int dd = (d & ~63) + lane;
+            if (dd <= d) row[dd] = keep;
+        }
+    }
+}
+
+// ---- Capon --------------------------------------------------------------------------------------------------------------------------
 // MP = 2 x microphone pairs (2, 4, 6, 8).  An odd count's last pair has a zero partner channel: its spectrum (the transform's rounding
 // residue) is never formed -- row MP-1 of R~ is pinned to the identity and its steering entry to 0, so it adds nothing to |u|^2.
 // The strict lower triangle of R (then of L) and the real diagonal (then 1 / L_ii) are registers; every loop below is unrolled.
 template <int MP>
-__global__ __launch_bounds__(64) void doa_capon_kernel(CaponArgs a) {
-    constexpr int NT = MP * (MP - 1) / 2, NP = MP / 2;
-    const int lane = threadIdx.x, G = a.n_segments;
-    const long b = blockIdx.x / G;
-    const int g = (int)(blockIdx.x - b * G), s = blockIdx.y;
-    const int M = a.n_mics, N = a.nfft, D = a.n_angles, W = a.frames_per_block, nK = a.n_bins;
-    int kk = g * kCaponSegBins + lane;
-    const bool live = kk < nK;  // the band's last segment: the lanes past the band work on its last bin and add 0
-    if (!live) kk = nK - 1;
-    const int k = a.klo + kk;
-    const f64x2 *zr = a.Z + ((long)s * a.frames_ws + b * W) * NP * N;
+__global__ __launch_bounds__(64) void doa_capon_kernel(DoaCovArgs a) {
+    constexpr int NT = MP * (MP - 1) / 2;
+    const CovLane p(a, MP / 2);
+    const int M = a.n_mics;
     double Rr[NT > 0 ? NT : 1], Ri[NT > 0 ? NT : 1], Rd[MP];
-    cov_accumulate<MP>(zr, k, N, M, W, Rr, Ri, Rd);
+    cov_accumulate<MP>(p.zr, p.k, a.nfft, M, a.frames_per_block, Rr, Ri, Rd);
     double tau = 0.0;
 #pragma unroll
     for (int i = 0; i < MP; ++i) tau += Rd[i];  // (the pinned row's entry is an exact 0)
@@ -554,23 +679,8 @@ __global__ __launch_bounds__(64) void doa_capon_kernel(CaponArgs a) {
         }
     }
     const double cnum = (double)M / (1.0 + a.delta);
-    const f64x2 *st = a.steer + kk;
-    double *row = a.part + (((long)g * a.n_streams + s) * a.blocks_ws + b) * D;
-    f64x2 an[MP];  // the next angle's steering column: requested in front of this angle's substitution
-#pragma unroll
-    for (int m = 0; m < MP; ++m) an[m] = m < M ? st[(long)m * nK] : f64x2{0.0, 0.0};
-    double keep = 0.0;
-    for (int d = 0; d < D; ++d) {
-        double ur[MP], ui[MP];
-#pragma unroll
-        for (int m = 0; m < MP; ++m) {
-            ur[m] = an[m].x;
-            ui[m] = an[m].y;
-        }
-        const int dn = d + 1 < D ? d + 1 : d;
-#pragma unroll
-        for (int m = 0; m < MP; ++m)
-            if (m < M) an[m] = st[((long)dn * M + m) * nK];
+    const bool counts = p.live && ok;
+    walk_angles<MP>(a, p, [&](double (&ur)[MP], double (&ui)[MP]) {
         double q = 0.0;
 #pragma unroll
         for (int i = 0; i < MP; ++i) {  // u_i = (a_i - sum_{c < i} L_ic u_c) / L_ii
@@ -584,94 +694,65 @@ __global__ __launch_bounds__(64) void doa_capon_kernel(CaponArgs a) {
             ui[i] *= Rd[i];
             q = fma(ui[i], ui[i], fma(ur[i], ur[i], q));
         }
-        const double sum = wave_sum64(live && ok ? cnum / q : 0.0);
-        if (lane == (d & 63)) keep = sum;  // 64 angles' sums leave in one row of stores
-        if ((d & 63) == 63 || d == D - 1) {
-            const int dd = (d & ~63) + lane;
-            if (dd <= d) row[dd] = keep;
-        }
-    }
+        const double c = cnum / q;  // formed on every lane: the choice below is a select, not a branch round the solve
+        return counts ? c : 0.0;
+    });
 }
 
-// More than 8 microphones: the same per-lane algorithm with the lower triangle (diagonal included, idx(i, c) = i (i + 1) / 2 + c) and the
-// frame's spectra / the solve's vector (NT + i) in memory, [element][lane of the grid]: consecutive lanes, consecutive addresses.
-__global__ __launch_bounds__(64) void doa_capon_ws_kernel(CaponArgs a) {
-    const int lane = threadIdx.x, G = a.n_segments;
-    const long b = blockIdx.x / G;
-    const int g = (int)(blockIdx.x - b * G), s = blockIdx.y;
-    const int M = a.n_mics, NP = (M + 1) / 2, N = a.nfft, D = a.n_angles, W = a.frames_per_block, nK = a.n_bins, NT = M * (M + 1) / 2;
-    int kk = g * kCaponSegBins + lane;
-    const bool live = kk < nK;
-    if (!live) kk = nK - 1;
-    const int k = a.klo + kk;
-    const long stride = (long)gridDim.y * gridDim.x * 64;
-    f64x2 *A = a.ws + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 64 + lane;
-    auto at = [&](int e) -> f64x2 & { return A[(long)e * stride]; };
-    const f64x2 *zr = a.Z + ((long)s * a.frames_ws + b * W) * NP * N;
-    for (int e = 0; e < NT; ++e) at(e) = f64x2{0.0, 0.0};
-    for (int t = 0; t < W; ++t, zr += (long)NP * N) {
-        for (int m = 0; m < M; ++m) {  // never the zero partner of an odd count: m < M
-            const f64x2 *pr = zr + (long)(m >> 1) * N;
-            at(NT + m) = unpack_mic(pr[k], pr[N - k], m & 1);
-        }
-        for (int i = 0; i < M; ++i) {
-            const f64x2 x = at(NT + i);
-            for (int c = 0; c < i; ++c) {
-                const f64x2 y = at(NT + c);
-                f64x2 &r = at(i * (i + 1) / 2 + c);
-                r = f64x2{fma(x.y, y.y, fma(x.x, y.x, r.x)), fma(-x.x, y.y, fma(x.y, y.x, r.y))};
-            }
-            f64x2 &r = at(i * (i + 1) / 2 + i);
-            r.x = fma(x.y, x.y, fma(x.x, x.x, r.x));
-        }
-    }
+// More than 8 microphones: the same per-lane algorithm through the work space, the solve's vector at NT + i.
+__global__ __launch_bounds__(64) void doa_capon_ws_kernel(DoaCovArgs a) {
+    const int lane = threadIdx.x, M = a.n_mics, D = a.n_angles, nK = a.n_bins;
+    const CovLane p(a, (M + 1) / 2);
+    EigMem e(a);
+    const int NT = e.NT;
+    cov_accumulate(e, p.zr, p.k, a.nfft, a.frames_per_block);
     double tau = 0.0;
-    for (int i = 0; i < M; ++i) tau += at(i * (i + 1) / 2 + i).x;
+    for (int i = 0; i < M; ++i) tau += e.diag(i);
     const bool ok = tau > 0.0;
     const double inv = ok ? 1.0 / tau : 0.0, load = a.delta / (double)M;
     for (int i = 0; i < M; ++i) {
         for (int c = 0; c < i; ++c) {
-            f64x2 &r = at(i * (i + 1) / 2 + c);
+            f64x2 &r = e.at(i * (i + 1) / 2 + c);
             r = f64x2{r.x * inv, r.y * inv};
         }
-        f64x2 &r = at(i * (i + 1) / 2 + i);
+        f64x2 &r = e.at(i * (i + 1) / 2 + i);
         r.x = fma(r.x, inv, load);
     }
     for (int j = 0; j < M; ++j) {
-        const double rinv = 1.0 / sqrt(at(j * (j + 1) / 2 + j).x);
-        at(j * (j + 1) / 2 + j).x = rinv;
+        const double rinv = 1.0 / sqrt(e.at(j * (j + 1) / 2 + j).x);
+        e.at(j * (j + 1) / 2 + j).x = rinv;
         for (int i = j + 1; i < M; ++i) {
-            f64x2 &r = at(i * (i + 1) / 2 + j);
+            f64x2 &r = e.at(i * (i + 1) / 2 + j);
             r = f64x2{r.x * rinv, r.y * rinv};
         }
         for (int c = j + 1; c < M; ++c) {
-            const f64x2 l = at(c * (c + 1) / 2 + j);
-            f64x2 &dg = at(c * (c + 1) / 2 + c);
+            const f64x2 l = e.at(c * (c + 1) / 2 + j);
+            f64x2 &dg = e.at(c * (c + 1) / 2 + c);
             dg.x = fma(-l.y, l.y, fma(-l.x, l.x, dg.x));
             for (int i = c + 1; i < M; ++i) {
-                const f64x2 p = at(i * (i + 1) / 2 + j);
-                f64x2 &r = at(i * (i + 1) / 2 + c);
-                r = f64x2{fma(-p.y, l.y, fma(-p.x, l.x, r.x)), fma(p.x, l.y, fma(-p.y, l.x, r.y))};
+                const f64x2 pv = e.at(i * (i + 1) / 2 + j);
+                f64x2 &r = e.at(i * (i + 1) / 2 + c);
+                r = f64x2{fma(-pv.y, l.y, fma(-pv.x, l.x, r.x)), fma(pv.x, l.y, fma(-pv.y, l.x, r.y))};
             }
         }
     }
     const double cnum = (double)M / (1.0 + a.delta);
-    const f64x2 *st = a.steer + kk;
-    double *row = a.part + (((long)g * a.n_streams + s) * a.blocks_ws + b) * D;
+    const f64x2 *st = a.steer + p.kk;
+    double *row = p.sums(a, a.part, D);
     for (int d = 0; d < D; ++d) {
         double q = 0.0;
         for (int i = 0; i < M; ++i) {
             f64x2 u = st[((long)d * M + i) * nK];
             for (int c = 0; c < i; ++c) {
-                const f64x2 l = at(i * (i + 1) / 2 + c), v = at(NT + c);
+                const f64x2 l = e.at(i * (i + 1) / 2 + c), v = e.at(NT + c);
                 u = f64x2{fma(l.y, v.y, fma(-l.x, v.x, u.x)), fma(-l.y, v.x, fma(-l.x, v.y, u.y))};
             }
-            const double rinv = at(i * (i + 1) / 2 + i).x;
+            const double rinv = e.at(i * (i + 1) / 2 + i).x;
             u = f64x2{u.x * rinv, u.y * rinv};
-            at(NT + i) = u;
+            e.at(NT + i) = u;
             q = fma(u.y, u.y, fma(u.x, u.x, q));
         }
-        const double sum = wave_sum64(live && ok ? cnum / q : 0.0);
+        const double sum = wave_sum64(p.live && ok ? cnum / q : 0.0);
         if (lane == 0) row[d] = sum;
     }
 }
@@ -679,43 +760,17 @@ __global__ __launch_bounds__(64) void doa_capon_ws_kernel(CaponArgs a) {
 // ---- MUSIC --------------------------------------------------------------------------------------------------------------------------
 // The Capon kernels' lane per (stream, block, bin) and covariance; then R / tau = V diag(lambda) V^H by doa_eig.hpp's Jacobi sweeps (a fixed
 // count: no lane waits for another), the eigenvalues' ranks by comparisons, and per angle nu = 1 / M sum_{noise i} |v_i^H a_d|^2.
-// The store of the register kernels: the strict lower triangle, the real diagonal and V as plain arrays.  doa_eig.hpp indexes them with
-// constants only, so they are registers: 64 + 128 doubles at MP = 8 (DESIGN.md has the compiler's resource report).
-template <int MP>
-struct EigRegs {
-    static constexpr int NT = MP * (MP - 1) / 2;
-    double Rr[NT], Ri[NT], Rd[MP], Vr[MP * MP], Vi[MP * MP];
-    __device__ __forceinline__ double diag(int i) const { return Rd[i]; }
-    __device__ __forceinline__ void set_diag(int i, double v) { Rd[i] = v; }
-    __device__ __forceinline__ EigC low(int i, int c) const { return EigC{Rr[i * (i - 1) / 2 + c], Ri[i * (i - 1) / 2 + c]}; }
-    __device__ __forceinline__ void set_low(int i, int c, EigC z) {
-        Rr[i * (i - 1) / 2 + c] = z.re;
-        Ri[i * (i - 1) / 2 + c] = z.im;
-    }
-    __device__ __forceinline__ EigC vec(int r, int c) const { return EigC{Vr[r * MP + c], Vi[r * MP + c]}; }
-    __device__ __forceinline__ void set_vec(int r, int c, EigC z) {
-        Vr[r * MP + c] = z.re;
-        Vi[r * MP + c] = z.im;
-    }
-};
-
+//
 // MP = 2 x microphone pairs (2, 4, 6, 8).  An odd count's zero partner channel is never formed: row and column MP-1 are zero with -1 on
 // the diagonal and a zero steering entry.  No rotation touches them (their pivots are exact zeros), the eigenvalue -1 sorts last, so
 // its vector e_{MP-1} is always noise (n_sources <= M - 1 <= MP - 2) and adds |e^H a|^2 = 0.
 template <int MP>
-__global__ __launch_bounds__(64) void doa_music_kernel(CaponArgs a) {
-    constexpr int NT = MP * (MP - 1) / 2, NP = MP / 2;
-    const int lane = threadIdx.x, G = a.n_segments;
-    const long b = blockIdx.x / G;
-    const int g = (int)(blockIdx.x - b * G), s = blockIdx.y;
-    const int M = a.n_mics, N = a.nfft, D = a.n_angles, W = a.frames_per_block, nK = a.n_bins;
-    int kk = g * kCaponSegBins + lane;
-    const bool live = kk < nK;  // the band's last segment: the lanes past the band work on its last bin and add 0
-    if (!live) kk = nK - 1;
-    const int k = a.klo + kk;
-    const f64x2 *zr = a.Z + ((long)s * a.frames_ws + b * W) * NP * N;
+__global__ __launch_bounds__(64) void doa_music_kernel(DoaCovArgs a) {
+    constexpr int NT = MP * (MP - 1) / 2;
+    const CovLane p(a, MP / 2);
+    const int lane = threadIdx.x, M = a.n_mics;
     EigRegs<MP> e;
-    cov_accumulate<MP>(zr, k, N, M, W, e.Rr, e.Ri, e.Rd);
+    cov_accumulate<MP>(p.zr, p.k, a.nfft, M, a.frames_per_block, e.Rr, e.Ri, e.Rd);
     double tau = 0.0;
 #pragma unroll
     for (int i = 0; i < MP; ++i) tau += e.Rd[i];  // (the pinned row's entry is an exact 0)
@@ -743,28 +798,12 @@ __global__ __launch_bounds__(64) void doa_music_kernel(CaponArgs a) {
         double v = 0.0;
 #pragma unroll
         for (int i = 0; i < MP; ++i) v = rk[i] == j ? fmax(e.Rd[i], 0.0) : v;
-        const double sum = wave_sum64(live && ok ? v : 0.0);
+        const double sum = wave_sum64(p.live && ok ? v : 0.0);
         if (lane == j) keep = sum;
     }
-    if (lane < M) a.epart[(((long)g * a.n_streams + s) * a.blocks_ws + b) * M + lane] = keep;
+    if (lane < M) p.sums(a, a.epart, M)[lane] = keep;
 
-    const f64x2 *st = a.steer + kk;
-    double *row = a.part + (((long)g * a.n_streams + s) * a.blocks_ws + b) * D;
-    f64x2 an[MP];  // the next angle's steering column: requested in front of this angle's products
-#pragma unroll
-    for (int m = 0; m < MP; ++m) an[m] = m < M ? st[(long)m * nK] : f64x2{0.0, 0.0};
-    keep = 0.0;
-    for (int d = 0; d < D; ++d) {
-        double ur[MP], ui[MP];
-#pragma unroll
-        for (int m = 0; m < MP; ++m) {
-            ur[m] = an[m].x;
-            ui[m] = an[m].y;
-        }
-        const int dn = d + 1 < D ? d + 1 : d;
-#pragma unroll
-        for (int m = 0; m < MP; ++m)
-            if (m < M) an[m] = st[((long)dn * M + m) * nK];
+    walk_angles<MP>(a, p, [&](double (&ur)[MP], double (&ui)[MP]) {
         double q = 0.0;
 #pragma unroll
         for (int i = 0; i < MP; ++i) {  // y = v_i^H a = sum_m conj(V_mi) a_m
@@ -776,66 +815,19 @@ __global__ __launch_bounds__(64) void doa_music_kernel(CaponArgs a) {
             }
             q = fma(wgt[i], fma(yi, yi, yr * yr), q);
         }
-        const double nu = ok ? q / (double)M : 1.0;
-        const double sum = wave_sum64(live ? nu : 0.0);
-        if (lane == (d & 63)) keep = sum;  // 64 angles' sums leave in one row of stores
-        if ((d & 63) == 63 || d == D - 1) {
-            const int dd = (d & ~63) + lane;
-            if (dd <= d) row[dd] = keep;
-        }
-    }
+        const double quot = q / (double)M;  // formed on every lane: the choices below are selects, not a branch round the products
+        const double nu = ok ? quot : 1.0;
+        return p.live ? nu : 0.0;
+    });
 }
 
-// More than 8 microphones: the same per-lane algorithm in memory, [element][lane of the grid] as doa_capon_ws_kernel.  Elements: the lower
-// triangle with its diagonal (idx(i, c) = i (i + 1) / 2 + c), the frame's spectra -- later per column (noise weight, rank) -- at NT + i,
-// the eigenvectors V_rc at NT + M + r M + c.  doa_eig.hpp's solver runs on it through the store below.  Correct, not tuned.
-struct EigMem {
-    f64x2 *A;
-    long stride;
-    int M, NT;
-    __device__ __forceinline__ f64x2 &at(int e) const { return A[(long)e * stride]; }
-    __device__ __forceinline__ double diag(int i) const { return at(i * (i + 1) / 2 + i).x; }
-    __device__ __forceinline__ void set_diag(int i, double v) { at(i * (i + 1) / 2 + i).x = v; }
-    __device__ __forceinline__ EigC low(int i, int c) const {
-        const f64x2 z = at(i * (i + 1) / 2 + c);
-        return EigC{z.x, z.y};
-    }
-    __device__ __forceinline__ void set_low(int i, int c, EigC z) { at(i * (i + 1) / 2 + c) = f64x2{z.re, z.im}; }
-    __device__ __forceinline__ EigC vec(int r, int c) const {
-        const f64x2 z = at(NT + M + r * M + c);
-        return EigC{z.x, z.y};
-    }
-    __device__ __forceinline__ void set_vec(int r, int c, EigC z) { at(NT + M + r * M + c) = f64x2{z.re, z.im}; }
-};
-
-__global__ __launch_bounds__(64) void doa_music_ws_kernel(CaponArgs a) {
-    const int lane = threadIdx.x, G = a.n_segments;
-    const long b = blockIdx.x / G;
-    const int g = (int)(blockIdx.x - b * G), s = blockIdx.y;
-    const int M = a.n_mics, NP = (M + 1) / 2, N = a.nfft, D = a.n_angles, W = a.frames_per_block, nK = a.n_bins, NT = M * (M + 1) / 2;
-    int kk = g * kCaponSegBins + lane;
-    const bool live = kk < nK;
-    if (!live) kk = nK - 1;
-    const int k = a.klo + kk;
-    EigMem e{a.ws + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 64 + lane, (long)gridDim.y * gridDim.x * 64, M, NT};
-    const f64x2 *zr = a.Z + ((long)s * a.frames_ws + b * W) * NP * N;
-    for (int t = 0; t < NT; ++t) e.at(t) = f64x2{0.0, 0.0};
-    for (int t = 0; t < W; ++t, zr += (long)NP * N) {
-        for (int m = 0; m < M; ++m) {  // never the zero partner of an odd count: m < M
-            const f64x2 *pr = zr + (long)(m >> 1) * N;
-            e.at(NT + m) = unpack_mic(pr[k], pr[N - k], m & 1);
-        }
-        for (int i = 0; i < M; ++i) {
-            const f64x2 x = e.at(NT + i);
-            for (int c = 0; c < i; ++c) {
-                const f64x2 y = e.at(NT + c);
-                f64x2 &r = e.at(i * (i + 1) / 2 + c);
-                r = f64x2{fma(x.y, y.y, fma(x.x, y.x, r.x)), fma(-x.x, y.y, fma(x.y, y.x, r.y))};
-            }
-            f64x2 &r = e.at(i * (i + 1) / 2 + i);
-            r.x = fma(x.y, x.y, fma(x.x, x.x, r.x));
-        }
-    }
+// More than 8 microphones: doa_eig.hpp's solver runs on the work space through EigMem; at NT + i per column (noise weight, rank).
+__global__ __launch_bounds__(64) void doa_music_ws_kernel(DoaCovArgs a) {
+    const int lane = threadIdx.x, M = a.n_mics, D = a.n_angles, nK = a.n_bins;
+    const CovLane p(a, (M + 1) / 2);
+    EigMem e(a);
+    const int NT = e.NT;
+    cov_accumulate(e, p.zr, p.k, a.nfft, a.frames_per_block);
     double tau = 0.0;
     for (int i = 0; i < M; ++i) tau += e.diag(i);
     const bool ok = tau > 0.0;
@@ -849,16 +841,16 @@ __global__ __launch_bounds__(64) void doa_music_ws_kernel(CaponArgs a) {
         const int r = eig_rank<0>(e, M, i);
         e.at(NT + i) = f64x2{r >= a.n_sources ? 1.0 : 0.0, (double)r};
     }
-    double *erow = a.epart + (((long)g * a.n_streams + s) * a.blocks_ws + b) * M;
+    double *erow = p.sums(a, a.epart, M);
     for (int j = 0; j < M; ++j) {
         double v = 0.0;
         for (int i = 0; i < M; ++i)
             if ((int)e.at(NT + i).y == j) v = fmax(e.diag(i), 0.0);
-        const double sum = wave_sum64(live && ok ? v : 0.0);
+        const double sum = wave_sum64(p.live && ok ? v : 0.0);
         if (lane == 0) erow[j] = sum;
     }
-    const f64x2 *st = a.steer + kk;
-    double *row = a.part + (((long)g * a.n_streams + s) * a.blocks_ws + b) * D;
+    const f64x2 *st = a.steer + p.kk;
+    double *row = p.sums(a, a.part, D);
     for (int d = 0; d < D; ++d) {
         double q = 0.0;
         for (int i = 0; i < M; ++i) {
@@ -872,48 +864,42 @@ __global__ __launch_bounds__(64) void doa_music_ws_kernel(CaponArgs a) {
             q = fma(e.at(NT + i).x, fma(yi, yi, yr * yr), q);
         }
         const double nu = ok ? q / (double)M : 1.0;
-        const double sum = wave_sum64(live ? nu : 0.0);
+        const double sum = wave_sum64(p.live ? nu : 0.0);
         if (lane == 0) row[d] = sum;
     }
 }
 
+// the register kernel of the method at one compile-time size
+template <int MP>
+void launch_cov_regs(const DoaCovArgs &a, bool music, dim3 grid, hipStream_t s) {
+    if (music) BF_LAUNCH(doa_music_kernel<MP>, grid, dim3(64), 0, s, a);
+    else BF_LAUNCH(doa_capon_kernel<MP>, grid, dim3(64), 0, s, a);
+}
+
 }  // namespace
 
-hipError_t launch_capon_table(const f64x2 *src, f64x2 *dst, int n_bins, int n_mics, int n_angles, hipStream_t s) {
+hipError_t launch_doa_cov_table(const f64x2 *src, f64x2 *dst, int n_bins, int n_mics, int n_angles, hipStream_t s) {
     const long n = (long)n_bins * n_mics * n_angles;
     const long blocks = (n + kDoaBlock - 1) / kDoaBlock;
     BF_LAUNCH(capon_table_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(kDoaBlock), 0, s, src, dst, n_bins, n_mics, n_angles);
     return hipGetLastError();
 }
 
-hipError_t launch_capon(const CaponArgs &a, const CaponPlan &p, hipStream_t s) {
-    if (a.n_blocks < 1 || a.n_blocks > p.chunk_blocks || a.n_segments != p.segments) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)(a.n_blocks * p.segments), p.grid_y);
-    switch (p.mp) {
-        case 2: BF_LAUNCH(doa_capon_kernel<2>, grid, dim3(64), 0, s, a); break;
-        case 4: BF_LAUNCH(doa_capon_kernel<4>, grid, dim3(64), 0, s, a); break;
-        case 6: BF_LAUNCH(doa_capon_kernel<6>, grid, dim3(64), 0, s, a); break;
-        case 8: BF_LAUNCH(doa_capon_kernel<8>, grid, dim3(64), 0, s, a); break;
-        default:
-            if (p.path != CaponPath::kWorkspace || !a.ws) return hipErrorInvalidValue;
-            BF_LAUNCH(doa_capon_ws_kernel, grid, dim3(64), 0, s, a);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_music(const CaponArgs &a, const CaponPlan &p, hipStream_t s) {
-    if (a.n_blocks < 1 || a.n_blocks > p.chunk_blocks || a.n_segments != p.segments || !a.epart || a.n_sources < 1 ||
-        a.n_sources > a.n_mics - 1)
+hipError_t launch_doa_cov(const DoaCovArgs &a, const DoaPlan &p, hipStream_t s) {
+    const bool music = p.method == kDoaMusic;
+    if ((!music && p.method != kDoaCapon) || a.n_blocks < 1 || a.n_blocks > p.chunk_blocks || a.n_segments != p.segments)
         return hipErrorInvalidValue;
+    if (music && (!a.epart || a.n_sources < 1 || a.n_sources > a.n_mics - 1)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(a.n_blocks * p.segments), p.grid_y);
     switch (p.mp) {
-        case 2: BF_LAUNCH(doa_music_kernel<2>, grid, dim3(64), 0, s, a); break;
-        case 4: BF_LAUNCH(doa_music_kernel<4>, grid, dim3(64), 0, s, a); break;
-        case 6: BF_LAUNCH(doa_music_kernel<6>, grid, dim3(64), 0, s, a); break;
-        case 8: BF_LAUNCH(doa_music_kernel<8>, grid, dim3(64), 0, s, a); break;
+        case 2: launch_cov_regs<2>(a, music, grid, s); break;
+        case 4: launch_cov_regs<4>(a, music, grid, s); break;
+        case 6: launch_cov_regs<6>(a, music, grid, s); break;
+        case 8: launch_cov_regs<8>(a, music, grid, s); break;
         default:
-            if (p.path != CaponPath::kWorkspace || !a.ws) return hipErrorInvalidValue;
-            BF_LAUNCH(doa_music_ws_kernel, grid, dim3(64), 0, s, a);
+            if (p.path != DoaPath::kWorkspace || !a.ws) return hipErrorInvalidValue;
+            if (music) BF_LAUNCH(doa_music_ws_kernel, grid, dim3(64), 0, s, a);
+            else BF_LAUNCH(doa_capon_ws_kernel, grid, dim3(64), 0, s, a);
     }
     return hipGetLastError();
 }
@@ -925,17 +911,16 @@ hipError_t launch_doa_hop_flags(const float *x, const float *hist, unsigned *fla
     return hipGetLastError();
 }
 
-hipError_t launch_doa_map(const DoaMapArgs &a, hipStream_t s) {
+hipError_t launch_doa_map(const DoaMapArgs &a, const DoaPlan &p, hipStream_t s) {
+    if (p.path != DoaPath::kFrameTiles || a.n_frames < 1 || a.n_frames > p.chunk_frames || a.n_mics < 1 || a.n_mics > 32) return hipErrorInvalidValue;
     const long n_ft = (a.n_frames + kDoaTileFrames - 1) / kDoaTileFrames, n_at = (a.n_angles + kDoaTileAngles - 1) / kDoaTileAngles;
-    const dim3 grid((unsigned)(n_ft * n_at), (unsigned)doa_segments(a.n_bins), (unsigned)a.n_streams);
-    switch (a.n_mics) {
+    const dim3 grid((unsigned)(n_ft * n_at), p.grid_y, p.grid_z);
+    switch (p.mp) {
         case 2: BF_LAUNCH(doa_map_kernel<2>, grid, dim3(kDoaBlock), 0, s, a); break;
         case 4: BF_LAUNCH(doa_map_kernel<4>, grid, dim3(kDoaBlock), 0, s, a); break;
         case 8: BF_LAUNCH(doa_map_kernel<8>, grid, dim3(kDoaBlock), 0, s, a); break;
         case 16: BF_LAUNCH(doa_map_kernel<16>, grid, dim3(kDoaBlock), 0, s, a); break;
-        default:
-            if (a.n_mics < 1 || a.n_mics > 32) return hipErrorInvalidValue;
-            BF_LAUNCH(doa_map_kernel<0>, grid, dim3(kDoaBlock), 0, s, a);
+        default: BF_LAUNCH(doa_map_kernel<0>, grid, dim3(kDoaBlock), 0, s, a);
     }
     return hipGetLastError();
 }

@@ -1,7 +1,7 @@
 """Capon (MVDR) direction-of-arrival maps on the host: the two new symbols and their refusals, the float64 restatement
 (tests/doa_capon_ref.py) against its loop-nest twin and a closed form, the greedy source picker, the multi-source claim on
-restatement maps (where the SRP-PHAT map shows the strongest source's sidelobes), and the launch decisions of
-beamform_amd/csrc/doa.hpp, compiled here with g++."""
+restatement maps (where the SRP-PHAT map shows the strongest source's sidelobes), and the launch plan of the three methods
+(doa_decide, beamform_amd/csrc/doa.hpp), compiled here with g++."""
 import ctypes as C
 import os
 import re
@@ -138,30 +138,33 @@ PLAN_SRC = r"""
 #define BF_DOA_PLAN_ONLY
 #include "%s"
 using namespace bf;
-extern "C" void plan(int M, int S, int nfft, int D, int nK, int W, long long F, long long *o) {
-    const CaponPlan p = capon_decide(CaponShape{M, S, nfft, D, nK, W, (long)F});
-    const long long v[] = {(long long)p.path, p.mp, p.segments, p.ws_elems, p.chunk_blocks, p.chunk_frames, p.grid_x, p.grid_y,
-                           (long long)p.z_bytes, (long long)p.part_bytes, (long long)p.ws_bytes, (long long)p.table_bytes};
+extern "C" void plan(int method, int M, int S, int nfft, int D, int nK, int W, long long F, long long *o) {
+    const DoaPlan p = doa_decide(DoaShape{M, S, nfft, D, nK, W, (long)F}, method);
+    const long long v[] = {p.method, (long long)p.path, p.mp, p.seg_bins, p.segments, p.ws_elems, p.chunk_blocks, p.chunk_frames,
+                           p.grid_x, p.grid_y, p.grid_z, (long long)p.z_bytes, (long long)p.flags_bytes, (long long)p.part_bytes,
+                           p.epart_offset, (long long)p.ws_bytes, (long long)p.table_bytes};
     for (unsigned i = 0; i < sizeof(v) / sizeof(v[0]); ++i) o[i] = v[i];
 }
 """
-FIELDS = "path mp segments ws_elems chunk_blocks chunk_frames grid_x grid_y z_bytes part_bytes ws_bytes table_bytes".split()
+FIELDS = ("method path mp seg_bins segments ws_elems chunk_blocks chunk_frames grid_x grid_y grid_z z_bytes flags_bytes part_bytes "
+          "epart_offset ws_bytes table_bytes").split()
+SRP_PHAT, CAPON, MUSIC = 0, 1, 2
 
 
 @pytest.fixture(scope="module")
 def plan(tmp_path_factory):
-    d = tmp_path_factory.mktemp("capon_plan")
+    d = tmp_path_factory.mktemp("doa_plan")
     src, so = os.path.join(d, "plan.cpp"), os.path.join(d, "libplan.so")
     with open(src, "w") as f:
         f.write(PLAN_SRC % os.path.join(ROOT, "beamform_amd", "csrc", "doa.hpp"))
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", "-o", so, src])
     lib = C.CDLL(so)
-    lib.plan.argtypes = [C.c_int] * 6 + [C.c_longlong, C.POINTER(C.c_longlong)]
+    lib.plan.argtypes = [C.c_int] * 7 + [C.c_longlong, C.POINTER(C.c_longlong)]
     lib.plan.restype = None
 
-    def run(M, S, nfft, D, nK, W, F):
+    def run(method, M, S, nfft, D, nK, W, F):
         o = (C.c_longlong * len(FIELDS))()
-        lib.plan(M, S, nfft, D, nK, W, F, o)
+        lib.plan(method, M, S, nfft, D, nK, W, F, o)
         return dict(zip(FIELDS, o))
     return run
 
@@ -171,27 +174,57 @@ def test_launch_plan(plan):
     for M in range(2, 33):
         for S, nfft, D, nK, W, F in ((1, 1024, 72, 339, 16, 65536), (3, 1024, 360, 509, 8, 32), (1, 256, 1, 37, 1, 1 << 20),
                                      (1, 4096, 8, 64, 4, 4), (2, 8192, 1024, 65, 1, 3), (1, 128, 72, 128, 5000, 10000)):
-            p = plan(M, S, nfft, D, nK, W, F)
-            case = (M, S, nfft, D, nK, W, F)
             NP = (M + 1) // 2
-            # the path by the microphone count alone
-            assert p["path"] == (0 if M <= 8 else 1), case
-            assert p["mp"] == (2 * NP if M <= 8 else 0), case
-            assert p["ws_elems"] == (0 if M <= 8 else M * (M + 1) // 2 + M), case
-            # the segments by |K| alone: 64 bins each
-            G = -(-nK // 64)
-            assert p["segments"] == G, case
-            # a chunk: whole blocks within the budget, at least one, at most the batch
-            per_block = W * S * NP * nfft * 16 + G * S * D * 8 + p["ws_elems"] * S * G * 64 * 16
-            nb = max(1, min(budget // per_block, F // W))
-            assert p["chunk_blocks"] == nb and p["chunk_frames"] == nb * W, case
-            assert (p["grid_x"], p["grid_y"]) == (G * nb, S), case
-            assert p["z_bytes"] == nb * W * S * NP * nfft * 16, case
-            assert p["part_bytes"] == G * S * nb * D * 8, case
-            assert p["ws_bytes"] == p["ws_elems"] * S * nb * G * 64 * 16, case
+            # Capon and MUSIC: the work space per problem and the partial-sum columns differ, nothing else
+            for method, ws_elems, cols in ((CAPON, M * (M + 1) // 2 + M, D), (MUSIC, M * (M + 1) // 2 + M + M * M, D + M)):
+                p = plan(method, M, S, nfft, D, nK, W, F)
+                case = (method, M, S, nfft, D, nK, W, F)
+                assert p["method"] == method, case
+                # the path by the microphone count alone
+                assert p["path"] == (0 if M <= 8 else 1), case
+                assert p["mp"] == (2 * NP if M <= 8 else 0), case
+                assert p["ws_elems"] == (0 if M <= 8 else ws_elems), case
+                # the segments by |K| alone: 64 bins each
+                G = -(-nK // 64)
+                assert (p["seg_bins"], p["segments"]) == (64, G), case
+                # a chunk: whole blocks within the budget, at least one, at most the batch
+                per_block = W * S * NP * nfft * 16 + G * S * cols * 8 + p["ws_elems"] * S * G * 64 * 16
+                nb = max(1, min(budget // per_block, F // W))
+                assert p["chunk_blocks"] == nb and p["chunk_frames"] == nb * W, case
+                assert (p["grid_x"], p["grid_y"], p["grid_z"]) == (G * nb, S, 1), case
+                assert p["z_bytes"] == nb * W * S * NP * nfft * 16, case
+                assert p["flags_bytes"] == 0, case
+                assert p["part_bytes"] == G * S * nb * cols * 8, case
+                assert p["ws_bytes"] == p["ws_elems"] * S * nb * G * 64 * 16, case
+                assert p["table_bytes"] == D * M * nK * 16, case
+                if nb > 1:
+                    assert p["z_bytes"] + p["part_bytes"] + p["ws_bytes"] <= budget, case
+                # MUSIC's eigenvalue sums lie behind the chunk's angle rows, and part_bytes covers both regions
+                assert p["epart_offset"] == (G * S * nb * D if method == MUSIC else 0), case
+                if method == MUSIC:
+                    assert p["part_bytes"] == (p["epart_offset"] + G * S * nb * M) * 8, case
+            # SRP-PHAT: frames within the budget, rounded down to whole blocks, at least one block, at most the batch
+            p = plan(SRP_PHAT, M, S, nfft, D, nK, W, F)
+            case = (SRP_PHAT, M, S, nfft, D, nK, W, F)
+            G48 = -(-nK // 48)
+            assert (p["method"], p["path"], p["ws_elems"], p["ws_bytes"], p["epart_offset"]) == (SRP_PHAT, 2, 0, 0, 0), case
+            assert p["mp"] == (M if M in (2, 4, 8, 16) else 0), case
+            assert (p["seg_bins"], p["segments"]) == (48, G48), case
+            per_frame = S * (NP * nfft * 16 + G48 * D * 8 + 8)
+            CF = budget // per_frame
+            CF = min(max(CF - CF % W, W), F)
+            assert p["chunk_frames"] == CF and p["chunk_blocks"] * W == CF, case
+            assert (p["grid_x"], p["grid_y"], p["grid_z"]) == (-(-CF // 64) * -(-D // 32), G48, S), case
+            assert p["z_bytes"] == S * CF * NP * nfft * 16, case
+            assert p["flags_bytes"] == S * (CF + 1) * 2 * 4, case
+            assert p["part_bytes"] == G48 * S * CF * D * 8, case
             assert p["table_bytes"] == D * M * nK * 16, case
-            if nb > 1:
-                assert p["z_bytes"] + p["part_bytes"] + p["ws_bytes"] <= budget, case
-    # the segment count does not move with anything but |K|
-    assert {plan(M, S, 1024, D, 130, W, 64 * W)["segments"] for M in (2, 8, 9, 32) for S in (1, 4) for D in (1, 360) for W in (1, 16)} == {3}
-    assert [plan(8, 1, 1024, 72, nK, 16, 64)["segments"] for nK in (1, 63, 64, 65, 128, 129, 511)] == [1, 1, 1, 2, 2, 3, 8]
+            if CF > W:
+                assert CF * per_frame <= budget, case
+    # the segment count does not move with anything but the method and |K|
+    for method in (SRP_PHAT, CAPON, MUSIC):  # 130 bins: three segments of 48 as of 64
+        assert {plan(method, M, S, 1024, D, 130, W, 64 * W)["segments"]
+                for M in (2, 8, 9, 32) for S in (1, 4) for D in (1, 360) for W in (1, 16)} == {3}
+    assert [plan(CAPON, 8, 1, 1024, 72, nK, 16, 64)["segments"] for nK in (1, 63, 64, 65, 128, 129, 511)] == [1, 1, 1, 2, 2, 3, 8]
+    assert [plan(MUSIC, 8, 1, 1024, 72, nK, 16, 64)["segments"] for nK in (1, 63, 64, 65, 128, 129, 511)] == [1, 1, 1, 2, 2, 3, 8]
+    assert [plan(SRP_PHAT, 8, 1, 1024, 72, nK, 16, 64)["segments"] for nK in (1, 47, 48, 49, 96, 97, 511)] == [1, 1, 1, 2, 2, 3, 11]
