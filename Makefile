@@ -63,9 +63,10 @@ dispatch-table: $(LIB)
 
 emul:
 	g++ -O2 -std=c++17 -fPIC -shared -o tests/host_emul/libemul.so tests/host_emul/emul.cpp
+	g++ -O2 -std=c++17 -ffp-contract=off -fPIC -shared -o tests/host_emul_sep/libemul_sep.so tests/host_emul_sep/emul_sep.cpp
 
 clean:
-	rm -rf build $(LIB) tests/host_emul/libemul.so examples/file_node examples/theta_scan examples/shard_node examples/separate_node examples/follow_sources_node
+	rm -rf build $(LIB) tests/host_emul/libemul.so tests/host_emul_sep/libemul_sep.so examples/file_node examples/theta_scan examples/shard_node examples/separate_node examples/follow_sources_node
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle emul ubench clean dispatch-table

@@ -321,29 +321,34 @@ __global__ __launch_bounds__(kBlock) void das_f64_w64_kernel(DasF64Args a, int f
 // 0-3 slept a third of the kernel waiting for 4-7, i.e. a third of the time each SIMD ran ONE wavefront).  So (i) frame pairs are taken
 // from an LDS counter -- the fast wavefronts end up with ~72 % of them and all eight finish together -- and (ii) the overlap-add
 // between pairs never waits for the other side's arithmetic (claim_boundary below).
-// Gains: ce_m is Hermitian, so only bins 0 .. 512 are kept: [mic][row 2 g + k3, k3 < 2][65] = ce_m[64 g + 256 k3 + c], c = 0 .. 64.
-// Register 4 g + k3 of lane l is bin l + 64 g + 256 k3: k3 < 2 reads row (g, k3) column l; k3 >= 2 reads row (3 - g, 3 - k3) column
-// 64 - l (N - k = (64 - l) + 64 (3 - g) + 256 (3 - k3)) and conjugates through the FMA signs.  The 65th column is the bin behind the row.
+// Gains: a das weight row is a delay, so ce_m[k] / N = A[k1] B[k2] C[k3] over the digits k = k1 + 16 k2 + 256 k3 (geometry.hpp
+// das_sep_gains_w64_f64, which also checks it against the per-bin table).  B[k2] is inside the slot's own tw2' table; register 4 g + k3 of
+// lane l (bin l + 64 g + 256 k3, k1 = l & 15) takes G[k3][k1] = A[k1] C[k3], the Hermitian mirror of the upper half folded into G[2] and
+// G[3]: four ds_read_b128 per microphone for 14 registers.  Registers 13 and 2 hold the bins 511 and 512, 513, where the reference's
+// frequency vector breaks the ramp: they read an entry per lane, the per-bin table's own divided by B.
 // read-back of a parked half: non-temporal (used once); a plain load moved 4 % more bytes across the fabric (-DBF_PARK_PLAIN for A/B runs)
 #ifdef BF_PARK_PLAIN
 #define BF_PARK_LD(p) (*(const volatile float *)(p))
 #else
 #define BF_PARK_LD(p) __builtin_nontemporal_load(p)
 #endif
-constexpr int kGRow = 65;                                  // complex entries per gain row
-constexpr int kGMic = 8 * kGRow;                           // per microphone
+// LDS map of the frame-pair kernels, 119 KB: tw1 rows 1 .. 15 + tw2' (16.1 KB; tw2' serves the backward transform only), 8 exchange planes
+// (65 KB), 7 slots of delay-structured gains (28.4 KB: per slot G 1 KB, the two exception rows 2 KB, the slot's tw2' B 1.1 KB), boundary
+// and ring states, window rows (9 KB).
+constexpr int kGSlot = kDasSepMic;                         // complex entries per slot: geometry.hpp das_sep_gains_w64_f64
 constexpr int kSlots = 64;                                 // boundary states in flight (<= 2 pairs per wavefront are): a ring
 constexpr int kTwP = 2 * (960 + 4 * kTw2RowW64Rot);        // tw1 rows k1 = 1 .. 15 (row 0 is all ones and never read) + tw2'
 constexpr int pTw = 0;
 constexpr int pPlane = kTwP;
 constexpr int pGain = pPlane + kWaves * kPlaneD;
-constexpr int pFlag = pGain + 7 * kGMic * 2;       // microphones 1 .. 7 (microphone 0 has no gains: below)
+constexpr int pFlag = pGain + 7 * kGSlot * 2;      // microphones 1 .. 7 (microphone 0 has no gains: below)
 constexpr int kRingR = 32;                                 // [sample][mic] input: shared hop slots of the block's ring (16 pairs), + one private slot per wavefront
 constexpr int kRingSlots = kRingR + kWaves;
 constexpr int pRing = pFlag + (kSlots + 4) / 2;          // kSlots ints + the 64-bit work word, padded to 16 bytes; then kRingR slot states
 constexpr int pWin = pRing + kRingR / 2;
 constexpr int kLdsP = pWin + 64 * kWinRow;
-static_assert(kLdsP * 8 <= 160 * 1024, "LDS");
+static_assert(kLdsP * 8 <= 120 * 1024, "LDS");
+static_assert(kGSlot <= kBlock, "a slot's table is copied into LDS in one trip of the block");
 static_assert((pGain & 1) == 0 && (pWin & 1) == 0, "16-byte alignment");
 
 
@@ -546,14 +551,16 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
     double *wcol = plane + w64_col_rot(lane);
     double *row16 = plane + (lane & 15) * kRS + 16 * (lane >> 4);
     const double *wrow = lds + pWin + lane * kWinRow;
-    // the gain rows lie beyond the 64 KB a DS offset field reaches: a per-lane base register that hipcc cannot split back into
-    // "lane + constant" (it then spent 16 v_add_u32 per microphone on the sixteen row addresses)
+    // the gain slots lie beyond the 64 KB a DS offset field reaches: per-lane base registers that hipcc cannot split back into
+    // "lane + constant" (it then spends a v_add_u32 per address).  gG0: G[.][lane & 15]; gE0: the exception rows' entry of this lane;
+    // gT0: row lane >> 4 of the slot's tw2' B -- all of slot 0
     typedef double cxa __attribute__((ext_vector_type(2)));  // 16-byte aligned (re, im): one ds_read_b128
     typedef const __attribute__((address_space(3))) cxa *lds_gain_t;
-    unsigned gd0 = (unsigned)(size_t)(lds_gain_t)(s_gain + lane);
-    asm volatile("" : "+v"(gd0));
-    gd0 &= ~15u;  // (what the asm hid: 16-byte alignment)
-    const unsigned g_mirror = 2u * (unsigned)(size_t)(lds_gain_t)s_gain + 1024u;  // byte address of column 64 - lane = g_mirror - that of column lane
+    unsigned gG0 = (unsigned)(size_t)(lds_gain_t)(s_gain + kDasSepG + (lane & 15));
+    unsigned gE0 = (unsigned)(size_t)(lds_gain_t)(s_gain + kDasSepE13 + lane);
+    unsigned gT0 = (unsigned)(size_t)(lds_gain_t)(s_gain + kDasSepTw2 + (lane >> 4) * kTw2RowW64Rot);
+    asm volatile("" : "+v"(gG0), "+v"(gE0), "+v"(gT0));
+    gG0 &= ~15u; gE0 &= ~15u; gT0 &= ~15u;  // (what the asm hid: 16-byte alignment)
 
     // hops tA - 1 (hop -1 = the carried hop), tA, tA + 1 of one microphone: register j <- sample 64 j + lane of the hop.  h1 = hop tA.
     float n0[8], n1[8], n2[8];
@@ -728,10 +735,9 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
         f64x2 *ltw = reinterpret_cast<f64x2 *>(lds + pTw), *lg = reinterpret_cast<f64x2 *>(lds + pGain);
 #pragma unroll 4
         for (int i = tid; i < kTwP / 2; i += kBlock) ltw[i] = tw2[i];
-        for (int k = 0; k < NT; ++k) {  // the gains of slot k's microphone (microphone 0 has none: below)
-            const f64x2 *g2 = a.gains_mic + a.slot_mic[k] * kGMic;
-#pragma unroll 2
-            for (int i = tid; i < kGMic; i += kBlock) lg[k * kGMic + i] = g2[i];
+        for (int k = 0; k < NT; ++k) {  // the gains of slot k's microphone (microphone 0 has none: below): 260 entries, one trip
+            const f64x2 *g2 = a.gains_sep + a.slot_mic[k] * kGSlot;
+            if (tid < kGSlot) lg[k * kGSlot + tid] = g2[tid];
         }
 #pragma unroll 2
         for (int i = tid; i < 1024; i += kBlock) lds[pWin + (i & 63) * kWinRow + (i >> 6)] = a.win[i];
@@ -868,35 +874,38 @@ __device__ __forceinline__ void das_f64_pair_body(const DasF64Args &a, const Das
             mul_tw<false, 9, 16>(re, im, tw);
             BF_STAGE();
             T1_fwd(re, im, wcol, row16);
-            load_tw2<1, 9>(tw, s_tw2, lane);
+            // the slot's own second-pass twiddles: tw2' with the gain's B[k2] inside (row lane >> 4, entries of 16 bytes)
+            const lds_gain_t gt = (lds_gain_t)(size_t)(gT0 + (unsigned)(k * kGSlot * 16));
+#pragma unroll
+            for (int i = 1; i < 9; ++i) { const cxa v = gt[brev4(i)]; tw[i - 1] = cx<double>{v.x, v.y}; }
             BF_STAGE();
             fft16_core<double, -1, true>(re, im);
             BF_STAGE();
-            load_tw2<9, 16>(tw, s_tw2, lane);
+#pragma unroll
+            for (int i = 9; i < 16; ++i) { const cxa v = gt[brev4(i)]; tw[i - 1] = cx<double>{v.x, v.y}; }
             BF_STAGE();
             mul_tw<false, 1, 9>(re, im, tw);
             BF_STAGE();
             mul_tw<false, 9, 16>(re, im, tw);
             BF_STAGE();
             w64_T2_any<true>(re, im, row16 - 16 * (lane >> 4), lane >> 4);
-            cxa g[16];
-            const lds_gain_t gd = (lds_gain_t)(size_t)(gd0 + (unsigned)(k * kGMic * 16));  // k3 < 2: row (g, k3), column lane
-            const lds_gain_t gm = (lds_gain_t)(size_t)((g_mirror + (unsigned)(2 * k * kGMic * 16)) - (gd0 + (unsigned)(k * kGMic * 16)));  // k3 >= 2: row (3 - g, 3 - k3), column 64 - lane, conjugated
+            // G[k3] for the registers 4 g + k3, and this lane's entries of the two exception rows (registers 13 and 2)
+            cxa g[4], g13, g2;
+            const lds_gain_t gd = (lds_gain_t)(size_t)(gG0 + (unsigned)(k * kGSlot * 16));
+            const lds_gain_t ge = (lds_gain_t)(size_t)(gE0 + (unsigned)(k * kGSlot * 16));
             BF_STAGE();
 #pragma unroll
-            for (int r = 0; r < 8; ++r)
-                g[r] = (r & 3) < 2 ? gd[(2 * (r >> 2) + (r & 3)) * kGRow] : gm[(2 * (3 - (r >> 2)) + 3 - (r & 3)) * kGRow];
+            for (int k3 = 0; k3 < 4; ++k3) g[k3] = gd[16 * k3];  // lands during the 4-point transforms
+            g13 = ge[0];
+            g2 = ge[kDasSepE2 - kDasSepE13];
             BF_STAGE();
             w64_fwd_p3<double>(re, im);
             BF_STAGE();
 #pragma unroll
-            for (int r = 8; r < 16; ++r)
-                g[r] = (r & 3) < 2 ? gd[(2 * (r >> 2) + (r & 3)) * kGRow] : gm[(2 * (3 - (r >> 2)) + 3 - (r & 3)) * kGRow];
-            BF_STAGE();
-#pragma unroll
             for (int r = 0; r < 16; ++r) {
                 if (r == 8) BF_STAGE();
-                const double gx = g[r].x, gy = (r & 3) < 2 ? g[r].y : -g[r].y;
+                const cxa gr = r == 13 ? g13 : r == 2 ? g2 : g[r & 3];
+                const double gx = gr.x, gy = gr.y;
                 if constexpr (FIRST) {  // the first microphone starts the sum
                     Sr[r] = fma(-gy, im[r], gx * re[r]);
                     Si[r] = fma(gy, re[r], gx * im[r]);

@@ -275,6 +275,86 @@ inline std::vector<f64x2> das_mic_gains_w64_f64(const SteeringSet &s, int n_mics
     return T;
 }
 
+// The same gains in the DELAY-STRUCTURED form the frame-pair kernels read.  A das weight row is a pure delay (das.cpp:27-45): away from
+// the bins 511 .. 513, where the reference's frequency vector breaks the ramp (quirk Q1), ce_m[k] / N = e^(i phi k) / (M N) for k < 512 and
+// e^(i phi (k - N)) / (M N) above, so over the transform's index digits k = k1 + 16 k2 + 256 k3 the gain is a product A[k1] B[k2] C[k3].
+// B rides on the second pass's twiddles (a 4-point transform of the third pass has one k2), and register 4 g + k3 of lane l -- bin
+// l + 64 g + 256 k3, k1 = l & 15 -- needs G[k3][k1] = A[k1] C[k3] only: four values per lane instead of sixteen.  Per microphone,
+// kDasSepMic entries:
+//   [0, 64)      G[k3][k1], 1 / (M N) and, for k3 >= 2, the Hermitian mirror's e^(-i phi N) folded in
+//   [64, 128)    register 13 (bins 448 + l, with bin 511) per lane: the TABLE's own entry divided by B[12 + (l >> 4)]
+//   [128, 192)   register 2 (bins 512 + l, with bins 512 and 513) per lane: the table's (mirrored) entry divided by B[l >> 4]
+//   [192, 260)   tw2'[b][k2] B[k2] in the layout of twiddle_table_w64_rot's second part (that table's doubles times B)
+// The factors are read off the steering table itself -- A[k1] = conj w[k1], B[k2] = conj w[16 k2], C[1] = conj w[256], C[3] = conj w[768],
+// C[2] = C[3]^2 -- and multiplied in long double, every entry rounded once.
+// The check.  ok = for every microphone 1 .. M - 1 and every bin the product the kernel forms (G, or the exception entry, times B) is
+// within `bound` of das_mic_gains_w64_f64's entry (its mirror's conjugate above bin 512), relative to 1 / (M N); `worst` = the largest
+// deviation seen.  The bound: the reference evaluates every weight as exp(-i 2 pi f tau) in double, where the phase carries four
+// roundings (<= 4 u |phase|, u = 2^-53) and exp, the Hermitian mean and the two divisions about 4 u more; a product of three such factors
+// carries the phase errors of bins k1, 16 k2 and 256 k3 (together below 4 u x 1.5 x the largest phase) beside the table entry's own:
+// (16 + 12 phi_max) u with phi_max = 512 |phi|, |phi| taken from bin 1.  "A few ulp" therefore means a few ulp per radian of the row's
+// largest phase: on a 0.2 m array that is 1e-13, where 1.8e-14 is the worst seen.  The factor of six between them is the distance between
+// every rounding falling the same way (the bound) and what roundings do on average (the measurement); the bound is the a-priori one on
+// purpose, so that no geometry or look angle of a real das table is ever sent to the chain by it, and it still sits an order of magnitude
+// below the smallest defect that would show in the float output (1e-12 moves a sample in 1e5).  A table that is not a delay in some row
+// misses it by orders of magnitude and goes to the chain (DasF64Shape::tables).
+// (The kernel multiplies no twiddle at k2 = 0: it takes B[0] = conj w[0] for 1.  That is exact for das -- f[0] = 0 -- and the check
+// multiplies by the table's B[0], so a row with any other w[0] fails it.)
+constexpr int kDasSepG = 0, kDasSepE13 = 64, kDasSepE2 = 128, kDasSepTw2 = 192, kDasSepMic = 192 + 4 * kTw2RowW64Rot;
+struct DasSepTables {
+    std::vector<f64x2> t;  // [microphone][kDasSepMic]
+    bool ok = false;
+    double bound = 0.0, worst = 0.0;  // relative to 1 / (M N), over every microphone
+};
+inline DasSepTables das_sep_gains_w64_f64(const SteeringSet &s, const std::vector<f64x2> &T /* das_mic_gains_w64_f64(s, n_mics_alloc) */, int n_mics_alloc) {
+    typedef std::complex<long double> cl;
+    const int N = s.n_fft, M = s.n_mics;
+    DasSepTables r;
+    r.t.assign((size_t)n_mics_alloc * kDasSepMic, f64x2{0, 0});
+    if (N != 1024 || M < 1) return r;
+    const long double scale = 1.0L / ((long double)M * (long double)N);
+    const std::vector<f64x2> tw2 = twiddle_table_w64_rot();
+    auto wl = [&](int k, int m) { const cplxd w = s.at(k, m, 0); return cl((long double)w.real(), -(long double)w.imag()); };  // conj w
+    auto tab = [&](int m, int k) -> cl {  // the table's gain of bin k (bins above 512: the mirror's conjugate, as the kernel read it)
+        const int kk = k <= 512 ? k : N - k, k3 = kk >= 512 ? 1 : (kk >> 8) & 1, g = kk >= 512 ? 3 : (kk >> 6) & 3, c = kk - 64 * g - 256 * k3;
+        const f64x2 v = T[((size_t)m * kDasMicGainRows + 2 * g + k3) * kDasMicGainRow + c];
+        return cl((long double)v.x, k <= 512 ? (long double)v.y : -(long double)v.y);
+    };
+    auto rnd = [](cl v) { return f64x2{(double)v.real(), (double)v.imag()}; };
+    r.ok = true;
+    for (int m = 1; m < M && m < n_mics_alloc; ++m) {
+        f64x2 *t = r.t.data() + (size_t)m * kDasSepMic;
+        cl B[16];
+        for (int k2 = 0; k2 < 16; ++k2) B[k2] = wl(16 * k2, m);
+        const cl C3 = wl(768, m), C[4] = {cl(1.0L, 0.0L), wl(256, m), C3 * C3, C3};
+        for (int k3 = 0; k3 < 4; ++k3)
+            for (int k1 = 0; k1 < 16; ++k1) t[kDasSepG + 16 * k3 + k1] = rnd(wl(k1, m) * C[k3] * scale);
+        for (int l = 0; l < 64; ++l) {
+            t[kDasSepE13 + l] = rnd(tab(m, 448 + l) / B[12 + (l >> 4)]);
+            t[kDasSepE2 + l] = rnd(tab(m, 512 + l) / B[l >> 4]);
+        }
+        for (int b = 0; b < 4; ++b)
+            for (int k2 = 0; k2 < 16; ++k2) {
+                // (the shared table's own doubles times B: a row of ones leaves the transform's twiddles bit for bit what they were)
+                const f64x2 w2 = tw2[1024 + b * kTw2RowW64Rot + k2];
+                t[kDasSepTw2 + b * kTw2RowW64Rot + k2] = rnd(cl((long double)w2.x, (long double)w2.y) * B[k2]);
+            }
+        const cplxd w1 = s.at(1, m, 0);
+        const double bound = (16.0 + 12.0 * 512.0 * std::fabs(std::atan2(w1.imag(), w1.real()))) * 0x1p-53;
+        if (bound > r.bound) r.bound = bound;
+        for (int k = 0; k < N; ++k) {
+            const int k1 = k & 15, k2 = (k >> 4) & 15, k3 = k >> 8, l = k & 63, reg = 4 * (k2 >> 2) + k3;
+            const f64x2 gv = reg == 13 ? t[kDasSepE13 + l] : reg == 2 ? t[kDasSepE2 + l] : t[kDasSepG + 16 * k3 + k1];
+            const f64x2 bv = rnd(B[k2]);  // (the kernel's B sits inside its twiddle; what is checked is the gain, not the twiddle's rounding)
+            const cl d = cl((long double)gv.x, (long double)gv.y) * cl((long double)bv.x, (long double)bv.y) - tab(m, k);
+            const double dev = (double)(std::abs(d) / scale);
+            if (!(dev <= bound)) r.ok = false;  // (a NaN fails)
+            if (dev > r.worst || dev != dev) r.worst = dev;
+        }
+    }
+    return r;
+}
+
 // What das_f64_pair_kernel needs to know about a das steering table beyond its gains (pipeline_kernels.hpp DasF64Args of the same names):
 // whether microphone 0's weight row is identically 1 (das.cpp:33-38 writes it once; quirk Q3 can leave it 0) -- only then may the kernel
 // skip that microphone's transform -- and its walk over the others: slot k transforms microphone slot_mic[k], k < n_tr, and extra_mic

@@ -108,7 +108,7 @@ class BinPipelineImpl : public Engine {
         for (auto &b : d_steer_) ENGINE_HIP(b.alloc(steer_elems()));
         if (das_one_launch_shape()) {
             for (auto &t : das_) ENGINE_HIP(t.gains_w64.alloc((size_t)4 * 1024));
-            for (auto &t : das_) ENGINE_HIP(t.gains_mic.alloc((size_t)8 * kDasMicGainRows * kDasMicGainRow));
+            for (auto &t : das_) ENGINE_HIP(t.gains_sep.alloc((size_t)8 * kDasSepMic));
             ENGINE_HIP(d_das_sched_.alloc(das_f64_sched_ws_bytes()));  // das_f64_pair_kernel's work queue (chunk table + counter)
         }
         if (N_ == 1024) ENGINE_HIP(d_tw_w64_.upload(twiddle_table_w64_rot()));
@@ -157,12 +157,17 @@ class BinPipelineImpl : public Engine {
                     }
         const int nxt = steer_cur_ ^ 1;
         std::vector<f64x2> dg64, dgm;  // das in double in one launch: the gains of the (single) look direction and its summary, same double buffering
+        DasSepTables sep;              // (lives until the synchronisation below, like the others: the copies read pageable memory)
         if (das_one_launch_shape()) {
             dg64 = das_pair_gains_w64_f64(das_pair_gains_t<f64x2>(dirs[0], 4), 4);
             dgm = das_mic_gains_w64_f64(dirs[0], 8);
             das_[nxt].slots = das_f64_slots(dirs[0]);
+            // the delay-structured form the frame-pair kernels read, checked entry by entry against dgm: a row that is not a delay sends
+            // the batches of this table to the chain (run_das_one_launch: DasF64Shape::tables)
+            sep = das_sep_gains_w64_f64(dirs[0], dgm, 8);
+            das_[nxt].sep_ok = sep.ok; das_[nxt].sep_bound = sep.bound; das_[nxt].sep_worst = sep.worst;
+            ENGINE_HIP(hipMemcpyAsync(das_[nxt].gains_sep.get(), sep.t.data(), sep.t.size() * sizeof(f64x2), hipMemcpyHostToDevice, stream));
             ENGINE_HIP(hipMemcpyAsync(das_[nxt].gains_w64.get(), dg64.data(), dg64.size() * sizeof(f64x2), hipMemcpyHostToDevice, stream));
-            ENGINE_HIP(hipMemcpyAsync(das_[nxt].gains_mic.get(), dgm.data(), dgm.size() * sizeof(f64x2), hipMemcpyHostToDevice, stream));
         }
         ENGINE_HIP(hipMemcpyAsync(d_steer_[nxt].get(), t.data(), t.size() * sizeof(f64x2), hipMemcpyHostToDevice, stream));
         ENGINE_HIP(hipStreamSynchronize(stream));  // `t` is pageable and about to go out of scope
@@ -200,7 +205,8 @@ class BinPipelineImpl : public Engine {
         sn.gss_reset_mask = gss_reset_mask_;
         sn.steer = d_steer_[steer_cur_].get();
         sn.steer_dir_stride = steer_dir_stride_;
-        sn.das = DasSnapshot{das_[steer_cur_].gains_w64.get(), das_[steer_cur_].gains_mic.get(), das_[steer_cur_].slots};
+        sn.das = DasSnapshot{das_[steer_cur_].gains_w64.get(),
+                             das_[steer_cur_].sep_ok ? das_[steer_cur_].gains_sep.get() : nullptr, das_[steer_cur_].slots};
         sn.track_tables = d_track_.get();
         sn.track_n = track_n_;
         gss_reset_mask_ = 0;
@@ -282,7 +288,9 @@ class BinPipelineImpl : public Engine {
     DeviceBuffer<f64x2> d_steer_[2];     // double-buffered with steer_cur_: a batch in flight keeps the table it was launched with
     // das in double in one launch, of the same table (geometry.hpp): das_pair_gains_w64_f64 (microphone-pair kernel), das_mic_gains_w64_f64
     // (frame-pair kernels), das_f64_slots (is row 0 identically 1, which microphones get a forward transform in which order)
-    struct DasTables { DeviceBuffer<f64x2> gains_w64, gains_mic; DasSlots slots; } das_[2];
+    // das_sep_gains_w64_f64 (the frame-pair kernels' delay-structured gains; sep_ok: its check against the per-bin table das_mic_gains_w64_f64, host only, held, with the bound it
+    // used and the worst deviation it saw)
+    struct DasTables { DeviceBuffer<f64x2> gains_w64, gains_sep; DasSlots slots; bool sep_ok = false; double sep_bound = 0.0, sep_worst = 0.0; } das_[2];
     DeviceBuffer<f64x2> d_tw_w64_;       // twiddle_table_w64_rot
     DeviceBuffer<char> d_das_sched_;     // das_f64_pair_kernel: chunk table + counter (das_f64_sched_ws_bytes())
     int steer_cur_ = 0;
@@ -315,7 +323,7 @@ int BinPipelineImpl::run_das_one_launch(const float *x, long F, float *y, hipStr
     const Switches &sw = switches();
     if (!das_one_launch_shape() || sw.fused_bins != 1 || snap.das.gains_w64 == nullptr) return kDeclined;
     const DasSlots &sl = snap.das.slots;
-    const DasF64Launch d = das_f64_decide(DasF64Shape{layout, M_, S_, n_cus_, F, sl.mic0_unit, snap.das.gains_mic && d_das_sched_.get(), sl.n_tr,
+    const DasF64Launch d = das_f64_decide(DasF64Shape{layout, M_, S_, n_cus_, F, sl.mic0_unit, snap.das.gains_sep && d_das_sched_.get(), sl.n_tr,
                                                       sw.das_il_ring, sw.das_f64_sched});
     if (d.path == DasF64Path::kChain) return kDeclined;
     ENGINE_HIP(d_planar_.reserve((d.scratch_bytes + sizeof(float) - 1) / sizeof(float)));
@@ -325,7 +333,7 @@ int BinPipelineImpl::run_das_one_launch(const float *x, long F, float *y, hipStr
     da.tail_in = d_tail_[tail_cur_].get(); da.tail_out = d_tail_[tail_cur_ ^ 1].get();
     da.win = d_win_.get(); da.n_frames = F; da.mic_stride = mic_stride;
     da.stream_stride_x = (long)M_ * F * H_; da.n_streams = S_; da.n_mics = M_; da.run_len = 1; da.layout = layout;
-    da.gains = snap.das.gains_w64; da.gains_mic = snap.das.gains_mic; da.tw = d_tw_w64_.get();
+    da.gains = snap.das.gains_w64; da.gains_sep = snap.das.gains_sep; da.tw = d_tw_w64_.get();
     da.mic0_unit = sl.mic0_unit ? 1 : 0; da.n_tr = sl.n_tr; da.extra_mic = sl.extra_mic;
     for (int k = 0; k < 8; ++k) da.slot_mic[k] = sl.slot_mic[k];
     da.sched_ws = d_das_sched_.get(); da.sched_ws_bytes = d_das_sched_.get() ? das_f64_sched_ws_bytes() : 0;

@@ -20,8 +20,9 @@ namespace bf {
 // das in double in one launch: the gain tables of the batch's steering table and what the kernel has to know about it
 struct DasSnapshot {
     // das_pair_gains_w64_f64: pair gains in the register / lane order of the 64-lane kernel (das_f64_w64.hip); das_mic_gains_w64_f64:
-    // per-microphone Hermitian gains of the frame-pair kernel (das_f64_pair_kernel)
-    const f64x2 *gains_w64 = nullptr, *gains_mic = nullptr;
+    // per-microphone Hermitian gains, one entry per bin (host only); das_sep_gains_w64_f64: the same gains delay-structured, what the
+    // frame-pair kernels (das_f64_pair_kernel, das_f64_ring_kernel) read -- null where the table is not a delay in every row (the host's check)
+    const f64x2 *gains_w64 = nullptr, *gains_sep = nullptr;
     DasSlots slots;  // geometry.hpp das_f64_slots of that table
 };
 

@@ -144,7 +144,7 @@ struct DasF64Args {
     int layout = 0;        // bf_layout of x and hist as the kernel reads them: [sample][mic] for das_f64_ring_kernel and das_f64_w64_kernel<1>;
                            // planar for das_f64_pair_kernel, also behind the transposition (enqueue_das_f64 then points x / hist at its scratch)
     float *hist_out = nullptr;         // das_f64_pair_kernel: receives the last hop of the batch (the ring-buffer carry), layout as hist
-    const f64x2 *gains_mic = nullptr;  // das_mic_gains_w64_f64: per-microphone Hermitian gains of the frame-pair kernel (planar input)
+    const f64x2 *gains_sep = nullptr;  // das_sep_gains_w64_f64: the same gains delay-structured, [microphone][kDasSepMic] -- what the frame-pair kernels read
     // das_f64_pair_kernel: the microphones that get a forward transform, in the order the kernel walks them (slot k -> microphone slot_mic[k],
     // never microphone 0), and at most one more microphone whose weight row is bitwise identical to slot 0's (extra_mic, -1 = none): it
     // shares slot 0's transform (das.cpp:60-63 is linear in the microphones; the reference drops z, so aira16's microphones 1 and 7 coincide)
