@@ -38,12 +38,13 @@ EXPORTS = (
     "bf_doa_reset", "bf_doa_destroy",
     "bf_track_set_angles", "bf_process_batch_device_tracked", "bf_track_from_peaks_device",
     "bf_ctrack_set_angles", "bf_process_batch_device_ctracked",
-    "bf_doa_pick_device", "bf_ctrack_from_picks_device",
+    "bf_doa_pick_device", "bf_ctrack_from_picks_device", "bf_ctrack_assign_device",
 )
 BF_DOA_MAX_ANGLES = 1024
 BF_DOA_SRP_PHAT, BF_DOA_CAPON, BF_DOA_MUSIC = 0, 1, 2   # bf_doa_method
 BF_TRACK_MAX_ANGLES = 1024   # = BF_DOA_MAX_ANGLES: a Doa peak index is a track index
 BF_DOA_MAX_PICKS = 16        # = BF_MAX_INTERF + 1: a look direction and every interferer
+BF_ASSIGN_STATE_INTS = 4     # bf_ctrack_assign_device: {idx, hits, misses, out} per slot
 
 
 class BfConfig(C.Structure):
@@ -226,6 +227,9 @@ def load():
                                      C.c_void_p]
     L.bf_ctrack_from_picks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_double,
                                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bf_ctrack_assign_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int,
+                                          C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
     _lib = L
     return L
 
@@ -668,6 +672,25 @@ def ctrack_from_picks_device(picks_ptr: int, map_ptr: int, n_angles: int, k: int
                                        track_ptr or None, stream or None)
     if rc:
         raise BfError(rc, "bf_ctrack_from_picks_device", (L.bf_last_error(None) or b"").decode() or L.bf_strerror(rc).decode())
+
+
+def ctrack_assign_device(picks_ptr: int, map_ptr: int, angles_ptr: int, n_angles: int, k: int, n_streams: int, n_blocks: int,
+                         frames_per_block: int, latency_blocks: int, min_peak: float, gate_deg: float, min_hits: int, max_coast: int,
+                         n_cols: int, state_ptr: int, track_ptr: int, active_ptr: int = 0, stream: int = 0):
+    """Picks [n_streams][n_blocks][k] (maps, 0 = none when min_peak <= 0; the picker's grid [n_angles] float64 on the device) -> a column
+    track [n_streams][n_blocks * frames_per_block][n_cols] in which a column is a talker, on the device (bf_ctrack_assign_device):
+    controllers.assign_sources.  Per block the picks of a publishing block are matched to the live columns, nearest pair within gate_deg
+    first; a column that was not heard coasts for up to max_coast blocks and is then freed, an unmatched pick is born into the lowest
+    free column and counts from its min_hits-th block on.  state [n_streams][n_cols][BF_ASSIGN_STATE_INTS] int32 {idx, hits, misses,
+    out} is read and updated so that the next call continues the stream (start with -1); active (0 = none)
+    [n_streams][n_blocks][n_cols] int32 says which columns were heard in which block."""
+    L = load()
+    rc = L.bf_ctrack_assign_device(picks_ptr or None, map_ptr or None, angles_ptr or None, int(n_angles), int(k), int(n_streams),
+                                   int(n_blocks), int(frames_per_block), int(latency_blocks), float(min_peak), float(gate_deg),
+                                   int(min_hits), int(max_coast), int(n_cols), state_ptr or None, track_ptr or None, active_ptr or None,
+                                   stream or None)
+    if rc:
+        raise BfError(rc, "bf_ctrack_assign_device", (L.bf_last_error(None) or b"").decode() or L.bf_strerror(rc).decode())
 
 
 class Doa:

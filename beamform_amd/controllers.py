@@ -557,3 +557,125 @@ def follow_sources_device(node, doa, x: np.ndarray, frames_per_block: int, k: in
     for c in sorted(c for c in last if c > 0):
         node.set_interference(c, last[c])
     return y, published
+
+
+def assign_sources(picks, maps, angles, frames_per_block: int, latency_blocks: int, min_peak: float, gate_deg: float, min_hits: int,
+                   max_coast: int, n_cols: int, state=None):
+    """The host counterpart of ctrack_assign_device (bf_ctrack_assign_device, include/bfcore.h), as sources_track is of the older
+    builder: a column track in which a column is a talker, not a loudness rank.  picks: [S, nb, k] indices into `angles` (what
+    doa_pick_device or pick_sources gives, -1 in the unused places); maps: [S, nb, A] or None (then every block with a valid first pick
+    publishes); state: [S, n_cols, 4] int32 {idx, hits, misses, out} per column, None = -1 everywhere, a cold start.
+
+    Block by block: a publishing block's valid picks are its candidates.  The closest (live column, candidate) pair within gate_deg is
+    matched first (ties: the lowest column, then the lowest pick), then the next, until none is left; a matched column moves to its pick.
+    A column that was not heard is freed at once while it has fewer than min_hits hits, otherwise it coasts and is freed after more than
+    max_coast silent blocks.  An unmatched candidate is born into the lowest free column.  `out` of a column follows it while it is
+    live and has min_hits hits, and stays where it was otherwise; the frames of block b get `out` as it stood after block
+    b - latency_blocks (the incoming `out` in front of that).
+    Returns (track [S, nb * frames_per_block, n_cols] int32, active [S, nb, n_cols] int32 -- heard in that block and confirmed --,
+    state [S, n_cols, 4] int32 after the last block)."""
+    picks = np.asarray(picks)
+    if picks.ndim != 3:
+        raise ValueError("picks must be [n_streams, n_blocks, k]")
+    S, nb, k = picks.shape
+    ang = np.asarray(angles, dtype=np.float64).ravel()
+    A, W, lat, n_cols, cap = ang.size, int(frames_per_block), int(latency_blocks), int(n_cols), 1 << 30
+    if W < 1 or n_cols < 1 or lat < 0 or int(min_hits) < 1 or int(max_coast) < 0 or not (np.isfinite(gate_deg) and gate_deg >= 0):
+        raise ValueError("frames_per_block, n_cols, min_hits >= 1; latency_blocks, max_coast >= 0; gate_deg finite and >= 0")
+    st = np.full((S, n_cols, 4), -1, np.int32) if state is None else np.array(state, dtype=np.int32).reshape(S, n_cols, 4)
+    track = np.empty((S, nb * W, n_cols), np.int32)
+    active = np.zeros((S, nb, n_cols), np.int32)
+    for s in range(S):
+        idx, hits, misses, out = ([int(v) for v in st[s, :, i]] for i in range(4))
+        outs = [list(out)]  # outs[b]: `out` once blocks 0 .. b-1 have had their say
+        for b in range(nb):
+            row = [int(p) for p in picks[s, b]]
+            cand = []
+            if 0 <= row[0] < A and (maps is None or not (maps[s][b][row[0]] < min_peak)):
+                cand = [p for p in row if 0 <= p < A]
+            live = [c for c in range(n_cols) if 0 <= idx[c] < A]
+            heard = set()
+            if live and cand:
+                with np.errstate(invalid="ignore"):
+                    d = np.abs((ang[[idx[c] for c in live]][:, None] - ang[cand][None, :] + 180.0) % 360.0 - 180.0)
+                    d = np.where(d <= gate_deg, d, np.inf)  # a NaN is not within the gate
+                while np.isfinite(d).any():
+                    i, j = np.unravel_index(int(np.argmin(d)), d.shape)  # the first of equal minima: the lowest column, then the lowest pick
+                    c = live[i]
+                    idx[c], hits[c], misses[c] = cand[j], min(hits[c] + 1, cap), 0
+                    heard.add(c)
+                    cand[j] = None
+                    d[i, :] = np.inf
+                    d[:, j] = np.inf
+            for c in live:
+                if c in heard:
+                    continue
+                if hits[c] < min_hits:
+                    idx[c] = -1
+                else:
+                    misses[c] = min(misses[c] + 1, cap)
+                    if misses[c] > max_coast:
+                        idx[c] = -1
+            for p in cand:
+                free = [c for c in range(n_cols) if not 0 <= idx[c] < A]
+                if p is None or not free:
+                    continue
+                c = free[0]
+                idx[c], hits[c], misses[c] = p, 1, 0
+                heard.add(c)
+            for c in range(n_cols):
+                if 0 <= idx[c] < A and hits[c] >= min_hits:
+                    out[c] = idx[c]
+                    active[s, b, c] = int(c in heard)
+            outs.append(list(out))
+        for b in range(nb):
+            track[s, b * W:(b + 1) * W] = outs[max(0, b - lat + 1)]
+        st[s] = np.array([idx, hits, misses, out], np.int64).astype(np.int32).T
+    return track, active, st
+
+
+def follow_talkers_device(node, doa, x: np.ndarray, frames_per_block: int, k: int, min_sep_deg: float, rel_floor: float = 0.0,
+                          min_peak: float = 0.0, gate_deg: float = 20.0, min_hits: int = 2, max_coast: int = 8):
+    """follow_sources_device with talker identities: the same four enqueues on one stream with nothing copied or synchronised in
+    between, ctrack_assign_device in the third place (assign_sources: state -1, latency 1, n_cols = node.S).  Column c of the track --
+    column 0 the look direction, row c of an lcmv_out_beams node's output -- is one talker: it follows the pick nearest to where that
+    talker was last heard, holds through up to max_coast silent blocks and beyond (a freed column keeps its last angle until a new
+    talker is born into it), and another talker becoming the loudest does not move it.
+
+    node, doa, x: as follow_sources_device takes them.  The node is left at the last `out` of every column that has one: set_theta for
+    column 0, set_interference(c, ...) for the others.
+    Returns (y [F*hop] -- [R, F*hop] when the node has lcmv_out_beams = R > 1 --, columns [nb, n_cols] float64: the angle of every
+    column after each block, NaN while it has none --, active [nb, n_cols] int32: the column's talker was heard in that block)."""
+    import torch
+    from .capi import BF_ASSIGN_STATE_INTS, ctrack_assign_device, doa_pick_device
+    H, W, k = node.H, int(frames_per_block), int(k)
+    F = x.shape[1] // H
+    nb, A, n_cols = F // W, int(doa.angles.size), int(node.S)
+    node.set_ctrack_angles(doa.angles)
+    st = torch.cuda.current_stream().cuda_stream
+    xd = torch.from_numpy(np.ascontiguousarray(x, np.float32)).cuda()
+    ad = torch.from_numpy(np.ascontiguousarray(doa.angles, np.float64)).cuda()
+    maps = torch.empty((nb, A), dtype=torch.float64, device="cuda")
+    picks = torch.empty((nb, k), dtype=torch.int32, device="cuda")
+    state = torch.full((n_cols, BF_ASSIGN_STATE_INTS), -1, dtype=torch.int32, device="cuda")
+    track = torch.empty((nb * W, n_cols), dtype=torch.int32, device="cuda")
+    active = torch.empty((nb, n_cols), dtype=torch.int32, device="cuda")
+    R = int(getattr(node, "n_out", 1))  # lcmv_out_beams: a row per beam
+    yd = torch.empty((R, nb * W * H) if R > 1 else (nb * W * H,), dtype=torch.float32, device="cuda")
+    doa.process_device(xd.data_ptr(), nb * W, maps.data_ptr(), 0, st)
+    doa_pick_device(maps.data_ptr(), ad.data_ptr(), A, 1, nb, k, min_sep_deg, rel_floor, picks.data_ptr(), st)
+    ctrack_assign_device(picks.data_ptr(), maps.data_ptr(), ad.data_ptr(), A, k, 1, nb, W, 1, min_peak, gate_deg, min_hits, max_coast,
+                         n_cols, state.data_ptr(), track.data_ptr(), active.data_ptr(), st)
+    node.process_device_ctracked(xd.data_ptr(), nb * W, yd.data_ptr(), track.data_ptr(), n_cols, 0, st)
+    y, trk, act, last = yd.cpu().numpy(), track.cpu().numpy(), active.cpu().numpy(), state.cpu().numpy()[:, 3]
+    # with one block of latency the frames of block b + 1 hold `out` after block b; the state holds it after the last block
+    outs = np.concatenate([trk.reshape(nb, W, n_cols)[1:, 0], last[None]]) if nb else np.empty((0, n_cols), np.int32)
+    grid = np.asarray(doa.angles, np.float64)
+    columns = np.where(outs >= 0, grid[np.clip(outs, 0, A - 1)], np.nan)
+    for c in range(n_cols):
+        if 0 <= last[c] < A:
+            if c == 0:
+                node.set_theta(float(grid[last[c]]))
+            else:
+                node.set_interference(c, float(grid[last[c]]))
+    return y, columns, act

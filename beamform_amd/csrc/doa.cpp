@@ -12,6 +12,7 @@
 #include "../../include/bfcore.h"
 #include "device_mem.hpp"
 #include "doa.hpp"
+#include "doa_assign.hpp"
 #include "geometry.hpp"
 #include "pipeline_kernels.hpp"
 #include "switches.hpp"
@@ -472,6 +473,44 @@ int bf_ctrack_from_picks_device(const int32_t *picks_dev, const double *map_dev,
     a.frames_per_block = frames_per_block;
     a.latency = latency_blocks;
     DOA_HIP(nullptr, launch_ctrack_from_picks(a, n_streams, (hipStream_t)hip_stream));
+    return BF_OK;
+}
+
+static_assert(BF_ASSIGN_STATE_INTS == kAssignStateInts && kAssignMax == kPickMax, "a slot per column, a candidate per pick");
+
+int bf_ctrack_assign_device(const int32_t *picks_dev, const double *map_dev, const double *angles_dev, int n_angles, int k,
+                            int n_streams, size_t n_blocks, int frames_per_block, int latency_blocks, double min_peak,
+                            double gate_deg, int min_hits, int max_coast, int n_cols, int32_t *state_dev, int32_t *track_dev,
+                            int32_t *active_dev, void *hip_stream) {
+    if (n_angles < 1 || n_angles > BF_DOA_MAX_ANGLES) return fail(nullptr, BF_EINVAL, "bf_ctrack_assign_device: n_angles must be in 1 .. BF_DOA_MAX_ANGLES");
+    if (k < 1 || k > BF_DOA_MAX_PICKS) return fail(nullptr, BF_EINVAL, "bf_ctrack_assign_device: k must be in 1 .. BF_DOA_MAX_PICKS");
+    if (n_streams < 1 || frames_per_block < 1 || latency_blocks < 0)
+        return fail(nullptr, BF_EINVAL, "bf_ctrack_assign_device: n_streams, frames_per_block >= 1 and latency_blocks >= 0");
+    if (n_cols < 1 || n_cols > BF_MAX_INTERF + 1) return fail(nullptr, BF_EINVAL, "bf_ctrack_assign_device: n_cols must be in 1 .. BF_MAX_INTERF + 1");
+    if (!std::isfinite(gate_deg) || gate_deg < 0) return fail(nullptr, BF_EINVAL, "bf_ctrack_assign_device: gate_deg must be finite and >= 0");
+    if (min_hits < 1 || max_coast < 0) return fail(nullptr, BF_EINVAL, "bf_ctrack_assign_device: min_hits >= 1 and max_coast >= 0");
+    if (!picks_dev || !angles_dev || !state_dev || !track_dev)
+        return fail(nullptr, BF_EINVAL, "bf_ctrack_assign_device: picks, angles, state or track is NULL");
+    if (!map_dev && min_peak > 0) return fail(nullptr, BF_EINVAL, "bf_ctrack_assign_device: min_peak > 0 needs the map");
+    if (n_blocks == 0) return BF_OK;  // the state stays: what block 0 of the next call finds
+    CtrackAssignArgs a;
+    a.picks = picks_dev;
+    a.map = map_dev;
+    a.angles = angles_dev;
+    a.state = state_dev;
+    a.track = track_dev;
+    a.active = active_dev;
+    a.min_peak = min_peak;
+    a.gate = gate_deg;
+    a.n_blocks = (long)n_blocks;
+    a.n_angles = n_angles;
+    a.k = k;
+    a.n_cols = n_cols;
+    a.frames_per_block = frames_per_block;
+    a.latency = latency_blocks;
+    a.min_hits = min_hits;
+    a.max_coast = max_coast;
+    DOA_HIP(nullptr, launch_ctrack_assign(a, n_streams, (hipStream_t)hip_stream));
     return BF_OK;
 }
 

@@ -159,6 +159,19 @@ struct CtrackFromPicksArgs {
     int n_angles, k, n_cols, frames_per_block, latency;
 };
 
+// bf_ctrack_assign_device: picks (and maps) of the blocks -> a column track in which a column is a talker (the rule: doa_assign.hpp)
+struct CtrackAssignArgs {
+    const int32_t *picks;      // [stream][n_blocks][k]
+    const double *map;         // [stream][n_blocks][n_angles]; null: every block with a valid first pick publishes
+    const double *angles;      // [n_angles] degrees, the picker's grid
+    int32_t *state;            // [stream][n_cols][4] {idx, hits, misses, out}: in, the slots in front of block 0; out, after the last block
+    int32_t *track;            // [stream][n_blocks * frames_per_block][n_cols]
+    int32_t *active;           // [stream][n_blocks][n_cols] (nullable)
+    double min_peak, gate;
+    long n_blocks;
+    int n_angles, k, n_cols, frames_per_block, latency, min_hits, max_coast;
+};
+
 // per hop of x (hops -1 .. n_frames-1, hop -1 = hist) the microphones with a nonzero sample: layout as the stft kernel reads it
 hipError_t launch_doa_hop_flags(const float *x, const float *hist, unsigned *flags, long n_frames, long mic_stride, long stream_stride_x,
                                 int n_streams, int n_mics, int hop, int layout, hipStream_t s);
@@ -167,6 +180,7 @@ hipError_t launch_doa_reduce(const DoaReduceArgs &a, hipStream_t s);
 hipError_t launch_track_from_peaks(const TrackFromPeaksArgs &a, int n_streams, hipStream_t s);
 hipError_t launch_doa_pick(const DoaPickArgs &a, hipStream_t s);
 hipError_t launch_ctrack_from_picks(const CtrackFromPicksArgs &a, int n_streams, hipStream_t s);
+hipError_t launch_ctrack_assign(const CtrackAssignArgs &a, int n_streams, hipStream_t s);
 
 // ---- the covariance methods, Capon and MUSIC (doa_kernels.hip) -------------------------------------------------------------------------
 struct DoaCovArgs {

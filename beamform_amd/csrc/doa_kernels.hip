@@ -41,10 +41,12 @@
 // per-angle arithmetic.
 //
 // Behind the maps, without a handle: doa_pick_kernel (bf_doa_pick_device: the k strongest separated peaks of every row) and the two
-// track builders, track_from_peaks_kernel and ctrack_from_picks_kernel (one look angle, or one angle per constraint column, per frame).
+// track builders, track_from_peaks_kernel and ctrack_from_picks_kernel (one look angle, or one angle per constraint column, per frame),
+// and ctrack_assign_kernel (bf_ctrack_assign_device: a column track whose columns are talkers, not loudness ranks).
 #include <climits>
 
 #include "doa.hpp"
+#include "doa_assign.hpp"
 #include "doa_eig.hpp"
 #include "doa_pick.hpp"
 #include "launch_trace.hpp"
@@ -448,6 +450,209 @@ __global__ __launch_bounds__(64) void ctrack_from_picks_kernel(CtrackFromPicksAr
         __syncthreads();
     }
     if (lane < C) carry[lane] = cur;
+}
+
+// bf_ctrack_assign_device: a column is a talker.  The rule is doa_assign.hpp's assign_block, block after block; here one wavefront serves
+// one stream and does a block's steps side by side.  Lane l = 16 g + c:
+//   slots       every lane keeps slot c = l & 15 {idx, hits, misses, out} and the angle of idx in registers, the four lane groups g as
+//               four identical copies: every decision below is wavefront-uniform, so the copies never part and no slot is broadcast.
+//   loads       a round is four blocks: lane l asks for pick c of block 4 r + g, and behind it for that pick's angle and, for the
+//               publishing rule, the map value there.  The picks are requested two rounds (eight blocks) ahead and the gathers one
+//               round ahead of their use: the chain picks -> angles[pick] -> match waits only for loads issued four blocks earlier.
+//               Every address is clamped into its buffer first: an invalid pick is a candidate of no block and the index of no load.
+//   distances   the 16 x 16 (slot, candidate) matrix is four entries per lane, slot c against candidates g, g + 4, g + 8, g + 12,
+//               formed once per block with pick_sep; an entry outside the gate, of a free slot or of no candidate is +infinity.
+//   match       per greedy round the lane's least entry (ascending j, strict <), then a butterfly over the key (d, 16 c + j): the least
+//               d, then the lowest slot, then the lowest candidate.  Keys of real pairs are distinct and no d is a NaN; the steps whose
+//               partner lanes cannot hold a pair (slots >= n_cols, candidates >= k) are left out, lane 0 holds the winner and every
+//               lane takes it from there.  At most 16 rounds; the rounds end when the live slots or the candidates run out.
+//   births      the unmatched candidates and the free slots are two 16-bit masks of ballots; the lowest bits pair off.
+//   track       block b's `out` goes to the frames of block b + latency as [frame][column] rows, consecutive lanes on consecutive
+//               int32s, lane i taking column i mod n_cols from the lane that holds it.
+// Registers only: no LDS, no atomics, vector stores, and nothing shared between streams, so the bytes cannot depend on the launch.
+constexpr int kAssignNone = 0x7fff;  // the key of "no pair"
+
+// lane `l`'s value in every lane; l is the same in every lane
+__device__ __forceinline__ double wave_read_lane(double v, int l) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+
+__global__ __launch_bounds__(64) void ctrack_assign_kernel(CtrackAssignArgs a) {
+    const int lane = threadIdx.x, c = lane & 15, g = lane >> 4;
+    const int W = a.frames_per_block, L = a.latency, C = a.n_cols, K = a.k, A = a.n_angles;
+    const long s = blockIdx.x, nb = a.n_blocks, WC = (long)W * C;
+    const int *__restrict__ picks = a.picks + s * nb * K;
+    const double *__restrict__ map = a.map ? a.map + s * nb * A : nullptr;
+    const double *__restrict__ angles = a.angles;
+    int *__restrict__ trk = a.track + s * nb * WC;
+    int *__restrict__ act = a.active ? a.active + s * nb * C : nullptr;
+    int *__restrict__ state = a.state + s * C * kAssignStateInts;
+    const int KG = K < 4 ? K : 4;  // lane groups that hold a candidate
+    const bool in = c < C;  // lanes of the slots past n_cols hold a free slot that nothing is born into
+    int idx = -1, hits = 0, misses = 0, out = -1;
+    if (in) {
+        idx = state[c * kAssignStateInts];
+        hits = state[c * kAssignStateInts + 1];
+        misses = state[c * kAssignStateInts + 2];
+        out = state[c * kAssignStateInts + 3];
+    }
+    double sang = angles[idx >= 0 && idx < A ? idx : 0];  // of use while the slot is live
+    // blocks 0 .. latency-1: no block of this call is old enough, they get `out` as it came in
+    const int c_lane = lane % C, c64 = 64 % C;
+    const long n_head = (L < nb ? (long)L : nb) * WC;
+    {
+        int cc = c_lane;
+        for (long i0 = 0; i0 < n_head; i0 += 64) {  // every lane takes part in the shuffle, also in a short last round
+            const int v = __shfl(out, cc, 64);
+            if (i0 + lane < n_head) trk[i0 + lane] = v;
+            cc += c64;
+            if (cc >= C) cc -= C;
+        }
+    }
+    // this lane's requests of round r: pick c of block 4 r + g, then the angle and the map value at that pick.  The addresses are
+    // clamped and the loads unconditional; what a lane past n_blocks or k has read is set to -1 where the round is used, not here, so
+    // that no load has to be waited for where it is issued.
+    const int jc = c < K ? c : K - 1;
+    auto block_of = [&](long r) { return 4 * r + g < nb ? 4 * r + g : nb - 1; };
+    auto mine = [&](long r, int p) { return 4 * r + g < nb && c < K ? p : -1; };
+    auto load_pick = [&](long r) { return picks[block_of(r) * K + jc]; };
+    auto gather = [&](long r, int p, double &ang, double &mv) {
+        p = mine(r, p);
+        const int pi = p >= 0 && p < A ? p : 0;
+        ang = angles[pi];
+        mv = map ? map[block_of(r) * A + pi] : 0.0;
+    };
+    const long n_rounds = (nb + 3) / 4;
+    int p_nxt = load_pick(0), p_far = load_pick(1);
+    double ang_nxt, mv_nxt;
+    gather(0, p_nxt, ang_nxt, mv_nxt);
+    // Round 0's values are waited for here, once, rather than inside the loop: the compiler drains every outstanding load in front of a
+    // loop of stores that reads a register a load is still on its way to, and it would do so in every round (vmcnt(0), expcnt and
+    // lgkmcnt left alone).
+    __builtin_amdgcn_s_waitcnt(0x0f70);
+    for (long r = 0; r < n_rounds; ++r) {
+        // what was asked for a round ago is taken over here, in front of this round's requests: the block loop below then uses no
+        // register that a load is still on its way to
+        const int p_cur = mine(r, p_nxt);
+        const double ang_cur = ang_nxt, mv_cur = mv_nxt;
+        p_nxt = p_far;
+        p_far = load_pick(r + 2);
+        gather(r + 1, p_nxt, ang_nxt, mv_nxt);
+        const bool p_ok = p_cur >= 0 && p_cur < A;
+        const unsigned long long ok_mask = __ballot(p_ok);
+        for (int q = 0; q < 4; ++q) {
+            const long b = 4 * r + q;
+            if (b >= nb) break;
+            const int base = 16 * q;
+            // 1. candidates: a bit per valid pick of a publishing block
+            const int p0 = __builtin_amdgcn_readlane(p_cur, base);
+            const double mv0 = wave_read_lane(mv_cur, base);
+            const bool pub = p0 >= 0 && p0 < A && (map == nullptr || !(mv0 < a.min_peak));
+            unsigned cm = pub ? (unsigned)((ok_mask >> base) & 0xffffull) : 0u;
+            const bool live0 = in && idx >= 0 && idx < A;
+            const unsigned lm = (unsigned)(__ballot(live0) & 0xffffull);
+            unsigned hit = 0u;  // slots matched or born in this block
+            // 2. and 3. match
+            if (cm != 0u && lm != 0u) {
+                double d[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    d[i] = INFINITY;
+                    if ((cm >> (4 * i)) == 0u) continue;  // no candidate from 4 i on, in any lane
+                    const int j = g + 4 * i;
+                    const double aj = __shfl(ang_cur, base + j, 64);
+                    const double dd = pick_sep(sang, aj);
+                    if (live0 && ((cm >> j) & 1u) && dd <= a.gate) d[i] = dd;
+                }
+                unsigned mc = 0u;  // candidates matched
+                while ((lm & ~hit) != 0u && (cm & ~mc) != 0u) {  // a live slot and a candidate are still without a partner
+                    double bd = INFINITY;
+                    int bk = kAssignNone;
+                    if (!((hit >> c) & 1u)) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const int j = g + 4 * i;
+                            if (!((mc >> j) & 1u) && d[i] < bd) {
+                                bd = d[i];
+                                bk = 16 * c + j;
+                            }
+                        }
+                    }
+                    // the butterfly, without the steps whose partner lanes hold no pair: slots >= n_cols (lane bits 0 .. 3), candidates >= k
+                    // (lane bits 4 and 5).  Lane 0 ends with the least key of all lanes, and every lane follows lane 0.
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) {
+                        if (o >= 16 ? (o >> 4) >= KG : o >= C) continue;
+                        const double od = __shfl_xor(bd, o, 64);
+                        const int ok = __shfl_xor(bk, o, 64);
+                        if (od < bd || (od == bd && ok < bk)) {
+                            bd = od;
+                            bk = ok;
+                        }
+                    }
+                    bk = __builtin_amdgcn_readfirstlane(bk);
+                    if (bk == kAssignNone) break;
+                    const int cw = bk >> 4, jw = bk & 15;
+                    const int pw = __builtin_amdgcn_readlane(p_cur, base + jw);
+                    const double aw = wave_read_lane(ang_cur, base + jw);
+                    if (c == cw) {
+                        idx = pw;
+                        sang = aw;
+                        hits = assign_count_up(hits);
+                        misses = 0;
+                    }
+                    hit |= 1u << cw;
+                    mc |= 1u << jw;
+                }
+                cm &= ~mc;
+            }
+            // 4. an unmatched live slot is freed or coasts
+            if (live0 && !((hit >> c) & 1u)) {
+                if (hits < a.min_hits) idx = -1;
+                else {
+                    misses = assign_count_up(misses);
+                    if (misses > a.max_coast) idx = -1;
+                }
+            }
+            // 5. births: the lowest unmatched candidate into the lowest free slot
+            unsigned fm = (unsigned)(__ballot(in && !(idx >= 0 && idx < A)) & 0xffffull);
+            while (cm != 0u && fm != 0u) {
+                const int jw = __ffs(cm) - 1, cw = __ffs(fm) - 1;
+                const int pw = __builtin_amdgcn_readlane(p_cur, base + jw);
+                const double aw = wave_read_lane(ang_cur, base + jw);
+                if (c == cw) {
+                    idx = pw;
+                    sang = aw;
+                    hits = 1;
+                    misses = 0;
+                }
+                hit |= 1u << cw;
+                cm &= cm - 1u;
+                fm &= fm - 1u;
+            }
+            // 6. out and active
+            const bool confirmed = in && idx >= 0 && idx < A && hits >= a.min_hits;
+            if (confirmed) out = idx;
+            if (act != nullptr && lane < C) act[b * C + lane] = confirmed && ((hit >> c) & 1u) ? 1 : 0;
+            // 7. the frames of block b + latency
+            if (b + L < nb) {
+                int *dst = trk + (b + L) * WC;
+                int cc = c_lane;
+                for (long i0 = 0; i0 < WC; i0 += 64) {
+                    const int v = __shfl(out, cc, 64);
+                    if (i0 + lane < WC) dst[i0 + lane] = v;
+                    cc += c64;
+                    if (cc >= C) cc -= C;
+                }
+            }
+        }
+    }
+    if (lane < C) {
+        state[lane * kAssignStateInts] = idx;
+        state[lane * kAssignStateInts + 1] = hits;
+        state[lane * kAssignStateInts + 2] = misses;
+        state[lane * kAssignStateInts + 3] = out;
+    }
 }
 
 // ---- the covariance methods: Capon and MUSIC ------------------------------------------------------------------------------------------
@@ -945,6 +1150,13 @@ hipError_t launch_doa_pick(const DoaPickArgs &a, hipStream_t s) {
 hipError_t launch_ctrack_from_picks(const CtrackFromPicksArgs &a, int n_streams, hipStream_t s) {
     if (a.n_cols < 1 || a.n_cols > kPickMax || a.k < 1 || a.k > kPickMax) return hipErrorInvalidValue;
     BF_LAUNCH(ctrack_from_picks_kernel, dim3((unsigned)n_streams), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_ctrack_assign(const CtrackAssignArgs &a, int n_streams, hipStream_t s) {
+    if (a.n_cols < 1 || a.n_cols > kAssignMax || a.k < 1 || a.k > kAssignMax || a.n_angles < 1 || a.n_blocks < 1 || n_streams < 1)
+        return hipErrorInvalidValue;
+    BF_LAUNCH(ctrack_assign_kernel, dim3((unsigned)n_streams), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 //
 //   follow_sources_node <beamform_config.yaml> <in.wav> <out.wav> <frames_per_block> <angle_lo> <angle_hi> <angle_step>
 //                       [k=2] [min_sep_deg=30] [rel_floor=0] [min_peak=0] [freq_lo=100] [freq_hi=16000] [beams=1] [capon|music[:n]]
+//                       [identity [gate_deg=20]]
 //
 // The config's look direction (initial_angle) and its interferers (angle_interf<k>) are where the node starts; the candidate grid is
 // angle_lo, angle_lo + angle_step, ... below angle_hi (degrees).  Per block of frames_per_block periods the strongest peak of the
@@ -15,6 +16,10 @@
 // direction, r: interferer r) with nulls on the others -- written to <out.wav>.<r>.wav, one file per row, instead of <out.wav>.
 // music[:n]: the MUSIC map instead of the Capon map, with a signal subspace of n dimensions (bf_doa_set_sources; default k, at most
 // n_mics - 1).
+// identity [gate_deg]: bf_ctrack_assign_device in the third place instead of bf_ctrack_from_picks_device -- a column of the track (and
+// with beams > 1 a row of the output) is one talker, not a loudness rank: it follows the pick within gate_deg of where its talker was
+// last heard, holds through pauses (min_hits 2, max_coast 8), and a new talker gets a free column.  After the publications one line per
+// column on stdout, "column <c> <last_angle_deg or -> <share of blocks in which its talker was heard>".
 // in.wav: a multichannel WAV file (its first n_mics channels, its sample rate).  Trailing periods that do not fill a block are dropped.
 #include <hip/hip_runtime.h>
 
@@ -47,7 +52,7 @@ int main(int argc, char **argv) {
     if (argc < 8) {
         fprintf(stderr,
                 "usage: %s <config.yaml> <in.wav> <out.wav> <frames_per_block> <angle_lo> <angle_hi> <angle_step> [k=2] [min_sep_deg=30] "
-                "[rel_floor=0] [min_peak=0] [freq_lo=100] [freq_hi=16000] [beams=1] [capon|music[:n]]\n",
+                "[rel_floor=0] [min_peak=0] [freq_lo=100] [freq_hi=16000] [beams=1] [capon|music[:n]] [identity [gate_deg=20]]\n",
                 argv[0]);
         return 2;
     }
@@ -64,7 +69,24 @@ int main(int argc, char **argv) {
     const double freq_lo = argc > 12 ? atof(argv[12]) : 100.0, freq_hi = argc > 13 ? atof(argv[13]) : 16000.0;
     const int beams = argc > 14 ? atoi(argv[14]) : 1;
     if (beams > 1) cfg.lcmv_out_beams = beams;
-    const char *method = argc > 15 ? argv[15] : "capon";
+    const char *method = "capon";
+    bool identity = false;
+    double gate = 20.0;
+    for (int i = 15; i < argc; ++i) {
+        if (strcmp(argv[i], "identity") != 0) {
+            method = argv[i];
+            continue;
+        }
+        identity = true;
+        if (i + 1 < argc) {  // a number behind it is the gate
+            char *end = nullptr;
+            const double v = strtod(argv[i + 1], &end);
+            if (end != argv[i + 1] && *end == '\0') {
+                gate = v;
+                ++i;
+            }
+        }
+    }
     const bool music = strncmp(method, "music", 5) == 0 && (method[5] == '\0' || method[5] == ':');
     if (!music && strcmp(method, "capon") != 0) {
         fprintf(stderr, "bad method %s (capon, music or music:<n>)\n", method);
@@ -106,11 +128,12 @@ int main(int argc, char **argv) {
 
     std::vector<double> maps(nb * A);
     std::vector<int32_t> picks(nb * k), carry(n_cols, -1);
+    std::vector<int32_t> state((size_t)n_cols * BF_ASSIGN_STATE_INTS, -1), active(identity ? nb * n_cols : 0);  // identity only
     if (nb) {
         hipStream_t s;
         float *x_dev, *y_dev;
         double *map_dev, *grid_dev;
-        int32_t *picks_dev, *carry_dev, *track_dev;
+        int32_t *picks_dev, *carry_dev, *track_dev, *state_dev = nullptr, *active_dev = nullptr;
         CK(hipStreamCreate(&s));
         CK(hipMalloc((void **)&x_dev, x.size() * sizeof(float)));
         CK(hipMalloc((void **)&y_dev, y.size() * sizeof(float)));
@@ -122,16 +145,29 @@ int main(int argc, char **argv) {
         CK(hipMemcpyAsync(x_dev, x.data(), x.size() * sizeof(float), hipMemcpyHostToDevice, s));
         CK(hipMemcpyAsync(grid_dev, grid.data(), grid.size() * sizeof(double), hipMemcpyHostToDevice, s));
         CK(hipMemcpyAsync(carry_dev, carry.data(), carry.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (identity) {
+            CK(hipMalloc((void **)&state_dev, state.size() * sizeof(int32_t)));
+            CK(hipMalloc((void **)&active_dev, active.size() * sizeof(int32_t)));
+            CK(hipMemcpyAsync(state_dev, state.data(), state.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        }
         // the loop
         BF(bf_doa_process_device(doa, x_dev, frames, map_dev, nullptr, s));
         BF(bf_doa_pick_device(map_dev, grid_dev, A, 1, nb, k, min_sep, rel_floor, picks_dev, s));
-        BF(bf_ctrack_from_picks_device(picks_dev, map_dev, A, k, 1, nb, W, 1, min_peak, n_cols, carry_dev, track_dev, s));
+        if (identity)
+            BF(bf_ctrack_assign_device(picks_dev, map_dev, grid_dev, A, k, 1, nb, W, 1, min_peak, gate, 2, 8, n_cols, state_dev, track_dev,
+                                       active_dev, s));
+        else BF(bf_ctrack_from_picks_device(picks_dev, map_dev, A, k, 1, nb, W, 1, min_peak, n_cols, carry_dev, track_dev, s));
         BF(bf_process_batch_device_ctracked(node, x_dev, frames, y_dev, nullptr, track_dev, n_cols, s));
         CK(hipMemcpyAsync(y.data(), y_dev, y.size() * sizeof(float), hipMemcpyDeviceToHost, s));
         CK(hipMemcpyAsync(maps.data(), map_dev, maps.size() * sizeof(double), hipMemcpyDeviceToHost, s));
         CK(hipMemcpyAsync(picks.data(), picks_dev, picks.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (identity) {
+            CK(hipMemcpyAsync(state.data(), state_dev, state.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            CK(hipMemcpyAsync(active.data(), active_dev, active.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        }
         CK(hipStreamSynchronize(s));
-        for (void *p : {(void *)x_dev, (void *)y_dev, (void *)map_dev, (void *)grid_dev, (void *)picks_dev, (void *)carry_dev, (void *)track_dev})
+        for (void *p : {(void *)x_dev, (void *)y_dev, (void *)map_dev, (void *)grid_dev, (void *)picks_dev, (void *)carry_dev, (void *)track_dev,
+                        (void *)state_dev, (void *)active_dev})
             (void)hipFree(p);
         (void)hipStreamDestroy(s);
     }
@@ -147,6 +183,13 @@ int main(int argc, char **argv) {
             if (p[j] >= 0 && p[j] < A) printf(" %.17g", grid[p[j]]);
         printf("\n");
         ++n_pub;
+    }
+    for (int c = 0; identity && c < n_cols; ++c) {  // where every column's talker was last heard, and how often it was
+        const int32_t last = state[(size_t)c * BF_ASSIGN_STATE_INTS + 3];
+        size_t heard = 0;
+        for (size_t b = 0; b < nb; ++b) heard += active[b * n_cols + c] != 0;
+        if (last >= 0 && last < A) printf("column %d %.17g %.6f\n", c, grid[last], nb ? (double)heard / (double)nb : 0.0);
+        else printf("column %d - %.6f\n", c, nb ? (double)heard / (double)nb : 0.0);
     }
     for (int r = 0; r < beams; ++r) {
         char name[4096];

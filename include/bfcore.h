@@ -622,7 +622,8 @@ int bf_process_batch_device_ctracked(bf_handle *h, const float *x_dev, size_t n_
  * The device half of controllers.pick_sources / DoaSources / sources_track: with these two a caller closes the multi-source loop in
  * four enqueues on one stream and no host synchronisation -- bf_doa_process_device (the Capon map), bf_doa_pick_device,
  * bf_ctrack_from_picks_device, bf_process_batch_device_ctracked (controllers.follow_sources_device, examples/follow_sources_node.cpp).
- * Neither takes a handle; each is one small launch on hip_stream. */
+ * Neither takes a handle; each is one small launch on hip_stream.  bf_ctrack_from_picks_device's columns are loudness ranks (pick j in
+ * column j); bf_ctrack_assign_device, the third call below, takes its place where a column has to stay with one talker. */
 #define BF_DOA_MAX_PICKS 16   /* = BF_MAX_INTERF + 1: a look direction and every interferer */
 /* The k strongest separated peaks of every map row.  map_dev: [n_streams][n_blocks][n_angles] as bf_doa_process_device writes it;
  * angles_dev: [n_angles] doubles ON THE DEVICE, the candidate grid in degrees (any order, any range); picks_dev:
@@ -664,6 +665,51 @@ int bf_doa_pick_device(const double *map_dev, const double *angles_dev, int n_an
 int bf_ctrack_from_picks_device(const int32_t *picks_dev, const double *map_dev, int n_angles, int k, int n_streams, size_t n_blocks,
                                 int frames_per_block, int latency_blocks, double min_peak, int n_cols, int32_t *carry_dev,
                                 int32_t *track_dev, void *hip_stream);
+/* From picks to a column track in which a column is a TALKER.  bf_ctrack_from_picks_device above puts pick j into column j, and picks
+ * are ordered by strength: its columns are loudness ranks, and they swap whenever another talker becomes the loudest.  This builder
+ * associates the picks of every block with the columns instead: a column follows the pick nearest to where its talker was last heard,
+ * holds through pauses, and a new talker gets a free column.  No handle, one small launch on hip_stream, one wavefront per stream,
+ * serial over the blocks; it stands in the third place of the four-enqueue loop (controllers.follow_talkers_device).
+ * picks_dev: [n_streams][n_blocks][k]; map_dev: [n_streams][n_blocks][n_angles], may be NULL when min_peak <= 0; angles_dev:
+ * [n_angles] doubles ON THE DEVICE, the picker's grid; track_dev: [n_streams][n_blocks * frames_per_block][n_cols], the layout
+ * bf_process_batch_device_ctracked reads; active_dev: [n_streams][n_blocks][n_cols] int32, may be NULL; state_dev:
+ * [n_streams][n_cols][BF_ASSIGN_STATE_INTS] int32, read and written: per slot (column) {idx, hits, misses, out}.
+ *   A slot is LIVE iff idx is in 0 .. n_angles-1; otherwise it is free and its hits and misses are ignored.  A state filled with -1 is a
+ *   cold start.
+ * Per stream, for each block b in ascending order:
+ *   1. Candidates.  The block publishes by the rule of bf_ctrack_from_picks_device: p0 = picks[s][b][0] is in 0 .. n_angles-1 and the
+ *      map is NULL or map[s][b][p0] is not below min_peak (a NaN publishes).  If it publishes, the candidates are the picks[s][b][j],
+ *      j < k, that are in 0 .. n_angles-1, in order of j; otherwise there are none.  Duplicate picks in a row are ordinary candidates.
+ *   2. Match.  Among the live slots and the candidates, repeat until no pair qualifies: take the unmatched pair (slot c, candidate j)
+ *      with the smallest d = sep(angles[idx_c], angles[p_j]) for which d <= gate_deg holds; ties go to the lowest c, then the lowest
+ *      j.  sep is the picker's circular distance (step 3 of bf_doa_pick_device, beamform_amd/csrc/doa_pick.hpp), the same function
+ *      to the bit; idx_c is the slot's index as the block found it.  A NaN distance never matches.
+ *   3. A matched slot: idx = p_j, hits = min(hits + 1, 2^30), misses = 0.
+ *   4. An unmatched live slot: with hits < min_hits it is tentative and is freed (idx = -1).  Otherwise misses = min(misses + 1, 2^30),
+ *      and the slot is freed when misses > max_coast.
+ *   5. Births.  Each unmatched candidate, in order of j, takes the lowest free slot c < n_cols -- slots freed in step 4 of this block
+ *      count as free -- with idx = p_j, hits = 1, misses = 0.  With no free slot the candidate is dropped.  A newborn talker may land
+ *      in column 0, the look direction, once column 0's talker has been freed.
+ *   6. Out.  For every live slot with hits >= min_hits: out = idx.  Any other out stays as it was: a freed column keeps pointing where
+ *      its talker was last heard.  active[s][b][c] = 1 iff slot c was matched or born in this block and has hits >= min_hits, else 0;
+ *      active is not delayed.
+ *   7. Frames.  Every frame of block b gets, per column, out as it stood after block b - latency_blocks; if there is no such block, out
+ *      as it was on entry.
+ * On exit the state is the state after the last block, so that consecutive calls continue one stream -- exactly for
+ * latency_blocks <= 1 (out is one index per column: a longer latency forgets what the last latency_blocks - 1 blocks of the previous
+ * call left in out).  The rule for one block in plain C++: beamform_amd/csrc/doa_assign.hpp; in numpy: controllers.assign_sources.
+ * A pick outside the map is neither a candidate nor ever read through.  A value read from the state is copied as it stands and never
+ * used as an index, but for an idx that has been checked against n_angles.  Streams do not see each other and a stream's blocks are
+ * walked in order by one wavefront: the bytes do not depend on the launch.
+ * BF_EINVAL, checked before any device work: n_angles outside 1 .. BF_DOA_MAX_ANGLES, k outside 1 .. BF_DOA_MAX_PICKS, n_streams < 1,
+ * frames_per_block < 1, latency_blocks < 0, n_cols outside 1 .. BF_MAX_INTERF + 1, a non-finite or negative gate_deg, min_hits < 1,
+ * max_coast < 0, NULL picks / angles / state / track, NULL map with min_peak > 0.  n_blocks = 0 is BF_OK and launches nothing (the
+ * state stays). */
+#define BF_ASSIGN_STATE_INTS 4
+int bf_ctrack_assign_device(const int32_t *picks_dev, const double *map_dev, const double *angles_dev, int n_angles, int k,
+                            int n_streams, size_t n_blocks, int frames_per_block, int latency_blocks, double min_peak,
+                            double gate_deg, int min_hits, int max_coast, int n_cols,
+                            int32_t *state_dev, int32_t *track_dev, int32_t *active_dev, void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -83,6 +83,37 @@ for it in range(runs + 2):
             ms[name].append(ev[i].elapsed_time(ev[i + 1]))
 for name, ts in ms.items():
     print(json.dumps(dict(shape, op=name, median_ms=round(float(np.median(ts)), 4), min_ms=round(float(np.min(ts)), 4))), flush=True)
+# the two track builders side by side, each launch alone between a pair of HIP events, in alternation: the tool's own shape (one stream,
+# the recording's blocks) and 256 streams x 256 blocks.  bf_ctrack_assign_device walks a stream's blocks in order with one wavefront;
+# bf_ctrack_from_picks_device takes 64 blocks per step.
+for S_b, nb_b, m_b in ((1, nb, maps), (256, 256, None)):
+    if m_b is None:
+        m_b = torch.rand((S_b, nb_b, D), dtype=torch.float64, device="cuda")
+    pk = torch.empty((S_b, nb_b, K), dtype=torch.int32, device="cuda")
+    capi.doa_pick_device(m_b.data_ptr(), ad.data_ptr(), D, S_b, nb_b, K, MIN_SEP, 0.0, pk.data_ptr(), st)
+    cr = torch.full((S_b, 2), -1, dtype=torch.int32, device="cuda")
+    state = torch.full((S_b, 2, capi.BF_ASSIGN_STATE_INTS), -1, dtype=torch.int32, device="cuda")
+    tk = torch.empty((S_b, nb_b * W, 2), dtype=torch.int32, device="cuda")
+    act = torch.empty((S_b, nb_b, 2), dtype=torch.int32, device="cuda")
+    builders = [
+        ("bf_ctrack_from_picks_device", lambda: capi.ctrack_from_picks_device(pk.data_ptr(), m_b.data_ptr(), D, K, S_b, nb_b, W, 1, 0.0, 2,
+                                                                              cr.data_ptr(), tk.data_ptr(), st)),
+        ("bf_ctrack_assign_device", lambda: capi.ctrack_assign_device(pk.data_ptr(), m_b.data_ptr(), ad.data_ptr(), D, K, S_b, nb_b, W, 1, 0.0,
+                                                                      20.0, 2, 8, 2, state.data_ptr(), tk.data_ptr(), act.data_ptr(), st)),
+    ]
+    bms = {name: [] for name, _ in builders}
+    for it in range(runs + 2):
+        for name, fn in builders:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(s)
+            fn()
+            e1.record(s)
+            e1.synchronize()
+            if it >= 2:
+                bms[name].append(e0.elapsed_time(e1))
+    for name, ts in bms.items():
+        print(json.dumps(dict(shape, op=name + " alone", streams=S_b, blocks=nb_b, median_ms=round(float(np.median(ts)), 4),
+                              min_ms=round(float(np.min(ts)), 4))), flush=True)
 # the host's share of the round trip, on its own: the numpy picker and schedule over the same maps
 from beamform_amd.controllers import sources_track  # noqa: E402
 mh = maps.cpu().numpy()
