@@ -273,7 +273,6 @@ __device__ __forceinline__ void st_y(const BinsArgs &a, long idx, int q, cd y) {
 // problem index -> FFT bin whose packed spectrum is read, and whether X must be conjugated
 __device__ __forceinline__ int q_src_bin(int q) { return q == kQX ? kN / 2 - 1 : q; }
 __device__ __forceinline__ int q_bin(int q) { return q; }
-inline int q_bin_host(int q) { return q; }
 
 // X_m for problem q out of the packed pair spectra of one frame (Zf = [NP][1024]).
 template <int MP, typename ZT>

@@ -2,7 +2,8 @@
 // in double): which kernel of each stage with which template arguments, the row formats between the stages and the workspace sizes, host
 // arithmetic (docs/DISPATCH.md lists the outcome per shape).  Plain C++: the CPU suite checks it through tests/host_emul (every chain row of
 // the dispatch table, random shapes, every switch).  BinPipelineImpl::run_chain (pipeline.hip) decides once per batch and the launchers of
-// the batch's FFT size (pipeline_kernels.hpp) carry the plan out; launch geometry stays with them.
+// the batch's FFT size (pipeline_kernels.hpp) carry the plan out.  The launch geometry of the plan -- runs, tiles, rounds, grids and the
+// integers the kernels decode their work from -- is decided at the same moment, as values too: chain_geom.hpp (included below).
 #pragma once
 
 #include <cstddef>
@@ -22,6 +23,8 @@ namespace bf {
 // gss_postfilter (last yet again: a shape written without it means 0 = off): bf_config.gss_postfilter, ignored by every node but gss.
 // lcmv_rows (last, as the others: a shape written without it means one): beams lcmv emits per stream and look direction
 // (bf_config.lcmv_out_beams; 0 = 1, ignored by every other node).
+// mvdr_tile (last, as the others: a shape written without it means 0 = chosen by cost): the switch of that name, read by the geometry only
+// (chain_geom.hpp).
 struct ChainShape {
     int algo, n_fft, layout, n_mics, n_streams, n_dirs, kp1, past_windows, precision;
     bool dump;
@@ -37,6 +40,7 @@ struct ChainShape {
     int ctrack_cols;
     int gss_postfilter;
     int lcmv_rows;
+    int mvdr_tile;
 };
 
 // The kernels of each stage, template arguments behind them as ChainPlan holds them:
@@ -57,6 +61,68 @@ enum class ChainBins { kFusedTail, kPointwise, kMpfMask, kMcra, kGscAlign, kMvdr
 enum class ChainRec { kNone, kRecursion, kRecIstft };
 enum class ChainIstft { kNone, kW64, kF32, kSmall, kSplit, kGeneric };
 enum class ChainTail { kNone, kSmooth4, kSmooth, kNlms, kNlmsPar, kNlmsMw };
+
+// ---- the launch geometry of a plan, one small record per scheme (filled by chain_geom, chain_geom.hpp) ----------------------------------
+// mvdr_fast_kernel's argument (by value: members, order and types are the kernel's ABI).  Lanes enumerate (time tile, problem) pairs of
+// ONE output stream, problem fastest, over the problems that need a solve only
+struct FastPlan {
+    int q_lo, n_main;  // problems q_lo .. q_lo + n_main - 1 are in band (a contiguous run inside 1 .. N/2-1)
+    int n_extra;       // the irregular problems of quirk Q1 that are in band: N/2 (f := 0) when 0 Hz is, N/2+1 (|f| = (N/2-1) sr/N)
+    int extra_q[2];
+    int solve0;        // lcmv with 0 Hz in band: problem 0 is an ordinary problem (mvdr passes X_0 through, mvdr.cpp:76)
+    int nb;            // 1 + n_main + n_extra
+    int tile, tiles, waves_per_stream;
+};
+
+// what the batch has to zero in Yh before mvdr_fast_kernel runs: the rows nobody solves but the backward transform reads
+enum class ChainZero { kNone, kF64Rows, kF32Rows };
+
+// kStft / kStftSmall / kStftWave2048 / kStftGeneric (StftArgs::run_len, blocks of 256 threads; kStftGeneric: run_len 1)
+struct StftGeom {
+    int run_len;
+    unsigned blocks;
+    bool ok;
+};
+// kFusedW64 / kFusedSmall / kFusedSplit: a round = fpr consecutive frames of one stream, rounds numbered stream * rps + round, one contiguous
+// range of rpb rounds per block (the N = 1024 kernel walks single frames: its frames_per_block / total_frames are rpb / total)
+struct FusedGeom {
+    int fpr;
+    long rps, total, rpb;
+    unsigned grid, tail_blocks;  // tail_blocks: fused_tail_kernel, one thread per (stream, frame, problem N/2 | N/2+1)
+};
+struct BinsGeom {
+    unsigned ew_blocks;      // pointwise_bins / mpf_mask / gsc_align: a thread per (stream, frame, problem), 256 per block
+    unsigned lane_blocks;    // mcra_node / mpf_recursion / gss_postfilter: a lane per (stream, problem), 64 per block
+    unsigned rec_blocks;     // mpf_rec_istft_kernel: a block per stream
+    unsigned expand_blocks;  // expand_spectrum_kernel: a thread per (stream, row, frame, bin)
+    int tile, tps;           // the group kernels (mvdr_lcmv_kernel, cov2d_kernel): frames per tile, tiles per stream
+    unsigned gx, gy;         // mvdr_lcmv_kernel: (tile of a stream, group of 256 / MP problems)
+    unsigned cov2d_grid;     // (unit, problem group) -> XCD-aware order in the kernel
+    FastPlan fp;             // kMvdrFast
+    unsigned fast_grid;
+    int fast_km, wpc;        // columns of the instantiation that runs; resident wavefronts per CU
+    ChainZero zero;
+    unsigned gss_grid;       // gss_kernel / gss_lane_kernel
+};
+// kF32: frames per chunk, chunks per stream; kW64: frame PAIRS per run, runs per stream; kSmall / kSplit: frames per run (runs per stream
+// is the kernel's own ceil(n_frames / L)); kGeneric: a block per (stream, frame) item, grid-strided, and the overlap-add pass
+struct IstftGeom {
+    int per_run, runs_per_stream;
+    unsigned grid, ola_grid;
+};
+struct TailGeom {
+    unsigned smooth_grid, smooth4_grid, state_grid;  // smooth_kernel, smooth4_kernel, smooth_state_kernel
+    size_t lds_serial, lds_par;                      // dynamic LDS bytes of gsc_nlms_kernel / of gsc_nlms_par_kernel and gsc_nlms_mw_kernel
+    unsigned nlms_grid;                              // a block per stream
+};
+struct ChainGeom {
+    bool ok;
+    StftGeom stft;
+    FusedGeom fused;
+    BinsGeom bins;
+    IstftGeom istft;
+    TailGeom tail;
+};
 
 struct ChainPlan {
     int algo, layout;
@@ -87,6 +153,9 @@ struct ChainPlan {
     // all rows of its (beam, problem): no second row buffer, yh_bytes stays what it is); post_rp = the rows padded to 1 / 2 / 4 / 8 / 16
     bool postfilter;
     int post_rp;
+    // how the batch is cut into runs, tiles and rounds, every grid and every integer the kernels decode their work from: chain_geom
+    // (chain_geom.hpp) fills it right behind chain_decide; the launchers read nothing else
+    ChainGeom geom;
     bool fused() const { return front >= ChainFront::kFusedW64; }
     bool rec_istft() const { return rec == ChainRec::kRecIstft; }
 };
@@ -183,3 +252,5 @@ inline ChainPlan chain_decide(const ChainShape &c) {
 }
 
 }  // namespace bf
+
+#include "chain_geom.hpp"  // the geometry of a plan (needs the types above)

@@ -2,10 +2,6 @@
 // onto lanes (thread-per-problem, row-per-lane over LDS, cyclic rows over DPP quads, row-per-lane over DPP rows).
 #include "launch_trace.hpp"
 #include "bins_common.hpp"
-#include "switches.hpp"
-
-#include <cmath>
-#include <vector>
 
 namespace bf {
 namespace BF_NTAG {
@@ -36,18 +32,11 @@ namespace {
 // Lanes enumerate (time tile, problem) pairs of ONE output stream, problem fastest, over the problems that need a solve
 // only: k = 0 is problem 0 (y = X_0, mvdr.cpp:76), then the in-band problems (FastPlan).  Out-of-band problems (34 % of
 // the rows at the launch-file band) occupy no lane at all, and the host picks the tile length so that the wavefronts
-// fill the chip's 4 x CUs slots a whole number of times (65 536 frames, 340 problems: 2 040 wavefronts of 171 frames
-// = two rounds, where one wavefront per (128-frame tile, 64 consecutive problems) took three).
+// fill the chip's 4 x CUs slots a whole number of times (65 536 frames, 340 problems, 256 CUs: 1 020 wavefronts of 342 frames
+// = one round, where one wavefront per (128-frame tile, 64 consecutive problems) took three; chain_geom.hpp, pinned by the CPU suite).
 // MP = 2 x microphone pairs (2, 4, 6, 8): an odd count's last pair has a zero partner channel, whose row is pinned to the
 // identity (its spectrum is the transform's ~1e-16 rounding residue, not an exact zero).
-struct FastPlan {
-    int q_lo, n_main;  // problems q_lo .. q_lo + n_main - 1 are in band (a contiguous run inside 1 .. N/2-1)
-    int n_extra;       // the irregular problems of quirk Q1 that are in band: N/2 (f := 0) when 0 Hz is, N/2+1 (|f| = (N/2-1) sr/N)
-    int extra_q[2];
-    int solve0;        // lcmv with 0 Hz in band: problem 0 is an ordinary problem (mvdr passes X_0 through, mvdr.cpp:76)
-    int nb;            // 1 + n_main + n_extra
-    int tile, tiles, waves_per_stream;
-};
+// (FastPlan itself: chain_plan.hpp; chain_geom.hpp fills it)
 
 // one row of 64 stored elements, global -> LDS (lane l's 12 or 16 bytes land at row + 16 l)
 template <bool Z128>
@@ -190,21 +179,21 @@ __device__ constexpr int LT(int a, int b) { return a * (a + 1) / 2 + b; }
 
 }  // namespace
 
-hipError_t launch_mvdr_lcmv(const ChainPlan &p, const BinsArgs &a, int n_cus, hipStream_t s) {
-    int tile = 64;
-    if (a.n_frames < tile) tile = (int)a.n_frames;
-    const int tps = (int)((a.n_frames + tile - 1) / tile);
+// tiles, grids, the FastPlan and the zero-fill of the batch: ChainPlan::geom (chain_geom.hpp)
+hipError_t launch_mvdr_lcmv(const ChainPlan &p, const BinsArgs &a, hipStream_t s) {
+    const BinsGeom &g = p.geom.bins;
+    const int tile = g.tile, tps = g.tps;
     // lcmv with bf_config.lcmv_out_beams > 1: every kernel stores p.rows rows per stream (Yh = [stream][rows][frame][kYhStride]).  The lane kernel
     // and cov2d_kernel have twins for it, instantiated for two columns and more: a batch without interferers runs the next larger one,
     // whose padding column is the identity (row 0 then equals the one-row kernel's to rounding, not bit for bit).  The group kernel counts at run time
     const bool rows = p.rows > 1;
     if (a.gss_rows != p.rows || (rows && a.cfg.algo != BF_LCMV)) return hipErrorInvalidValue;
     if (p.bins == ChainBins::kMvdrLcmv) {  // a group of MP lanes per problem, padding rows / columns are identity
+        const dim3 grid(g.gx, g.gy);
 #define BF_LAUNCH_ML(MP_, KM_)                                                                                               \
     do {                                                                                                                     \
-        const dim3 grid_(tps * a.n_streams, (kNQ + (256 / MP_) - 1) / (256 / MP_));                                          \
-        if (p.ctrack) BF_LAUNCH((mvdr_lcmv_track_kernel<MP_, KM_>), grid_, dim3(256), 0, s, a, tile, tps);                   \
-        else BF_LAUNCH((mvdr_lcmv_kernel<MP_, KM_>), grid_, dim3(256), 0, s, a, tile, tps);                                  \
+        if (p.ctrack) BF_LAUNCH((mvdr_lcmv_track_kernel<MP_, KM_>), grid, dim3(256), 0, s, a, tile, tps);                    \
+        else BF_LAUNCH((mvdr_lcmv_kernel<MP_, KM_>), grid, dim3(256), 0, s, a, tile, tps);                                   \
     } while (0)
         if (p.km == 1) {
             if (p.mp == 4) BF_LAUNCH_ML(4, 1); else if (p.mp == 8) BF_LAUNCH_ML(8, 1); else if (p.mp == 16) BF_LAUNCH_ML(16, 1); else BF_LAUNCH_ML(32, 1);
@@ -222,7 +211,7 @@ hipError_t launch_mvdr_lcmv(const ChainPlan &p, const BinsArgs &a, int n_cus, hi
     // three-wavefront build spills 30 registers per lane and the spill traffic alone is 6 GB per 32 768 frames of 16 microphones: two
     // wavefronts at 211 registers are 7 % faster; without constraints (mvdr) three wavefronts win by 12 %
     if (p.bins == ChainBins::kCov2d) {
-        const dim3 grid((unsigned)(((long)tps * a.n_streams + 7) / 8 * 8 * ((kNQ + 15) / 16)));  // (unit, problem group) -> XCD-aware order in the kernel
+        const dim3 grid(g.cov2d_grid);  // (unit, problem group) -> XCD-aware order in the kernel
         if (rows) {
             if (p.z48) BF_LAUNCH((cov2d_rows_kernel<4, 2, false>), grid, dim3(256), 0, s, a, tile, tps);
             else BF_LAUNCH((cov2d_rows_kernel<4, 2, true>), grid, dim3(256), 0, s, a, tile, tps);
@@ -235,53 +224,14 @@ hipError_t launch_mvdr_lcmv(const ChainPlan &p, const BinsArgs &a, int n_cus, hi
         }
         return hipGetLastError();
     }
-    // kMvdrFast.  The problems that need a solve (FastPlan): 0, the in-band run inside 1 .. N/2-1, and N/2 / N/2+1 when in band
-    // (the irregular problems of quirk Q1, util.h:190-199: f[N/2] = 0, f[N/2+1] = -(N/2-1) sr/N)
-    const std::vector<double> fr = frequency_vector(kN, a.cfg.sample_rate);  // the table the other kernels read (a.freqs)
-    auto inb = [&](int q) {
-        const double f = std::fabs(fr[q_bin_host(q)]);
-        return f >= a.cfg.freq_min && f <= a.cfg.freq_max;
-    };
-    FastPlan fp;
-    fp.q_lo = 1;
-    while (fp.q_lo < kN / 2 && !inb(fp.q_lo)) ++fp.q_lo;
-    fp.n_main = 0;
-    while (fp.q_lo + fp.n_main < kN / 2 && inb(fp.q_lo + fp.n_main)) ++fp.n_main;
-    for (int q = fp.q_lo + fp.n_main; q < kN / 2; ++q)
-        if (inb(q)) return hipErrorInvalidValue;  // cannot happen: |f| rises with q below N/2
-    fp.n_extra = 0;
-    fp.extra_q[0] = fp.extra_q[1] = 0;
-    if (inb(kN / 2)) fp.extra_q[fp.n_extra++] = kN / 2;          // f[N/2] := 0 (quirk Q1): in band when 0 Hz is
-    if (inb(kN / 2 + 1)) fp.extra_q[fp.n_extra++] = kN / 2 + 1;  // the conjugate problem
-    fp.solve0 = (a.cfg.algo == BF_LCMV && inb(0)) ? 1 : 0;
-    fp.nb = 1 + fp.n_main + fp.n_extra;
-    // tile length: the wavefronts (64 lanes = 64 (tile, problem) pairs) should fill the 4 x CUs slots a whole number of times;
-    // cost of a choice = rounds x (frames walked + P warm-up frames); BF_MVDR_TILE forces a length (tests: lanes that straddle tiles,
-    // a short last tile)
-    const int ft_env = switches().mvdr_tile;
-    // resident wavefronts per CU: the prefetch buffers (2 x 2 MP rows of 1 KiB in LDS) and the register count of the instantiation
-    // that will run decide -- 8 microphones: one per SIMD (512 registers); fewer microphones: more
-    const int km = rows && p.km == 1 ? 2 : p.km;  // columns of the instantiation that runs
-    const int wpc = p.mp == 2 ? 16 : p.mp == 4 ? (km <= 2 ? 9 : 8) : p.mp == 6 ? (km == 1 ? 6 : 4) : 4;
-    const long slots = (long)n_cus * wpc, F = a.n_frames;
-    long best_t = 1;
-    double best_c = 1e300;
-    for (long t = 1; t <= 512 && t <= F; ++t) {
-        const long tiles = (F + t - 1) / t;
-        const long waves = (long)a.n_streams * ((tiles * fp.nb + 63) / 64);
-        const long rounds = (waves + slots - 1) / slots;
-        const double c = (double)rounds * (double)(t + a.cfg.past_windows + 2);
-        if (c <= best_c) { best_c = c; best_t = t; }
-    }
-    if (ft_env > 0) best_t = ft_env < F ? ft_env : F;
-    fp.tile = (int)best_t;
-    fp.tiles = (int)((F + best_t - 1) / best_t);
-    fp.waves_per_stream = (int)(((long)fp.tiles * fp.nb + 63) / 64);
-    if (!p.yh32 && !p.band_rows)  // f64x2 rows read in full (spectrum dump, other FFT sizes, a band up to Nyquist): the rows nobody solves read as zero (mvdr.cpp:103)
+    // kMvdrFast: one lane per (tile, problem that needs a solve); the rows nobody solves but the backward transform reads are zeroed first
+    const FastPlan &fp = g.fp;
+    const int km = g.fast_km;  // columns of the instantiation that runs
+    if (g.zero == ChainZero::kF64Rows)
         (void)hipMemsetAsync(a.Yh, 0, (size_t)a.n_streams * p.rows * a.n_frames * kYhStride * sizeof(f64x2), s);
-    else if (p.yh32 && p.yh_lo == 0 && fp.nb < kNQ)  // f32x2 rows that the backward transform reads in full (a band up to the Nyquist problems) while part of them is out of band
+    else if (g.zero == ChainZero::kF32Rows)
         (void)hipMemsetAsync(a.Yh, 0, (size_t)a.n_streams * p.rows * a.n_frames * kYhStride * sizeof(f32x2), s);
-    const dim3 grid((unsigned)((long)fp.waves_per_stream * a.n_streams));
+    const dim3 grid(g.fast_grid);
 #define BF_FAST_GO(MP_, KC_)                                                                                         \
     do {                                                                                                             \
         if (p.ctrack) {                                                                                              \

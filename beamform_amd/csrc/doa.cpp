@@ -113,6 +113,8 @@ int enqueue_stft(bf_doa *d, const float *xc, long n, long frames_ws, long mic_st
     ChainPlan front{};  // only the STFT of the chain runs here
     front.layout = d->layout;
     front.front = chain_stft_front(d->N, switches().stft_small, switches().stft_split);
+    front.geom.stft = chain_stft_geom(front.front, d->N, d->S, n, d->M, d->n_cus);  // run length and blocks (chain_geom.hpp)
+    if (!front.geom.stft.ok) return fail(d, BF_EINVAL, "bf_doa: batch too large for the STFT's launch geometry");
     DOA_HIP(d, d->ks->stft(front, sa, d->n_cus, s));
     return BF_OK;
 }

@@ -644,8 +644,8 @@ hipError_t launch_gss(const ChainPlan &p, const BinsArgs &a, hipStream_t s) {
     // kernel from two wavefronts per CU on
     // p.rows > 1 (bf_config.gss_out_sources): the _all variants of the same (MP, KM); one row: the kernels as they always were
     const bool all = p.rows > 1;
+    const dim3 grid(p.geom.bins.gss_grid);  // kGssLane: a wavefront per 64 problems of a stream; kGss: a group of MP lanes per (stream, problem)
     if (p.bins == ChainBins::kGssLane) {
-        const dim3 grid((unsigned)(a.n_streams * ((kNQ + 63) / 64)));
 #define BF_LAUNCH_GSS_LANE(MP_, KM_)                                                            \
     do {                                                                                        \
         if (all) BF_LAUNCH((gss_lane_kernel_all<MP_, KM_>), grid, dim3(64), 0, s, a);           \
@@ -659,11 +659,10 @@ hipError_t launch_gss(const ChainPlan &p, const BinsArgs &a, hipStream_t s) {
 #undef BF_LAUNCH_GSS_LANE
         return hipGetLastError();
     }
-    const int groups = a.n_streams * kNQ;
-#define BF_LAUNCH_GSS(MP_, KM_)                                                                                                          \
-    do {                                                                                                                                 \
-        if (all) BF_LAUNCH((gss_kernel_all<MP_, KM_>), dim3((groups + (256 / MP_) - 1) / (256 / MP_)), dim3(256), 0, s, a);             \
-        else BF_LAUNCH((gss_kernel<MP_, KM_>), dim3((groups + (256 / MP_) - 1) / (256 / MP_)), dim3(256), 0, s, a);                     \
+#define BF_LAUNCH_GSS(MP_, KM_)                                                         \
+    do {                                                                                \
+        if (all) BF_LAUNCH((gss_kernel_all<MP_, KM_>), grid, dim3(256), 0, s, a);       \
+        else BF_LAUNCH((gss_kernel<MP_, KM_>), grid, dim3(256), 0, s, a);               \
     } while (0)
     if (p.km == 1) {
         if (p.mp == 4) BF_LAUNCH_GSS(4, 1); else if (p.mp == 8) BF_LAUNCH_GSS(8, 1); else if (p.mp == 16) BF_LAUNCH_GSS(16, 1); else BF_LAUNCH_GSS(32, 1);
@@ -678,15 +677,13 @@ hipError_t launch_gss(const ChainPlan &p, const BinsArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_gsc_nlms(const ChainPlan &p, const float *aligned, float *y, float *state, long n_samples, int n_streams, int n_mics,
+hipError_t launch_gsc_nlms(const ChainPlan &p, const float *aligned, float *y, float *state, long n_samples, int, int n_mics,
                            const bf_config &cfg, hipStream_t s) {
-    const int fs = cfg.gsc_filter_size, nb = n_mics - 1, nbr = nb > 0 ? nb : 1;
+    const int fs = cfg.gsc_filter_size;
     const bool serial = p.tail == ChainTail::kNlms;
     const int kp = serial || p.tail == ChainTail::kNlmsPar ? p.t1 : p.t2;  // KPL
-    const size_t lds_serial = sizeof(float) * ((size_t)nbr * ((fs + 64 * kp + 8) | 1) + (size_t)nbr * ((64 * kp + 8) | 1) + 2 * fs + 16 +
-                                               (size_t)nbr * 64 + 64 + 16 + 64);
-    const size_t lds_par = sizeof(float) * ((size_t)nbr * ((fs + 64 * kp + 8) | 1) + 2 * fs + 64 * kp + 16 + (size_t)nbr * 64 + 64 + 64 + 64);
-    const size_t lds = serial ? lds_serial : lds_par;
+    const size_t lds = serial ? p.geom.tail.lds_serial : p.geom.tail.lds_par;  // dynamic LDS (chain_geom.hpp)
+    const dim3 grid(p.geom.tail.nlms_grid);                             // a block per stream
 #define BF_BY_KPL(GO_, ...)                  \
     do {                                     \
         if (kp == 1) GO_(__VA_ARGS__, 1);    \
@@ -696,7 +693,7 @@ hipError_t launch_gsc_nlms(const ChainPlan &p, const float *aligned, float *y, f
     if (p.tail == ChainTail::kNlmsMw) {  // the branches dealt out to NW wavefronts per stream, NBL branches each
         const int nw = p.t0, nbl = p.t1;
 #define BF_MW(NW_, NBL_, KPL_)                                                                                                     \
-    BF_LAUNCH((gsc_nlms_mw_kernel<NW_, NBL_, KPL_>), dim3((unsigned)n_streams), dim3(64 * NW_), lds, s, aligned, y, state, \
+    BF_LAUNCH((gsc_nlms_mw_kernel<NW_, NBL_, KPL_>), grid, dim3(64 * NW_), lds, s, aligned, y, state, \
                        n_samples, n_mics, fs, cfg.gsc_use_vad, cfg.gsc_vad_threshold, cfg.gsc_mu0, cfg.gsc_mu_max)
 #define BF_MW_K(NW_, NBL_) BF_BY_KPL(BF_MW, NW_, NBL_)
         if (nw == 8) {
@@ -713,10 +710,10 @@ hipError_t launch_gsc_nlms(const ChainPlan &p, const float *aligned, float *y, f
 #define BF_NLMS(NBM_, KPL_)                                                                                                        \
     do {                                                                                                                            \
         if (serial)                                                                                                                 \
-            BF_LAUNCH((gsc_nlms_kernel<NBM_, KPL_>), dim3((unsigned)n_streams), dim3(64), lds, s, aligned, y, state,       \
+            BF_LAUNCH((gsc_nlms_kernel<NBM_, KPL_>), grid, dim3(64), lds, s, aligned, y, state,       \
                                n_samples, n_mics, fs, cfg.gsc_use_vad, cfg.gsc_vad_threshold, cfg.gsc_mu0, cfg.gsc_mu_max);         \
         else                                                                                                                        \
-            BF_LAUNCH((gsc_nlms_par_kernel<NBM_, KPL_>), dim3((unsigned)n_streams), dim3(64), lds, s, aligned, y, state,   \
+            BF_LAUNCH((gsc_nlms_par_kernel<NBM_, KPL_>), grid, dim3(64), lds, s, aligned, y, state,   \
                                n_samples, n_mics, fs, cfg.gsc_use_vad, cfg.gsc_vad_threshold, cfg.gsc_mu0, cfg.gsc_mu_max);         \
     } while (0)
     if (p.t0 == 1) BF_BY_KPL(BF_NLMS, 1);
@@ -728,9 +725,8 @@ hipError_t launch_gsc_nlms(const ChainPlan &p, const float *aligned, float *y, f
     return hipGetLastError();
 }
 
-hipError_t launch_gsc_align(const BinsArgs &a, hipStream_t s) {
-    const long total = (long)a.n_streams * a.n_frames * kNQ;
-    BF_LAUNCH(gsc_align_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+hipError_t launch_gsc_align(const ChainPlan &p, const BinsArgs &a, hipStream_t s) {
+    BF_LAUNCH(gsc_align_kernel, dim3(p.geom.bins.ew_blocks), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -1532,18 +1532,16 @@ __global__ __launch_bounds__(256, 1) void stft_bins_split_kernel(StftArgs a, Bin
 
 // what follows the per-bin kernel, after launch_bins and after launch_stft_bins_fused alike
 hipError_t launch_bins_end(const ChainPlan &p, const BinsArgs &a, hipStream_t s) {
+    const ChainGeom &g = p.geom;
     // aux (|out_int|^2 per problem) lives behind the Yh rows: the plan sizes Yh for it
     double *aux = reinterpret_cast<double *>(a.Yh + (long)a.n_streams * a.n_frames * kYhStride);
-    if (p.rec == ChainRec::kRecursion) {
-        const int nthr = a.n_streams * kNQ;
-        BF_LAUNCH(mpf_recursion_kernel, dim3((nthr + 63) / 64), dim3(64), 0, s, a, aux);
-    }
+    if (p.rec == ChainRec::kRecursion) BF_LAUNCH(mpf_recursion_kernel, dim3(g.bins.lane_blocks), dim3(64), 0, s, a, aux);
 #if BF_NFFT == 1024
-    if (p.rec == ChainRec::kRecIstft) BF_LAUNCH(mpf_rec_istft_kernel, dim3((unsigned)a.n_streams), dim3(kRiThreads), 0, s, a, aux);
+    if (p.rec == ChainRec::kRecIstft) BF_LAUNCH(mpf_rec_istft_kernel, dim3(g.bins.rec_blocks), dim3(kRiThreads), 0, s, a, aux);
 #endif
     const hipError_t e = hipGetLastError();
     // (gss with its post-filter: the dump shows the filtered rows -- launch_gss_postfilter expands behind the filter)
-    return e == hipSuccess && p.expand && !p.postfilter ? launch_expand_spectrum(a.Yh, a.spectrum, (long)a.n_streams * p.rows * a.n_frames, s) : e;
+    return e == hipSuccess && p.expand && !p.postfilter ? launch_expand_spectrum(p, a.Yh, a.spectrum, (long)a.n_streams * p.rows * a.n_frames, s) : e;
 }
 
 // gss's post-filter over the rows the per-bin stage left in Yh (ChainPlan::postfilter), then the spectrum dump.  The filter leaves out_amp
@@ -1553,7 +1551,7 @@ hipError_t launch_gss_postfilter(const ChainPlan &p, const BinsArgs &a, hipStrea
     BinsArgs b = a;
     b.cfg.out_amp = 1.0;
     const int n_live = a.kp1 < p.rows ? a.kp1 : p.rows;  // rows that exist in this batch: min(sources, rows)
-    const dim3 grid((unsigned)((a.n_streams * kNQ + 63) / 64));
+    const dim3 grid(p.geom.bins.lane_blocks);
     switch (p.post_rp) {
         case 1: BF_LAUNCH(gss_postfilter_kernel<1>, grid, dim3(64), 0, s, b, n_live); break;
         case 2: BF_LAUNCH(gss_postfilter_kernel<2>, grid, dim3(64), 0, s, b, n_live); break;
@@ -1563,36 +1561,28 @@ hipError_t launch_gss_postfilter(const ChainPlan &p, const BinsArgs &a, hipStrea
         default: return hipErrorInvalidValue;
     }
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess && p.expand ? launch_expand_spectrum(a.Yh, a.spectrum, (long)a.n_streams * p.rows * a.n_frames, s) : e;
+    return e == hipSuccess && p.expand ? launch_expand_spectrum(p, a.Yh, a.spectrum, (long)a.n_streams * p.rows * a.n_frames, s) : e;
 }
 
-// The fused front of this FFT size: frames per round of a block, and the kernel with its block size.  N = 1024 walks single frames.
+// The fused front of this FFT size: the kernel with its block size and the integers it decodes its rounds from (FusedGeom).  N = 1024 walks
+// single frames: its frames per block and total frames are the rounds'.
 #if BF_NFFT == 1024
-#define BF_FUSED_FPR 1
-#define BF_FUSED_FRONT(L_, MP_, A_) BF_LAUNCH((stft_bins_w64_kernel<L_, MP_, A_>), grid, dim3(512), 0, s, a, b, rpb, total, aux, xtail)
-#define BF_FUSED_FRONT_TRACK(L_, MP_, A_) BF_LAUNCH((stft_bins_w64_track_kernel<L_, MP_, A_>), grid, dim3(512), 0, s, a, b, rpb, total, aux, xtail)
+#define BF_FUSED_FRONT(L_, MP_, A_) BF_LAUNCH((stft_bins_w64_kernel<L_, MP_, A_>), grid, dim3(512), 0, s, a, b, f.rpb, f.total, aux, xtail)
+#define BF_FUSED_FRONT_TRACK(L_, MP_, A_) BF_LAUNCH((stft_bins_w64_track_kernel<L_, MP_, A_>), grid, dim3(512), 0, s, a, b, f.rpb, f.total, aux, xtail)
 #elif BF_NFFT == 2048
-#define BF_FUSED_FPR (p.mp == 4 ? 2 : 1)
-#define BF_FUSED_FRONT(L_, MP_, A_) BF_LAUNCH((stft_bins_split_kernel<L_, MP_, A_>), grid, dim3(256), 0, s, a, b, rps, total, rpb, aux, xtail)
+#define BF_FUSED_FRONT(L_, MP_, A_) BF_LAUNCH((stft_bins_split_kernel<L_, MP_, A_>), grid, dim3(256), 0, s, a, b, f.rps, f.total, f.rpb, aux, xtail)
 #elif BF_NFFT < 1024
-#define BF_FUSED_FPR ((p.mp == 4 ? 4 : 2) * (1024 / kN))
-#define BF_FUSED_FRONT(L_, MP_, A_) BF_LAUNCH((stft_bins_small_kernel<L_, MP_, A_>), grid, dim3(256), 0, s, a, b, rps, total, rpb, aux, xtail)
+#define BF_FUSED_FRONT(L_, MP_, A_) BF_LAUNCH((stft_bins_small_kernel<L_, MP_, A_>), grid, dim3(256), 0, s, a, b, f.rps, f.total, f.rpb, aux, xtail)
 #endif
 
 // stft + per-bin stage of the history-free nodes in one launch (ChainPlan::fused())
-hipError_t launch_stft_bins_fused(const ChainPlan &p, const StftArgs &a, const BinsArgs &b, int n_cus, hipStream_t s) {
+hipError_t launch_stft_bins_fused(const ChainPlan &p, const StftArgs &a, const BinsArgs &b, int, hipStream_t s) {
 #ifdef BF_FUSED_FRONT
-    const int fpr = BF_FUSED_FPR;
-    const long rps = (a.n_frames + fpr - 1) / fpr;
-    const long total = rps * a.n_streams;  // rounds, numbered stream * rps + round; one contiguous range per block
-    long blocks = total < n_cus ? total : n_cus;
-    if (blocks < 1) blocks = 1;
-    const long rpb = (total + blocks - 1) / blocks;
-    const dim3 grid((unsigned)((total + rpb - 1) / rpb));
+    const FusedGeom &f = p.geom.fused;
+    const dim3 grid(f.grid);
     double *aux = reinterpret_cast<double *>(b.Yh + (long)b.n_streams * b.n_frames * kYhStride);
     f64x2 *xtail = a.Z;  // [stream][frame][2][MP]: the plan sizes the Z workspace for it
-    const long tail_items = (long)b.n_streams * b.n_frames * 2;
-    const unsigned tail_blocks = (unsigned)((tail_items + 255) / 256);
+    const unsigned tail_blocks = f.tail_blocks;
 #ifdef BF_FUSED_FRONT_TRACK  // a tracked batch (ChainPlan::track): the twins that resolve the steering table per frame
 #define BF_FUSED_GO_TRACK(L_, MP_, A_)                                                                                     \
     if (p.track) {                                                                                                         \
@@ -1627,13 +1617,12 @@ hipError_t launch_stft_bins_fused(const ChainPlan &p, const StftArgs &a, const B
     const hipError_t e = hipGetLastError();
     return e != hipSuccess ? e : launch_bins_end(p, b, s);
 #else
-    (void)p; (void)a; (void)b; (void)n_cus; (void)s;
+    (void)p; (void)a; (void)b; (void)s;
     return hipErrorInvalidValue;  // no fused front at this size: the plan never names one
 #endif
 }
 #undef BF_FUSED_FRONT
 #undef BF_FUSED_FRONT_TRACK
-#undef BF_FUSED_FPR
 
 // MP_ = 4 / 8 / 16 / 32 of the plan -> the instantiation
 #define BF_BY_MP(GO_)                \
@@ -1646,8 +1635,7 @@ hipError_t launch_stft_bins_fused(const ChainPlan &p, const StftArgs &a, const B
 
 hipError_t launch_mpf_mask(const ChainPlan &p, const BinsArgs &a, hipStream_t s) {
     double *aux = reinterpret_cast<double *>(a.Yh + (long)a.n_streams * a.n_frames * kYhStride);
-    const long total = (long)a.n_streams * a.n_frames * kNQ;
-    const unsigned blocks = (unsigned)((total + 255) / 256);
+    const unsigned blocks = p.geom.bins.ew_blocks;
 #define BF_MASK(MP_) BF_LAUNCH((mpf_mask_kernel<MP_>), dim3(blocks), dim3(256), 0, s, a, aux)
 #define BF_MASK_TRACK(MP_) BF_LAUNCH((mpf_mask_track_kernel<MP_>), dim3(blocks), dim3(256), 0, s, a, aux)
     if (p.track) BF_BY_MP(BF_MASK_TRACK);
@@ -1658,8 +1646,7 @@ hipError_t launch_mpf_mask(const ChainPlan &p, const BinsArgs &a, hipStream_t s)
 }
 
 hipError_t launch_pointwise(const ChainPlan &p, const BinsArgs &a, hipStream_t s) {
-    const long total = (long)a.n_streams * a.n_frames * kNQ;
-    const unsigned blocks = (unsigned)((total + 255) / 256);
+    const unsigned blocks = p.geom.bins.ew_blocks;
 #define BF_PW_DAS(MP_) BF_LAUNCH((pointwise_bins_kernel<MP_, BF_DAS>), dim3(blocks), dim3(256), 0, s, a)
 #define BF_PW_PHASE(MP_) BF_LAUNCH((pointwise_bins_kernel<MP_, BF_PHASE>), dim3(blocks), dim3(256), 0, s, a)
 #define BF_PW_DAS_TRACK(MP_) BF_LAUNCH((pointwise_track_kernel<MP_, BF_DAS>), dim3(blocks), dim3(256), 0, s, a)
@@ -1677,8 +1664,8 @@ hipError_t launch_pointwise(const ChainPlan &p, const BinsArgs &a, hipStream_t s
 }
 #undef BF_BY_MP
 
-hipError_t launch_mcra_node(const BinsArgs &a, hipStream_t s) {
-    BF_LAUNCH(mcra_node_kernel, dim3((a.n_streams * kNQ + 63) / 64), dim3(64), 0, s, a);
+hipError_t launch_mcra_node(const ChainPlan &p, const BinsArgs &a, hipStream_t s) {
+    BF_LAUNCH(mcra_node_kernel, dim3(p.geom.bins.lane_blocks), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

@@ -90,20 +90,12 @@ class BinPipelineImpl : public Engine {
         ENGINE_HIP(d_win_.upload(sqrt_hann(N_)));
         freqs_ = frequency_vector(N_, cfg_.sample_rate);
         ENGINE_HIP(d_freq_.upload(freqs_));
-        skip_lo_ = N_; band_yh_hi_ = NQ_ - 1;
-        if (band_node_) {
-            int klo = N_, khi = 0;  // the lowest and the highest in-band problem past 0 (problem q = bin q for q <= N/2 + 1)
-            for (int q = 1; q < NQ_; ++q) {
-                const double f = std::fabs(freqs_[q]);
-                if (f >= cfg_.freq_min && f <= cfg_.freq_max) { if (q < klo) klo = q; khi = q; }
-            }
-            // the STFT stores everything except, for the band-limited nodes, the bins between the highest in-band bin k and its mirror N-k
-            // (quirk Q1 makes bins 511..513 irregular: only skip when the band ends below them)
-            if (khi < N_ / 2 - 2) { skip_lo_ = khi; skip_hi_ = N_ - khi; }
-            // mvdr / lcmv rows in front of a backward transform: only problem 0 and the band's problems exist (everything else is zero,
-            // mvdr.cpp:103, and is neither written nor read)
-            if (cov_node_ && khi < N_ / 2 - 1 && klo <= khi) { band_yh_lo_ = klo; band_yh_hi_ = khi; }
-            else if (cov_node_ && klo > khi) { band_yh_lo_ = 1; band_yh_hi_ = 0; }  // empty band: only problem 0
+        // the band, scanned once: what the STFT may skip, the rows mvdr / lcmv leave for the backward transform, the problems
+        // mvdr_fast_kernel enumerates (chain_geom.hpp)
+        band_ = band_plan(N_, cfg_.sample_rate, cfg_.freq_min, cfg_.freq_max, cfg_.algo);
+        if (!band_.ok) {
+            err_ = "the band [freq_min, freq_max] is not one run of bins";  // (cannot happen: |f| rises with the bin below N/2)
+            return BF_EINVAL;
         }
         for (auto &b : d_steer_) ENGINE_HIP(b.alloc(steer_elems()));
         if (das_one_launch_shape()) {
@@ -274,8 +266,7 @@ class BinPipelineImpl : public Engine {
     const bool post_filter_ = cfg_.algo == BF_GSS && cfg_.gss_postfilter != 0;  // the multi-source post-filter runs behind the gss kernels
     const bool post_amp_ = band_node_;                                    // out_amp is applied behind the backward transform
     const bool yraw_target_ = cfg_.algo == BF_PHASEMPF || time_node_;     // the backward transform feeds the smoother / the NLMS stage through d_yraw_
-    int skip_lo_, skip_hi_ = 0;        // StftArgs::skip_lo / skip_hi (init(); N_, 0 = store everything)
-    int band_yh_lo_ = 0, band_yh_hi_;  // BinsArgs::yh_lo / yh_hi of a batch with band-limited rows (init(); every problem unless mvdr / lcmv)
+    BandPlan band_{};  // init(): StftArgs::skip_lo / skip_hi, the band-limited rows of mvdr / lcmv, FastPlan's problems (chain_geom.hpp)
     bool z48_ = false;
     size_t zsz_ = sizeof(f64x2);  // bytes per packed-spectrum element
     int H_ = 512, N_ = 1024, NQ_ = 514, YS_ = 516;  // hop, FFT size, problems per frame, row stride of Yh
@@ -359,11 +350,20 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
     // 3.0: per-tile launches underfill the chip and the per-bin kernels lose their parallelism over time) -- DESIGN.md 3.2
     const Switches &sw = switches();
     // everything this batch launches, its row formats and workspace sizes: decided once, from values (chain_plan.hpp)
-    const ChainPlan p = chain_decide(ChainShape{cfg_.algo, N_, layout, M_, S_, cfg_.n_dirs > 1 ? cfg_.n_dirs : 1, snap.kp1, cfg_.past_windows,
-                                                cfg_.precision, spectrum != nullptr, F, n_cus_, cfg_.gsc_filter_size, cfg_.smooth_size,
-                                                band_yh_lo_, band_yh_hi_, (reinterpret_cast<size_t>(y) & 15) == 0, sw.fused_bins,
-                                                sw.stft_small, sw.stft_split, sw.mvdr_group, sw.gss_group, sw.gsc_serial, cfg_.algo == BF_GSS ? R_ : 1, snap.track != nullptr && snap.track_cols == 0,
-                                                snap.track != nullptr ? snap.track_cols : 0, post_filter_ ? 1 : 0, cfg_.algo == BF_LCMV ? R_ : 1});
+    const ChainShape shape{cfg_.algo, N_, layout, M_, S_, cfg_.n_dirs > 1 ? cfg_.n_dirs : 1, snap.kp1, cfg_.past_windows,
+                           cfg_.precision, spectrum != nullptr, F, n_cus_, cfg_.gsc_filter_size, cfg_.smooth_size,
+                           band_.yh_lo, band_.yh_hi, (reinterpret_cast<size_t>(y) & 15) == 0, sw.fused_bins,
+                           sw.stft_small, sw.stft_split, sw.mvdr_group, sw.gss_group, sw.gsc_serial, cfg_.algo == BF_GSS ? R_ : 1,
+                           snap.track != nullptr && snap.track_cols == 0, snap.track != nullptr ? snap.track_cols : 0, post_filter_ ? 1 : 0,
+                           cfg_.algo == BF_LCMV ? R_ : 1, sw.mvdr_tile};
+    ChainPlan p = chain_decide(shape);
+    // ... and how it is cut into runs, tiles and rounds, with every grid (chain_geom.hpp); a batch whose geometry does not fit the kernels'
+    // integers is refused here, before anything is enqueued
+    p.geom = chain_geom(shape, p, band_);
+    if (!p.geom.ok) {
+        err_ = "batch too large: a run, tile or grid count of its launch geometry exceeds what the kernels take";
+        return BF_EINVAL;
+    }
     float *const hist = d_hist2_[hist_cur_].get();
     const long FT = Phist_ + F;  // frames in the Z workspace per stream
     ENGINE_HIP(d_Z_.reserve(p.z_bytes));
@@ -383,7 +383,7 @@ int BinPipelineImpl::run_chain(const float *x, long F, float *y, f64x2 *spectrum
     sa.x = x; sa.hist = hist; sa.Z = Z; sa.tw = d_tw_.get(); sa.win = d_win_.get();
     sa.n_frames = F; sa.frames_ws = FT; sa.frame_off = Phist_; sa.mic_stride = mic_stride;
     sa.stream_stride_x = (long)M_ * F * H_; sa.n_streams = S_; sa.n_mics = M_; sa.n_fft_mics = MF_; sa.layout = layout;
-    sa.skip_lo = skip_lo_; sa.skip_hi = skip_hi_;
+    sa.skip_lo = band_.skip_lo; sa.skip_hi = band_.skip_hi;
     sa.z48 = p.z48 ? 1 : 0; sa.run_len = 1; sa.tw_w64 = d_tw_w64_.get();
     sa.halve = cov_node_ ? 1 : 0;
     if (time_node_ && spectrum) {  // time-domain node: there is no single y_fft; the dump reads as zeros

@@ -8,17 +8,17 @@
 namespace bf {
 namespace BF_NTAG {
 
-hipError_t launch_bins(const ChainPlan &p, const BinsArgs &a, int n_cus, hipStream_t s) {
+hipError_t launch_bins(const ChainPlan &p, const BinsArgs &a, int, hipStream_t s) {
     hipError_t e = hipErrorInvalidValue;  // (kFusedTail: the fused front ran the per-bin stage)
     switch (p.bins) {
         case ChainBins::kFusedTail: break;
         case ChainBins::kPointwise: e = launch_pointwise(p, a, s); break;
         case ChainBins::kMpfMask: e = launch_mpf_mask(p, a, s); break;
-        case ChainBins::kMcra: e = launch_mcra_node(a, s); break;
-        case ChainBins::kGscAlign: e = launch_gsc_align(a, s); break;
+        case ChainBins::kMcra: e = launch_mcra_node(p, a, s); break;
+        case ChainBins::kGscAlign: e = launch_gsc_align(p, a, s); break;
         case ChainBins::kMvdrFast:
         case ChainBins::kCov2d:
-        case ChainBins::kMvdrLcmv: e = launch_mvdr_lcmv(p, a, n_cus, s); break;
+        case ChainBins::kMvdrLcmv: e = launch_mvdr_lcmv(p, a, s); break;
         case ChainBins::kGss:
         case ChainBins::kGssLane: e = launch_gss(p, a, s); break;
     }

@@ -164,26 +164,29 @@ hipError_t enqueue_das_f64(DasF64Args a, const DasF64Launch &d, float *scratch, 
 
 #ifdef BF_NFFT
 // Every launcher carries out its stage of a ChainPlan (chain_plan.hpp): the plan names the kernel and its template arguments, the launcher
-// maps them to an instantiation and computes the launch geometry.
+// maps them to an instantiation; grids, block counts and the integers the kernels decode their work from come from the plan's geometry
+// (ChainPlan::geom, chain_geom.hpp), decided beside the plan.  No launcher computes any of them, reads a switch or looks at the CU count:
+// the `int` that four of them still take is ignored (the signatures of KernelSet are what the host harness's stubs, tests/host_tsan,
+// are written against).
 namespace BF_NTAG {
-hipError_t launch_stft(const ChainPlan &p, const StftArgs &a, int n_cus, hipStream_t s);
-hipError_t launch_bins(const ChainPlan &p, const BinsArgs &a, int n_cus, hipStream_t s);
+hipError_t launch_stft(const ChainPlan &p, const StftArgs &a, int, hipStream_t s);
+hipError_t launch_bins(const ChainPlan &p, const BinsArgs &a, int, hipStream_t s);
 // stft + per-bin stage in one launch for the nodes without a frame history (das fp64, phase, phasempf; N = 128 ... 2048, <= 8 mics,
 // one look direction): the spectra stay in LDS.  mask_kernels.hip
-hipError_t launch_stft_bins_fused(const ChainPlan &p, const StftArgs &a, const BinsArgs &b, int n_cus, hipStream_t s);
+hipError_t launch_stft_bins_fused(const ChainPlan &p, const StftArgs &a, const BinsArgs &b, int, hipStream_t s);
 // per-node launchers behind launch_bins (one translation unit per kernel family)
 hipError_t launch_pointwise(const ChainPlan &p, const BinsArgs &a, hipStream_t s);              // das (fp64), phase: mask_kernels.hip
 hipError_t launch_mpf_mask(const ChainPlan &p, const BinsArgs &a, hipStream_t s);               // phasempf: mask_kernels.hip
-hipError_t launch_mcra_node(const BinsArgs &a, hipStream_t s);                                  // mask_kernels.hip
-hipError_t launch_mvdr_lcmv(const ChainPlan &p, const BinsArgs &a, int n_cus, hipStream_t s);   // cov_kernels.hip
+hipError_t launch_mcra_node(const ChainPlan &p, const BinsArgs &a, hipStream_t s);              // mask_kernels.hip
+hipError_t launch_mvdr_lcmv(const ChainPlan &p, const BinsArgs &a, hipStream_t s);              // cov_kernels.hip
 hipError_t launch_gss(const ChainPlan &p, const BinsArgs &a, hipStream_t s);                    // gsc_gss_kernels.hip
-hipError_t launch_gsc_align(const BinsArgs &a, hipStream_t s);                                  // gsc_gss_kernels.hip
+hipError_t launch_gsc_align(const ChainPlan &p, const BinsArgs &a, hipStream_t s);              // gsc_gss_kernels.hip
 // what follows the per-bin kernel on the chained and on the fused route: phasempf's recursion over the frames, the spectrum dump.  mask_kernels.hip
 hipError_t launch_bins_end(const ChainPlan &p, const BinsArgs &a, hipStream_t s);
 // gss with bf_config.gss_postfilter: gss_postfilter_kernel in place over the rows of the per-bin stage, then the spectrum dump.  mask_kernels.hip
 hipError_t launch_gss_postfilter(const ChainPlan &p, const BinsArgs &a, hipStream_t s);
-hipError_t launch_expand_spectrum(const f64x2 *Yh, f64x2 *spectrum, long frames, hipStream_t s);  // stft_istft.hip
-hipError_t launch_istft(const ChainPlan &p, const IstftArgs &a, int n_cus, hipStream_t s);
+hipError_t launch_expand_spectrum(const ChainPlan &p, const f64x2 *Yh, f64x2 *spectrum, long frames, hipStream_t s);  // stft_istft.hip
+hipError_t launch_istft(const ChainPlan &p, const IstftArgs &a, int, hipStream_t s);
 // gsc.cpp:120-181: the sample-serial float32 NLMS sidelobe canceller over the phase-aligned microphone signals.
 // aligned = [stream][mic][n_samples] (ISTFT output of the align pass), y = [stream][n_samples],
 // state = [stream][(2*(M-1) + 1) * filter_size] floats: block_matrix rows, filter rows, last_outputs (reference order).

@@ -1170,79 +1170,47 @@ __global__ void smooth_state_kernel(const float *yraw, double *state, long n, in
 
 }  // namespace
 
-// the layout x z48 instantiations of one STFT kernel family, `blocks` blocks of 256 threads on the arguments b
-#define BF_STFT_GO(K_)                                                                       \
-    do {                                                                                     \
-        if (p.layout == 0) {                                                                 \
-            if (p.z48) BF_LAUNCH((K_<0, true>), dim3((unsigned)blocks), dim3(256), 0, s, b); \
-            else BF_LAUNCH((K_<0, false>), dim3((unsigned)blocks), dim3(256), 0, s, b);      \
-        } else {                                                                             \
-            if (p.z48) BF_LAUNCH((K_<1, true>), dim3((unsigned)blocks), dim3(256), 0, s, b); \
-            else BF_LAUNCH((K_<1, false>), dim3((unsigned)blocks), dim3(256), 0, s, b);      \
-        }                                                                                    \
+// the layout x z48 instantiations of one STFT kernel family, g.blocks blocks of 256 threads on the arguments b
+#define BF_STFT_GO(K_)                                                                     \
+    do {                                                                                   \
+        if (p.layout == 0) {                                                               \
+            if (p.z48) BF_LAUNCH((K_<0, true>), dim3(g.blocks), dim3(256), 0, s, b);       \
+            else BF_LAUNCH((K_<0, false>), dim3(g.blocks), dim3(256), 0, s, b);            \
+        } else {                                                                           \
+            if (p.z48) BF_LAUNCH((K_<1, true>), dim3(g.blocks), dim3(256), 0, s, b);       \
+            else BF_LAUNCH((K_<1, false>), dim3(g.blocks), dim3(256), 0, s, b);            \
+        }                                                                                  \
     } while (0)
 
-hipError_t launch_stft(const ChainPlan &p, const StftArgs &a, int n_cus, hipStream_t s) {
-    const long np = (a.n_fft_mics + 1) / 2;
+// run length and blocks: chain_stft_geom (chain_geom.hpp)
+hipError_t launch_stft(const ChainPlan &p, const StftArgs &a, int, hipStream_t s) {
+    const StftGeom &g = p.geom.stft;
+    if (!g.ok) return hipErrorInvalidValue;
     StftArgs b = a;
+    b.run_len = g.run_len;
 #if BF_NFFT == 1024
     if (p.front == ChainFront::kStft) {
-        // 256 threads, twiddles in LDS: a 512-thread block spills (44 VGPRs) and twiddles read from global memory cost 40 % (measured)
-        constexpr int halves = 256 / 32;
-        // frames per run: one run per half-wavefront slot (one block per CU) when the batch is long enough -- the first frame of a
-        // run fetches its leading hop a second time (1/run_len of the input)
-        const long slots = (long)n_cus * halves;  // (1 / 2 / 4 / 8 runs per slot measured: 0.713 / 0.720 / 0.732 / 0.739 ms)
-        long L = ((long)a.n_streams * a.n_frames * np + slots - 1) / slots;
-        if (L < 1) L = 1;
-        if (L > 256) L = 256;
-        b.run_len = (int)L;
-        const long total = (long)a.n_streams * ((a.n_frames + L - 1) / L) * np;
-        long blocks = (total + halves - 1) / halves;
-        const long cap = (long)n_cus * 4;
-        if (blocks > cap) blocks = cap;
         BF_STFT_GO(stft_kernel);
         return hipGetLastError();
     }
 #else
 #if BF_NFFT == 128 || BF_NFFT == 256 || BF_NFFT == 512
     if (p.front == ChainFront::kStftSmall) {  // the in-register kernel
-        constexpr int halves = 8;
-        const long slots = (long)n_cus * halves * 2;  // two rounds of runs per half-wavefront slot
-        long L = ((long)a.n_streams * a.n_frames * np + slots - 1) / slots;
-        L = ((L + kG - 1) / kG) * kG;  // whole groups of frames
-        if (L > 256) L = 256;
-        if (L < kG) L = kG;
-        b.run_len = (int)L;
-        const long items = (long)a.n_streams * ((a.n_frames + L - 1) / L) * np;
-        long blocks = (items + halves - 1) / halves;
-        if (blocks > (long)n_cus * 4) blocks = (long)n_cus * 4;
         BF_STFT_GO(stft_small_kernel);
         return hipGetLastError();
     }
 #endif
 #if BF_NFFT == 2048
     if (p.front == ChainFront::kStftWave2048) {  // one 2048-point transform per full wavefront
-        constexpr int waves = 4;
-        const long slots = (long)n_cus * waves * 2;
-        long L = ((long)a.n_streams * a.n_frames * np + slots - 1) / slots;
-        if (L > 256) L = 256;
-        if (L < 1) L = 1;
-        b.run_len = (int)L;
-        const long items = (long)a.n_streams * ((a.n_frames + L - 1) / L) * np;
-        long blocks = (items + waves - 1) / waves;
-        if (blocks > (long)n_cus * 4) blocks = (long)n_cus * 4;
         BF_STFT_GO(stft_wave2048_kernel);
         return hipGetLastError();
     }
 #endif
     if (p.front == ChainFront::kStftGeneric) {
-        const long total = (long)a.n_streams * a.n_frames * np;
-        long blocks = total < (long)n_cus * 8 ? total : (long)n_cus * 8;
-        if (blocks < 1) blocks = 1;
         if (p.layout == 0)
-            BF_LAUNCH(stft_generic_kernel<0>, dim3((unsigned)blocks), dim3(kGenBlock), 0, s, b);
+            BF_LAUNCH(stft_generic_kernel<0>, dim3(g.blocks), dim3(kGenBlock), 0, s, b);
         else
-            BF_LAUNCH(stft_generic_kernel<1>, dim3((unsigned)blocks), dim3(kGenBlock), 0, s, b);
+            BF_LAUNCH(stft_generic_kernel<1>, dim3(g.blocks), dim3(kGenBlock), 0, s, b);
         return hipGetLastError();
     }
 #endif
@@ -1250,70 +1218,35 @@ hipError_t launch_stft(const ChainPlan &p, const StftArgs &a, int n_cus, hipStre
 }
 #undef BF_STFT_GO
 
-hipError_t launch_istft(const ChainPlan &p, const IstftArgs &a, int n_cus, hipStream_t s) {
+// frames or pairs per run, runs per stream and grids: ChainPlan::geom (chain_geom.hpp)
+hipError_t launch_istft(const ChainPlan &p, const IstftArgs &a, int, hipStream_t s) {
+    const IstftGeom &g = p.geom.istft;
     switch (p.istft) {
 #if BF_NFFT == 1024
-        case ChainIstft::kF32: {  // fp32 backward transform of f32x2 rows, one frame per FFT
-            // two blocks per CU are resident (213-228 VGPRs): one chunk per half-wavefront slot = one round; every chunk recomputes one
-            // warm-up frame.  Measured per 65 536 frames: x1 0.181, x2 0.127, x3 0.160 (round 2's value), x4 0.134, x8 0.148 ms
-            long slots = (long)n_cus * kI32Halves * 2 / a.n_streams;
-            if (slots < 1) slots = 1;
-            long cps = slots < a.n_frames ? slots : a.n_frames;
-            const long fpc = (a.n_frames + cps - 1) / cps;
-            cps = (a.n_frames + fpc - 1) / fpc;
-            const long chunks = cps * a.n_streams;
-            const dim3 grid((unsigned)((chunks + kI32Halves - 1) / kI32Halves));
-            BF_LAUNCH(istft32_kernel, grid, dim3(kI32Block), 0, s, a, (int)fpc, (int)cps);
+        case ChainIstft::kF32:  // fp32 backward transform of f32x2 rows, one frame per FFT
+            static_assert(kI32Halves == 8, "chain_geom.hpp counts 8 chunks per block");
+            BF_LAUNCH(istft32_kernel, dim3(g.grid), dim3(kI32Block), 0, s, a, g.per_run, g.runs_per_stream);
             break;
-        }
-        case ChainIstft::kW64: {
-            const long pairs = (a.n_frames + 1) / 2;
-            // one run per wavefront slot (2 blocks x 4 wavefronts per CU), every run recomputes one warm-up frame
-            long slots = (long)n_cus * kIw64Waves * 2 / a.n_streams;
-            if (slots < 1) slots = 1;
-            long rps = slots < pairs ? slots : pairs;
-            const long ppr = (pairs + rps - 1) / rps;
-            rps = (pairs + ppr - 1) / ppr;
-            const long runs = rps * a.n_streams;
-            const dim3 grid((unsigned)((runs + kIw64Waves - 1) / kIw64Waves));
-            if (p.band_rows) BF_LAUNCH(istft_w64_kernel<true>, grid, dim3(kIw64Block), 0, s, a, (int)ppr, (int)rps);  // band-limited rows (mvdr / lcmv)
-            else BF_LAUNCH(istft_w64_kernel<false>, grid, dim3(kIw64Block), 0, s, a, (int)ppr, (int)rps);
+        case ChainIstft::kW64:
+            static_assert(kIw64Waves == 4, "chain_geom.hpp counts 4 runs per block");
+            if (p.band_rows) BF_LAUNCH(istft_w64_kernel<true>, dim3(g.grid), dim3(kIw64Block), 0, s, a, g.per_run, g.runs_per_stream);  // band-limited rows (mvdr / lcmv)
+            else BF_LAUNCH(istft_w64_kernel<false>, dim3(g.grid), dim3(kIw64Block), 0, s, a, g.per_run, g.runs_per_stream);
             break;
-        }
 #else
 #if BF_NFFT == 128 || BF_NFFT == 256 || BF_NFFT == 512
-        case ChainIstft::kSmall: {  // backward transform, window and overlap-add in registers
-            constexpr int halves = 8;
-            const long slots = (long)n_cus * halves;
-            long L = ((long)a.n_streams * a.n_frames + slots - 1) / slots;
-            L = ((L + kG - 1) / kG) * kG;  // whole groups of frames
-            if (L < 4 * kG) L = 4 * kG;    // a run recomputes one group
-            const long items = (long)a.n_streams * ((a.n_frames + L - 1) / L);
-            long blocks = (items + halves - 1) / halves;
-            BF_LAUNCH(istft_small_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, (int)L);
+        case ChainIstft::kSmall:  // backward transform, window and overlap-add in registers
+            BF_LAUNCH(istft_small_kernel, dim3(g.grid), dim3(256), 0, s, a, g.per_run);
             break;
-        }
 #endif
 #if BF_NFFT == 2048
-        case ChainIstft::kSplit: {  // one FFT-1024 per frame, window and overlap-add in registers
-            constexpr int halves = 8;
-            const long slots = (long)n_cus * halves;
-            long L = ((long)a.n_streams * a.n_frames + slots - 1) / slots;
-            if (L < 8) L = 8;  // a run recomputes one frame
-            const long items = (long)a.n_streams * ((a.n_frames + L - 1) / L);
-            BF_LAUNCH(istft_split_kernel, dim3((unsigned)((items + halves - 1) / halves)), dim3(256), 0, s, a, (int)L);
+        case ChainIstft::kSplit:  // one FFT-1024 per frame, window and overlap-add in registers
+            BF_LAUNCH(istft_split_kernel, dim3(g.grid), dim3(256), 0, s, a, g.per_run);
             break;
-        }
 #endif
-        case ChainIstft::kGeneric: {  // windowed frames through a.frames, overlap-added by a second pass
-            const long total = (long)a.n_streams * a.n_frames;
-            long blocks = total < (long)n_cus * 8 ? total : (long)n_cus * 8;
-            if (blocks < 1) blocks = 1;
-            BF_LAUNCH(istft_generic_kernel, dim3((unsigned)blocks), dim3(kGenBlock), 0, s, a);
-            const long samples = total * kHop;
-            BF_LAUNCH(ola_generic_kernel, dim3((unsigned)((samples + 255) / 256)), dim3(256), 0, s, a);
+        case ChainIstft::kGeneric:  // windowed frames through a.frames, overlap-added by a second pass
+            BF_LAUNCH(istft_generic_kernel, dim3(g.grid), dim3(kGenBlock), 0, s, a);
+            BF_LAUNCH(ola_generic_kernel, dim3(g.ola_grid), dim3(256), 0, s, a);
             break;
-        }
 #endif
         default: return hipErrorInvalidValue;  // a backward transform this size does not have: the plan never names one
     }
@@ -1321,12 +1254,11 @@ hipError_t launch_istft(const ChainPlan &p, const IstftArgs &a, int n_cus, hipSt
 }
 
 hipError_t launch_smooth(const ChainPlan &p, const float *yraw, float *y, double *state, long n_frames, int n_streams, hipStream_t s) {
+    const TailGeom &g = p.geom.tail;
     const long n = n_frames * kHop;
-    const long total = n * n_streams;
-    const dim3 g4((unsigned)((total / 4 + 255) / 256));
-#define BF_SM4(SZ_) BF_LAUNCH((smooth4_kernel<SZ_>), g4, dim3(256), 0, s, yraw, y, state, n, n_streams)
+#define BF_SM4(SZ_) BF_LAUNCH((smooth4_kernel<SZ_>), dim3(g.smooth4_grid), dim3(256), 0, s, yraw, y, state, n, n_streams)
     if (p.tail == ChainTail::kSmooth)
-        BF_LAUNCH(smooth_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, yraw, y, state, n, n_streams, p.t0);
+        BF_LAUNCH(smooth_kernel, dim3(g.smooth_grid), dim3(256), 0, s, yraw, y, state, n, n_streams, p.t0);
     else if (p.t0 == 1) BF_SM4(1);
     else if (p.t0 == 2) BF_SM4(2);
     else if (p.t0 == 3) BF_SM4(3);
@@ -1336,13 +1268,12 @@ hipError_t launch_smooth(const ChainPlan &p, const float *yraw, float *y, double
     else if (p.t0 == 7) BF_SM4(7);
     else BF_SM4(8);
 #undef BF_SM4
-    BF_LAUNCH(smooth_state_kernel, dim3((unsigned)((64 * n_streams + 255) / 256)), dim3(256), 0, s, yraw, state, n,
-                       n_streams);
+    BF_LAUNCH(smooth_state_kernel, dim3(g.state_grid), dim3(256), 0, s, yraw, state, n, n_streams);
     return hipGetLastError();
 }
 
-hipError_t launch_expand_spectrum(const f64x2 *Yh, f64x2 *spectrum, long frames, hipStream_t s) {
-    BF_LAUNCH(expand_spectrum_kernel, dim3((unsigned)((frames * kN + 255) / 256)), dim3(256), 0, s, Yh, spectrum, frames);
+hipError_t launch_expand_spectrum(const ChainPlan &p, const f64x2 *Yh, f64x2 *spectrum, long frames, hipStream_t s) {
+    BF_LAUNCH(expand_spectrum_kernel, dim3(p.geom.bins.expand_blocks), dim3(256), 0, s, Yh, spectrum, frames);
     return hipGetLastError();
 }
 

@@ -19,7 +19,8 @@ struct Switches {
     const bool stft_small = num("BF_STFT_SMALL", 1) != 0;      // off only when set and equal to 0: the generic kernels at N = 128 / 256 / 512
     const bool stft_split = num("BF_STFT_SPLIT", 1) != 0;      // likewise: the generic kernels at N = 2048
     const bool mvdr_group = num("BF_MVDR_GROUP", 0) != 0;      // on when set and non-zero: the group-per-problem kernel only
-    const int mvdr_tile = num("BF_MVDR_TILE", 0);              // tile length of mvdr_fast_kernel (0 = chosen by cost)
+    const int mvdr_tile = num("BF_MVDR_TILE", 0);              // tile length of mvdr_fast_kernel (0 = chosen by cost); held to min(value, frames, 512),
+                                                               // the slack the spectra workspace has for the prefetch past a short last tile (chain_geom.hpp)
     const int gss_group = num("BF_GSS_GROUP", -1);             // 1 / 0 force the group / the lane kernel (-1 = by shape)
     const bool gsc_serial = num("BF_GSC_SERIAL", 0) == 1;      // on only when equal to 1: the sums in the reference's tap order
 };

@@ -3,8 +3,6 @@ emul_chain_plan (integers only), formatted in Python into the kernel names that 
 import ctypes as C
 import os
 
-import numpy as np
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NODES = ("das", "mvdr", "lcmv", "gss", "phase", "phasempf", "mcra", "gsc")
 ALGO = {n: i for i, n in enumerate(NODES)}                     # bf_algo
@@ -53,17 +51,14 @@ def chain_kernels(d, nfft):
 
 
 def band_limits(lib, algo, nfft, freq_min, freq_max, sample_rate=48000.0):
-    """BinPipelineImpl::init's band_yh_lo_ / band_yh_hi_: the in-band problems of mvdr / lcmv past problem 0, when the band ends below the
-    Nyquist problems; (1, 0) for an empty band; every problem otherwise."""
-    nq = nfft // 2 + 2
-    if algo not in ("mvdr", "lcmv"):
-        return 0, nq - 1
-    f = np.empty(nfft)
-    lib.emul_freqs(nfft, C.c_double(sample_rate), f.ctypes.data_as(C.c_void_p))
-    inb = [q for q in range(1, nq) if freq_min <= abs(f[q]) <= freq_max]
-    if not inb:
-        return 1, 0
-    return (inb[0], inb[-1]) if inb[-1] < nfft // 2 - 1 else (0, nq - 1)
+    """The handle's band_yh_lo / band_yh_hi (csrc/chain_geom.hpp band_plan, through emul_band_plan): the in-band problems of mvdr / lcmv
+    past problem 0, when the band ends below the Nyquist problems; (1, 0) for an empty band; every problem otherwise.
+    (tests/chain_geom_ref.py restates the scan on its own; tests/test_chain_geom_cpu.py compares the two.)"""
+    out = (C.c_long * 12)()
+    lib.emul_band_plan.restype = None
+    lib.emul_band_plan.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p]
+    lib.emul_band_plan(nfft, sample_rate, freq_min, freq_max, ALGO[algo], out)
+    return out[2], out[3]
 
 
 def params_plan(lib, p, n_frames, n_cus, layout=0, streams=1, dirs=1, dump=False, mixed=False, **sw):

@@ -740,3 +740,183 @@ extern "C" void emul_chain_plan(const long *in, long *out) {
                         (long)p.frames_elems, p.fused()};
     memcpy(out, v, sizeof(v));
 }
+
+// ---- the launch geometry of a batch of the chain and the band of a handle (csrc/chain_geom.hpp) -------------------------------------------
+// band[12] = skip_lo, skip_hi, yh_lo, yh_hi, q_lo, n_main, n_extra, extra_q[0], extra_q[1], solve0, nb, ok of a BandPlan
+static void band_out(const bf::BandPlan &b, long *o) {
+    const long v[12] = {b.skip_lo, b.skip_hi, b.yh_lo, b.yh_hi, b.q_lo, b.n_main, b.n_extra, b.extra_q[0], b.extra_q[1], b.solve0, b.nb, b.ok};
+    memcpy(o, v, sizeof(v));
+}
+static bf::BandPlan band_in(const long *v) {
+    bf::BandPlan b{};
+    b.skip_lo = (int)v[0]; b.skip_hi = (int)v[1]; b.yh_lo = (int)v[2]; b.yh_hi = (int)v[3]; b.q_lo = (int)v[4]; b.n_main = (int)v[5];
+    b.n_extra = (int)v[6]; b.extra_q[0] = (int)v[7]; b.extra_q[1] = (int)v[8]; b.solve0 = (int)v[9]; b.nb = (int)v[10]; b.ok = v[11] != 0;
+    return b;
+}
+extern "C" void emul_band_plan(int n_fft, double sample_rate, double freq_min, double freq_max, int algo, long *out) {
+    band_out(bf::band_plan(n_fft, sample_rate, freq_min, freq_max, algo), out);
+}
+// in[29] = ChainShape's members in order, mvdr_tile last
+static bf::ChainShape shape_in(const long *in) {
+    return bf::ChainShape{(int)in[0], (int)in[1], (int)in[2], (int)in[3], (int)in[4], (int)in[5], (int)in[6], (int)in[7], (int)in[8], in[9] != 0,
+                          in[10], (int)in[11], (int)in[12], (int)in[13], (int)in[14], (int)in[15], in[16] != 0, (int)in[17], in[18] != 0,
+                          in[19] != 0, in[20] != 0, (int)in[21], in[22] != 0, (int)in[23], in[24] != 0, (int)in[25], (int)in[26], (int)in[27],
+                          (int)in[28]};
+}
+// out[32 + 43]: the plan as emul_chain_plan gives it, then rows, track, ctrack, postfilter, post_rp and two spare zeros; then the geometry,
+// record by record in the order of ChainGeom (ok first, FastPlan's members in place, ChainZero as an integer, the LDS sizes in bytes)
+extern "C" void emul_chain_geom(const long *in, const long *band, long *out) {
+    const bf::ChainShape c = shape_in(in);
+    const bf::ChainPlan p = bf::chain_decide(c);
+    const bf::ChainGeom g = bf::chain_geom(c, p, band_in(band));
+    const long pv[32] = {p.algo, p.layout, (long)p.front, p.z48, (long)p.bins, p.mp, p.km, p.wps, (long)p.rec, p.expand, (long)p.istft, (long)p.tail,
+                         p.t0, p.t1, p.t2, p.yh32, p.mpf32, p.band_rows, p.yh_lo, p.yh_hi, (long)p.z_bytes, (long)p.yh_bytes, (long)p.yraw_elems,
+                         (long)p.frames_elems, p.fused(), p.rows, p.track, p.ctrack, p.postfilter, p.post_rp, 0, 0};
+    const bf::BinsGeom &b = g.bins;
+    const long gv[43] = {g.ok, g.stft.run_len, g.stft.blocks, g.fused.fpr, g.fused.rps, g.fused.total, g.fused.rpb, g.fused.grid, g.fused.tail_blocks,
+                         b.ew_blocks, b.lane_blocks, b.rec_blocks, b.expand_blocks, b.tile, b.tps, b.gx, b.gy, b.cov2d_grid,
+                         b.fp.q_lo, b.fp.n_main, b.fp.n_extra, b.fp.extra_q[0], b.fp.extra_q[1], b.fp.solve0, b.fp.nb, b.fp.tile, b.fp.tiles,
+                         b.fp.waves_per_stream, b.fast_grid, b.fast_km, b.wpc, (long)b.zero, b.gss_grid,
+                         g.istft.per_run, g.istft.runs_per_stream, g.istft.grid, g.istft.ola_grid,
+                         g.tail.smooth_grid, g.tail.smooth4_grid, g.tail.state_grid, (long)g.tail.lds_serial, (long)g.tail.lds_par, g.tail.nlms_grid};
+    memcpy(out, pv, sizeof(pv));
+    memcpy(out + 32, gv, sizeof(gv));
+}
+
+// Walks every item of every partition of a valid geometry through the header's own decoding functions (chain_*_item: the arithmetic of
+// the kernels) and checks that the items of a stream, in index order, tile its frames without a gap or an overlap.
+namespace {
+struct Cover {
+    long s = 0, next = 0, items = 0, dropped = 0;
+    bool ok = true;
+    void add(const bf::ChainItem &it, long n_streams, long span) {  // span: frames (pairs) per stream
+        ++items;
+        if (it.stream >= n_streams || it.n <= 0) { ++dropped; return; }
+        if (it.stream != s) {
+            if (it.stream != s + 1 || next != span) ok = false;
+            s = it.stream; next = 0;
+        }
+        if (it.t0 != next) ok = false;
+        next = it.t0 + it.n;
+    }
+    void finish(long n_streams, long span) { if (s != n_streams - 1 || next != span) ok = false; }
+    void out(long *o) const { o[0] = ok; o[1] = items; o[2] = dropped; }
+};
+}  // namespace
+// out[12] = front: ok, items, dropped; per-bin stage (the group kernels' tiles, cov2d_kernel's blocks, mvdr_fast_kernel's lanes): ok, items,
+// dropped; the highest frame index a lane of mvdr_fast_kernel prefetches (tA0 + dt + n_it - 1; -1: another kernel); backward transform: ok,
+// items, dropped; streams of mvdr_fast_kernel walked lane by lane (the first and the last; the others: lanes 0 and 63 of every wavefront)
+// "dropped": items the kernel's own guard drops (a grid rounded up to whole blocks, the lanes behind a stream's last (tile, problem)).
+// ok = -1: nothing to walk (no such stage, or a generic kernel: one (stream, frame) item per index, decoded by division alone)
+extern "C" void emul_chain_cover(const long *in, const long *band, long *out) {
+    using namespace bf;
+    const ChainShape c = shape_in(in);
+    const ChainPlan p = chain_decide(c);
+    const ChainGeom g = chain_geom(c, p, band_in(band));
+    for (int i = 0; i < 12; ++i) out[i] = -1;
+    if (!g.ok) return;
+    const long F = c.n_frames, S = c.n_streams, So = S * (c.algo == BF_GSC ? c.n_mics : c.n_dirs), Si = So * p.rows;
+    const long np = ((c.algo == BF_MCRA ? 1 : c.n_mics) + 1) / 2;
+    {
+        Cover cv;
+        if (p.fused()) {
+            const FusedGeom &f = g.fused;
+            for (long b = 0; b < (long)f.grid; ++b) {  // blocks: contiguous ranges of rounds, none empty
+                const long r0 = b * f.rpb, r1 = r0 + f.rpb < f.total ? r0 + f.rpb : f.total;
+                if (r0 >= r1) cv.ok = false;
+                for (long r = r0; r < r1; ++r) cv.add(chain_run_item(r, F, f.fpr, f.rps), S, F);
+            }
+            cv.finish(S, F);
+            cv.out(out);
+        } else if (p.front != ChainFront::kStftGeneric) {
+            const long L = g.stft.run_len, runs = (F + L - 1) / L;
+            for (long sr = 0; sr < S * runs; ++sr) {
+                const ChainItem a = chain_stft_item(sr * np, F, L, np), z = chain_stft_item(sr * np + np - 1, F, L, np);
+                if (a.sub != 0 || z.sub != np - 1 || a.stream != z.stream || a.t0 != z.t0 || a.n != z.n) cv.ok = false;  // the pairs of a run
+                cv.add(a, S, F);
+            }
+            cv.finish(S, F);
+            cv.out(out);
+        }
+    }
+    {
+        Cover cv;
+        const BinsGeom &b = g.bins;
+        if (p.bins == ChainBins::kMvdrLcmv) {
+            for (long x = 0; x < (long)b.gx; ++x) cv.add(chain_run_item(x, F, b.tile, b.tps), So, F);
+            cv.finish(So, F);
+            cv.out(out + 3);
+        } else if (p.bins == ChainBins::kCov2d) {
+            const int n_grp = (c.n_fft / 2 + 2 + 15) / 16;
+            const long units = (long)b.tps * So;
+            std::vector<int> seen(units, 0);
+            long dropped = 0;
+            for (long x = 0; x < (long)b.cov2d_grid; ++x) {
+                long unit; int grp;
+                chain_cov2d_block(x, c.n_fft, &unit, &grp);
+                if (unit >= units) { ++dropped; continue; }
+                if (seen[unit] != grp) cv.ok = false;  // the problem groups of a unit back to back, each once
+                ++seen[unit];
+            }
+            for (long u = 0; u < units; ++u) {
+                if (seen[u] != n_grp) cv.ok = false;
+                cv.add(chain_run_item(u, F, b.tile, b.tps), So, F);
+            }
+            cv.finish(So, F);
+            cv.out(out + 3);
+            out[4] = b.cov2d_grid; out[5] = dropped;
+        } else if (p.bins == ChainBins::kMvdrFast) {
+            const FastPlan &fp = b.fp;
+            long hi = -1, walked = 0;
+            Cover first, last;
+            for (long x = 0; x < (long)b.fast_grid; ++x) {
+                const long s = x / fp.waves_per_stream;
+                const bool full = s == 0 || s == So - 1;
+                Cover &cs = s == 0 ? first : last;
+                for (int lane = 0; lane < 64; lane += full ? 1 : 63) {
+                    long tA0, dt, n_it;
+                    const ChainItem it = chain_fast_lane(fp, F, x, lane, &tA0, &dt, &n_it);
+                    if (it.stream != s) cv.ok = false;
+                    if (tA0 + dt + n_it - 1 > hi) hi = tA0 + dt + n_it - 1;
+                    if (!full) continue;
+                    const long id = (x - s * fp.waves_per_stream) * 64 + lane;
+                    if (it.n <= 0) {  // the lanes behind the stream's last (tile, problem)
+                        if (id < (long)fp.tiles * fp.nb) cv.ok = false;
+                        ++cs.items; ++cs.dropped;
+                        continue;
+                    }
+                    const long tl = id / fp.nb, k = id % fp.nb, t0 = tl * fp.tile;
+                    if (it.sub != k || it.t0 != t0 || it.n != (F - t0 < fp.tile ? F - t0 : fp.tile)) cv.ok = false;
+                    if (k == 0) { ChainItem z = it; z.stream = 0; cs.add(z, 1, F); --cs.items; }  // problem slot 0 of every tile: the tiles of the stream
+                    ++cs.items;
+                }
+            }
+            first.finish(1, F);
+            walked = 1;
+            if (So > 1) { last.finish(1, F); walked = 2; }
+            cv.ok = cv.ok && first.ok && (So == 1 || last.ok);
+            cv.items = first.items + (So > 1 ? last.items : 0);
+            cv.dropped = first.dropped + (So > 1 ? last.dropped : 0);
+            cv.out(out + 3);
+            out[6] = hi; out[10] = walked;
+        }
+    }
+    {
+        Cover cv;
+        const IstftGeom &is = g.istft;
+        if (p.istft == ChainIstft::kF32) {
+            for (long x = 0; x < (long)is.grid * 8; ++x) cv.add(chain_run_item(x, F, is.per_run, is.runs_per_stream), Si, F);
+            cv.finish(Si, F);
+            cv.out(out + 7);
+        } else if (p.istft == ChainIstft::kW64) {
+            for (long x = 0; x < (long)is.grid * 4; ++x) cv.add(chain_w64_item(x, F, is.per_run, is.runs_per_stream), Si, (F + 1) / 2);
+            cv.finish(Si, (F + 1) / 2);
+            cv.out(out + 7);
+        } else if (p.istft == ChainIstft::kSmall || p.istft == ChainIstft::kSplit) {
+            const long runs = (F + is.per_run - 1) / is.per_run;  // the kernel's own count
+            for (long x = 0; x < Si * runs; ++x) cv.add(chain_run_item(x, F, is.per_run, runs), Si, F);
+            cv.finish(Si, F);
+            cv.out(out + 7);
+        }
+    }
+}

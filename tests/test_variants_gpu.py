@@ -55,6 +55,7 @@ CASES = [
     ({"BF_MVDR_TILE": "7"}, "mvdr", 8, (), 40, False, MIXED),                 # mvdr_fast_kernel<8, 1, false> + the fp32 backward transform
     ({"BF_MVDR_TILE": "7"}, "lcmv", 8, (-60.0, 90.0), 40, True, REF),         # ... <8, 3, true>
     ({"BF_MVDR_TILE": "7"}, "mvdr", 8, (), 40, False, REF),                   # ... <8, 1, true> + the fp64 backward transform (f64x2 rows)
+    ({"BF_MVDR_TILE": "600"}, "mvdr", 8, (), 700, False, REF),                # a forced tile is held to 512: tiles of 512 and 188 frames, a wavefront whose lanes straddle them, a prefetch that ends inside the workspace's slack
     ({}, "mvdr", 3, (), 30, False, REF),                                      # <4, 1, true>: an odd microphone count's zero partner channel
     ({}, "mvdr", 3, (), 30, False, MIXED),
     ({}, "lcmv", 16, (-60.0, 90.0), 24, False, REF),                          # cov2d_kernel<4, 2, true> + the fp64 backward transform
